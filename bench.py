@@ -22,11 +22,13 @@ verification, Levenshtein records, per-word dedupe, records left in HBM).
           (torch.distributed.run as a child process); under a launcher (WORLD_SIZE set)
           it is one of the ranks.
 
-The timed region is `--steps` steps between barrier + synchronize on both sides; when
-steps <= 64 it is repeated (9 regions, each primed by the warm-up) and the median region
-is reported, with every sample in `samples_ms` (a 0.6 ms region is a fragile basis).
+The timed region is `--steps` steps behind `--warmup` warm-up steps, between barrier +
+synchronize on both sides; `ms_per_step` = its time / steps.  `--reps R` times R such
+regions (each behind its own warm-up) and reports the median, every sample in `samples_ms`.
+`--dump-outputs DIR` writes the records of the last timed step to DIR (dump_outputs).
 
-Prints ONE JSON line (rank 0): the driver's contract plus
+Prints ONE JSON line (rank 0): the driver's contract (metric, value, unit, ms_per_step, ...,
+config).  A plain run measures nothing else; with `--full` the line also holds
   roofline      the dominant kernel (k_scan_rows: tokens -> records in one launch):
                 algorithmic bytes per launch (4 B per fan token + 32 B per record,
                 SURVEY 8(d)) / its average duration over the timed steps, from HIP
@@ -41,6 +43,8 @@ Prints ONE JSON line (rank 0): the driver's contract plus
                 of the same workload on the host cores, and as `reference_shaped` the
                 literal Python restatement on configs[0] in a 4-process pool, the way
                 search.py:381-385 runs the original
+and, at N > 1, `config.gather_verified` (the records the last step's receiver holds
+checked against every rank's own).
 """
 
 import argparse
@@ -55,8 +59,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0     # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0     # MI355X HBM3E peak
 MALL_BYTES = 256 << 20    # Infinity Cache
+DUMP_BYTES = 60 << 20     # --dump-outputs: record bytes at most (64 MB in all with the file headers)
 
 
 def parse(argv=None):
@@ -71,9 +76,14 @@ def parse(argv=None):
     ap.add_argument("--gather-root", default="rotate",
                     help="N > 1: rotate (step i's records to rank i mod N, one all_to_all per N steps; default), "
                          "step (the same with one gather per step) or 0 (a gather per step, always to rank 0)")
-    ap.add_argument("--reps", type=int, default=0,
-                    help="timed regions of --steps steps (default: 9 when steps <= 64, else 3); "
-                         "the median is reported")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="timed regions of --steps steps, each behind its own warm-up; the median "
+                         "is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, companions, "
+                         "cpu_baseline, and at N > 1 the check of the gathered records")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the records of the last timed step to DIR/<field>.npy (float64)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch: rendezvous port (default: a free one)")
     ap.add_argument("--works", type=int, default=0, help="override works (per rank)")
     ap.add_argument("--window", type=int, default=6)
@@ -87,10 +97,10 @@ def parse(argv=None):
     ap.add_argument("--scan-timing", type=int, default=0,
                     help="HIP events around the dominant kernel of every Nth search (default: every "
                          "search when steps <= 64, every 4th otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--no-reference-shaped", action="store_true",
                     help="skip the Python reference-shaped leg of cpu_baseline")
-    ap.add_argument("--no-companions", action="store_true")
+    ap.add_argument("--no-companions", action="store_true", help="--full without companions")
     ap.add_argument("--backend", default="nccl",
                     help="nccl (RCCL, one GPU per rank) or gloo (rehearsal: every rank "
                          "computes on GPU 0, records gathered through host memory)")
@@ -555,6 +565,28 @@ def c3_companions(ix, script, chars, coff, inflight, shards=8, passes=5):
     return out
 
 
+def dump_outputs(directory, parts):
+    """--dump-outputs: the fs_row records of the last timed step (one array per rank; `rank`
+    is added when there are several) as DIR/<field>.npy in float64, which
+    holds every uint32 field exactly, and their count as DIR/n_rows.npy.  The order in which
+    records land in a device buffer depends on scheduling, so they are sorted by all fields;
+    beyond DUMP_BYTES a fixed seeded sample of the sorted records is written."""
+    rows = {name: np.concatenate([p[name] for p in parts]).astype(np.float64)
+            for name in parts[0].dtype.names}
+    if len(parts) > 1:
+        rows["rank"] = np.concatenate([np.full(len(p), r, dtype=np.float64) for r, p in enumerate(parts)])
+    names = list(rows)
+    n = len(rows[names[0]])
+    order = np.lexsort([rows[k] for k in reversed(names)])
+    keep = DUMP_BYTES // (8 * len(names))
+    if n > keep:
+        order = order[np.sort(np.random.default_rng(0).choice(n, keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    for k in names:
+        np.save(os.path.join(directory, k + ".npy"), rows[k][order])
+    np.save(os.path.join(directory, "n_rows.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     args = parse()
     cmd = launcher_command(args, sys.argv[1:], os.environ)
@@ -570,7 +602,7 @@ def main():
     os.environ["FS_LANES"] = str(max(1, args.lanes))
     inflight = args.inflight or max(1, args.lanes)
     ref_shaped = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline
             and not args.no_reference_shaped):
         ref_shaped = cpu_reference_shaped(args.window)
     rank = int(os.environ.get("RANK", "0"))
@@ -716,7 +748,7 @@ def main():
     # the dominant kernel carries timing events on every search of a short run (the driver
     # passes --steps 20), on every 4th of a long one (an event record costs stream time)
     ix.set_scan_timing(args.scan_timing or (1 if args.steps <= 64 else 4))
-    reps = args.reps or (9 if args.steps <= 64 else 3)
+    reps = max(1, args.reps)
     samples = []
     it = 0
     for rep in range(reps):
@@ -755,10 +787,15 @@ def main():
         sys.stderr.write("total %.1f us\n" % (dt * 1e6))
     st = last["st"]
 
+    # the last step's records, before anything else writes the buffers: on the rank that
+    # received them (every rank's records there at N > 1)
+    if args.dump_outputs and gather.roots[last["buf"]] == rank:
+        dump_outputs(args.dump_outputs, gather.rows(last["buf"])[0])
+
     # outside the timed region: what rank 0 holds after the last gather must be every
     # rank's own records of that step (CRC of the 32-byte rows)
     gather_verified = None
-    if world > 1:
+    if world > 1 and args.full:
         import zlib
         last_corpus = corpora[last_step % rotate]
         own, _ = ix.search(last_corpus)
@@ -779,86 +816,8 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = total_works * args.steps / dt
-        if not scan_ms:                       # no timed launch fell into the region
-            ix.set_scan_timing(1)
-            scan_ms.append(ix.search_end(ix.search_begin(corpora[0], gather.bufs[0].data_ptr(), cap,
-                                                         packed=packed, header=True))[1].scan_ms)
-        kernel_ms = float(np.mean(scan_ms))
-        # the same kernel with nothing else on the GPU: one search at a time
-        ix.set_scan_timing(1)
-        alone = []
-        for i in range(12):
-            alone.append(ix.search_end(ix.search_begin(corpora[i % rotate], gather.bufs[0].data_ptr(), cap,
-                                                       packed=packed, header=True))[1].scan_ms)
-        alone_ms = float(np.mean(alone[2:]))
-        kernel = ix.kernel_name(corpora[0])
-        # ... and a whole search alone: an index with one lane puts the records into place
-        # inside the same launch (no k_compact behind it), one search at a time.  This is the
-        # figure `frac` is made of: what rocprofv3 reports for the kernel under --lanes 1
-        # (profiles/*_lanes1_kernel_stats.csv)
-        search_alone_ms, kernel1 = alone_ms, kernel
-        if int(os.environ.get("FS_LANES", "1")) > 1:
-            os.environ["FS_LANES"] = "1"
-            ix1 = ScriptIndex(script, swords, emb, normals, cfg=cfg)
-            os.environ["FS_LANES"] = str(max(1, args.lanes))
-            c1s = [ix1.corpus(t, o, chars, coff) for t, o in zip(toks, offs)]
-            ix1.set_scan_timing(4)     # (every 4th launch carries the events: an event record costs stream time)
-            one, tk = [], []
-            # one lane = one stream: the searches run strictly one after the other, each with the
-            # GPU to itself; three are kept queued so that the GPU does not fall idle (and drop
-            # its clock) between them while the host collects the previous one
-            for i in range(80):
-                tk.append(ix1.search_begin(c1s[i % rotate], gather.bufs[i % len(gather.bufs)].data_ptr(), cap,
-                                           packed=packed, header=True))
-                if len(tk) >= min(3, len(gather.bufs)):
-                    one.append(ix1.search_end(tk.pop(0))[1].scan_ms)
-            while tk:
-                one.append(ix1.search_end(tk.pop(0))[1].scan_ms)
-            one = [x for x in one[8:] if x > 0]
-            search_alone_ms = float(np.mean(one))
-            kernel1 = ix1.kernel_name(c1s[0])
-            ix1.close()
-        # what the launch shape costs for this many bytes with no work at all: a kernel that only
-        # reads the ids the way k_scan_rows does (rotating over the distinct batches: from HBM)
-        floor_ms = float(np.mean([ix.stream_floor(corpora[i % rotate], reps=4) for i in range(2 * rotate)]))
         rows_step = float(np.mean(rows_per_corpus))
         exact = st.path == abi.FS_MODE_EXACT
-        fused = kernel.startswith("k_scan_rows")
-        if exact:
-            # 4 B per fan token read + 32 B per emitted record.  k_scan_rows
-            # is the whole search (ids in, records out); the k_scan8 chain's first kernel
-            # only reads the ids.
-            algo_bytes = 4.0 * n_tok + (32.0 * rows_step if fused else 0.0)
-            note = "4 B per fan token" + (" + 32 B per record" if fused else "")
-        elif kernel.startswith("k_scan_near"):
-            # the integer prefilter of the LSH pipeline is the kernel the events bracket; the
-            # LSH work proper (keys, buckets, distances of the flagged windows) is k_lsh_verify
-            algo_bytes = 4.0 * n_tok
-            note = "4 B per fan token (prefilter only; the step is dominated by k_lsh_verify)"
-        else:
-            algo_bytes = float(st.windows_processed) * args.window * 212 * 4
-            note = "n rows of 212 float32 projections (848 B) per window (cache-served gather)"
-        step_bytes = 4.0 * n_tok + 32.0 * rows_step
-        achieved = algo_bytes / (search_alone_ms * 1e-3) / 1e9
-        resident = rotate * shard_bytes <= MALL_BYTES
-        traffic, traffic_src = None, None
-        build = _lib.source_hash()
-        tpath = os.path.join(ROOT, "profiles", "scan_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                rec = json.load(open(tpath))
-                # the PMC passes are separate runs (gpurun refuses counters next to a trace): the
-                # figure is taken only when it was measured on these very sources and this workload
-                if (rec.get("build") == build and rec.get("kernel") == kernel and rec.get("n_tok") == n_tok
-                        and rec.get("rotate") == rotate
-                        and rec.get("lanes") in (None, int(os.environ.get("FS_LANES", "1")))):
-                    traffic = rec.get("hbm_bytes_per_launch")
-                    traffic_src = "profiles/scan_traffic.json (build %s): %s" % (build, rec.get("source", "rocprofv3 --pmc"))
-                else:
-                    traffic_src = ("profiles/scan_traffic.json does not apply (its build %s, this build %s)"
-                                   % (rec.get("build"), build))
-            except Exception:
-                traffic = None
         out = {
             "metric": "fanworks/sec (6-gram search)",
             "value": value,
@@ -905,51 +864,130 @@ def main():
                        "path": ("exact-ngram-scan (synthetic table only: the exact-n-gram proof holds, "
                                 "c_max %.3f); tables with near-synonyms take the LSH pipeline, see "
                                 "companions.lsh_clustered_table" % ix.info["c_max"]) if exact else "lsh"},
-            "roofline": {"bound": "infinity-cache" if resident else "hbm",
-                         "kernel": kernel, "bytes_model": note,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": algo_bytes, "build": build,
-                         "search_ms_alone": search_alone_ms, "kernel_alone": kernel1,
-                         "stream_floor_ms": floor_ms,
-                         "stream_floor_frac": 4.0 * n_tok / (floor_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "stream_floor_note": "k_stream_floor: the ids of a batch read in k_scan_rows' launch shape "
-                                              "and nothing else (fs_stream_floor), one launch at a time: the part of "
-                                              "search_ms_alone that is the launch and the HBM stream",
-                         "launch_ms_alone": alone_ms,
-                         "frac_alone": algo_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "overlapped_launch_ms": kernel_ms, "timed_launches": len(scan_ms),
-                         "frac_overlapped": algo_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "step": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "step_bytes": step_bytes,
-                         "note": "achieved / frac: a whole search by itself (search_ms_alone: an index with one "
-                                 "lane = one stream, the one launch of `kernel_alone` takes ids in and puts the "
-                                 "records into place, HIP events on its dispatch; the launches run one after the "
-                                 "other, three queued, nothing else on the GPU).  launch_ms_alone: "
-                                 "the kernel in the shape the timed region launches it in (%d lanes: k_compact "
-                                 "puts the records into place behind it), also by itself; overlapped_launch_ms: "
-                                 "its dispatch-to-completion time inside the timed region, where %d searches "
-                                 "share the GPU; step = (4 B x tokens + 32 B x records) / ms_per_step"
-                                 % (int(os.environ.get("FS_LANES", "1")), inflight)},
         }
-        if not exact:
-            # a search of several launches: the whole search, and the kernel with the largest share
-            rec, _, _ = search_companion(ix, corpora[0], n_works, n_tok, inflight)
-            out["roofline"] = dict(rec["roofline"], kernels_us=rec["kernels_us"], build=build, traffic=None,
-                                   overlapped_first_kernel_ms=kernel_ms)
-        if world == 1 and not args.no_companions:
-            out["companions"] = companions(ix, corpora, toks, offs, chars, coff, words, script,
-                                           swords, emb, args.window, n_works)
-            if wl == "c2" and args.window == 6 and not args.works:
-                for c in corpora:
-                    c.close()
-                out["companions"].update(c3_companions(ix, script, chars, coff, inflight))
-                out["companions"]["command_end_to_end"] = command_companion()
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, script, swords, words, emb, normals, tpw,
-                                               chars, coff, args.cpu_seconds)
-            if ref_shaped is not None:
-                out["cpu_baseline"]["reference_shaped"] = ref_shaped
+        if args.full:
+            if not scan_ms:                       # no timed launch fell into the region
+                ix.set_scan_timing(1)
+                scan_ms.append(ix.search_end(ix.search_begin(corpora[0], gather.bufs[0].data_ptr(), cap,
+                                                             packed=packed, header=True))[1].scan_ms)
+            kernel_ms = float(np.mean(scan_ms))
+            # the same kernel with nothing else on the GPU: one search at a time
+            ix.set_scan_timing(1)
+            alone = []
+            for i in range(12):
+                alone.append(ix.search_end(ix.search_begin(corpora[i % rotate], gather.bufs[0].data_ptr(), cap,
+                                                           packed=packed, header=True))[1].scan_ms)
+            alone_ms = float(np.mean(alone[2:]))
+            kernel = ix.kernel_name(corpora[0])
+            # ... and a whole search alone: an index with one lane puts the records into place
+            # inside the same launch (no k_compact behind it), one search at a time.  This is the
+            # figure `frac` is made of: what rocprofv3 reports for the kernel under --lanes 1
+            # (profiles/*_lanes1_kernel_stats.csv)
+            search_alone_ms, kernel1 = alone_ms, kernel
+            if int(os.environ.get("FS_LANES", "1")) > 1:
+                os.environ["FS_LANES"] = "1"
+                ix1 = ScriptIndex(script, swords, emb, normals, cfg=cfg)
+                os.environ["FS_LANES"] = str(max(1, args.lanes))
+                c1s = [ix1.corpus(t, o, chars, coff) for t, o in zip(toks, offs)]
+                ix1.set_scan_timing(4)     # (every 4th launch carries the events: an event record costs stream time)
+                one, tk = [], []
+                # one lane = one stream: the searches run strictly one after the other, each with the
+                # GPU to itself; three are kept queued so that the GPU does not fall idle (and drop
+                # its clock) between them while the host collects the previous one
+                for i in range(80):
+                    tk.append(ix1.search_begin(c1s[i % rotate], gather.bufs[i % len(gather.bufs)].data_ptr(), cap,
+                                               packed=packed, header=True))
+                    if len(tk) >= min(3, len(gather.bufs)):
+                        one.append(ix1.search_end(tk.pop(0))[1].scan_ms)
+                while tk:
+                    one.append(ix1.search_end(tk.pop(0))[1].scan_ms)
+                one = [x for x in one[8:] if x > 0]
+                search_alone_ms = float(np.mean(one))
+                kernel1 = ix1.kernel_name(c1s[0])
+                ix1.close()
+            # what the launch shape costs for this many bytes with no work at all: a kernel that only
+            # reads the ids the way k_scan_rows does (rotating over the distinct batches: from HBM)
+            floor_ms = float(np.mean([ix.stream_floor(corpora[i % rotate], reps=4) for i in range(2 * rotate)]))
+            fused = kernel.startswith("k_scan_rows")
+            if exact:
+                # 4 B per fan token read + 32 B per emitted record.  k_scan_rows
+                # is the whole search (ids in, records out); the k_scan8 chain's first kernel
+                # only reads the ids.
+                algo_bytes = 4.0 * n_tok + (32.0 * rows_step if fused else 0.0)
+                note = "4 B per fan token" + (" + 32 B per record" if fused else "")
+            elif kernel.startswith("k_scan_near"):
+                # the integer prefilter of the LSH pipeline is the kernel the events bracket; the
+                # LSH work proper (keys, buckets, distances of the flagged windows) is k_lsh_verify
+                algo_bytes = 4.0 * n_tok
+                note = "4 B per fan token (prefilter only; the step is dominated by k_lsh_verify)"
+            else:
+                algo_bytes = float(st.windows_processed) * args.window * 212 * 4
+                note = "n rows of 212 float32 projections (848 B) per window (cache-served gather)"
+            step_bytes = 4.0 * n_tok + 32.0 * rows_step
+            achieved = algo_bytes / (search_alone_ms * 1e-3) / 1e9
+            resident = rotate * shard_bytes <= MALL_BYTES
+            traffic, traffic_src = None, None
+            build = _lib.source_hash()
+            tpath = os.path.join(ROOT, "profiles", "scan_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    rec = json.load(open(tpath))
+                    # the PMC passes are separate runs (no counters next to a trace): the
+                    # figure is taken only when it was measured on these very sources and this workload
+                    if (rec.get("build") == build and rec.get("kernel") == kernel and rec.get("n_tok") == n_tok
+                            and rec.get("rotate") == rotate
+                            and rec.get("lanes") in (None, int(os.environ.get("FS_LANES", "1")))):
+                        traffic = rec.get("hbm_bytes_per_launch")
+                        traffic_src = "profiles/scan_traffic.json (build %s): %s" % (build, rec.get("source", "rocprofv3 --pmc"))
+                    else:
+                        traffic_src = ("profiles/scan_traffic.json does not apply (its build %s, this build %s)"
+                                       % (rec.get("build"), build))
+                except Exception:
+                    traffic = None
+            out["roofline"] = {"bound": "infinity-cache" if resident else "hbm",
+                                "kernel": kernel, "bytes_model": note,
+                                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                                "algorithmic_bytes_per_launch": algo_bytes, "build": build,
+                                "search_ms_alone": search_alone_ms, "kernel_alone": kernel1,
+                                "stream_floor_ms": floor_ms,
+                                "stream_floor_frac": 4.0 * n_tok / (floor_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "stream_floor_note": "k_stream_floor: the ids of a batch read in k_scan_rows' launch shape "
+                                                     "and nothing else (fs_stream_floor), one launch at a time: the part of "
+                                                     "search_ms_alone that is the launch and the HBM stream",
+                                "launch_ms_alone": alone_ms,
+                                "frac_alone": algo_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "overlapped_launch_ms": kernel_ms, "timed_launches": len(scan_ms),
+                                "frac_overlapped": algo_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "step": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "step_bytes": step_bytes,
+                                "note": "achieved / frac: a whole search by itself (search_ms_alone: an index with one "
+                                        "lane = one stream, the one launch of `kernel_alone` takes ids in and puts the "
+                                        "records into place, HIP events on its dispatch; the launches run one after the "
+                                        "other, three queued, nothing else on the GPU).  launch_ms_alone: "
+                                        "the kernel in the shape the timed region launches it in (%d lanes: k_compact "
+                                        "puts the records into place behind it), also by itself; overlapped_launch_ms: "
+                                        "its dispatch-to-completion time inside the timed region, where %d searches "
+                                        "share the GPU; step = (4 B x tokens + 32 B x records) / ms_per_step"
+                                        % (int(os.environ.get("FS_LANES", "1")), inflight)}
+            if not exact:
+                # a search of several launches: the whole search, and the kernel with the largest share
+                rec, _, _ = search_companion(ix, corpora[0], n_works, n_tok, inflight)
+                out["roofline"] = dict(rec["roofline"], kernels_us=rec["kernels_us"], build=build, traffic=None,
+                                       overlapped_first_kernel_ms=kernel_ms)
+            if world == 1 and not args.no_companions:
+                out["companions"] = companions(ix, corpora, toks, offs, chars, coff, words, script,
+                                               swords, emb, args.window, n_works)
+                if wl == "c2" and args.window == 6 and not args.works:
+                    for c in corpora:
+                        c.close()
+                    out["companions"].update(c3_companions(ix, script, chars, coff, inflight))
+                    out["companions"]["command_end_to_end"] = command_companion()
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg, script, swords, words, emb, normals, tpw,
+                                                   chars, coff, args.cpu_seconds)
+                if ref_shaped is not None:
+                    out["cpu_baseline"]["reference_shaped"] = ref_shaped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -49,10 +49,10 @@ pmc() {          # name, counter, bench args...
   rm -rf $OUT/pmc_${name}_$ctr
 }
 
-B="--no-companions --no-cpu-baseline"
+B="--full --no-companions --no-cpu-baseline"
 if [ "$part" = part1 ]; then
   echo "== default bench line (N=1, c2, four distinct batches, 4 lanes), and the driver's form"
-  run ${R}_c2_bench.json bench.py
+  run ${R}_c2_bench.json bench.py --full
   run ${R}_c2_bench_steps20.json bench.py --steps 20 --warmup 5 $B
   echo "== one lane (searches one after the other) and one resident batch"
   run ${R}_c2_bench_lanes1.json bench.py --lanes 1 --inflight 2 $B

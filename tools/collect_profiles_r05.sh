@@ -43,10 +43,10 @@ pmc() {          # name, counter, bench args...
   rm -rf $OUT/pmc_${name}_$ctr
 }
 
-B="--no-companions --no-cpu-baseline"
+B="--full --no-companions --no-cpu-baseline"
 if [ "$part" = part1 ]; then
   echo "== the driver's form with every companion, and 200 steps"
-  run ${R}_c2_bench_steps20.json bench.py --steps 20 --warmup 5
+  run ${R}_c2_bench_steps20.json bench.py --steps 20 --warmup 5 --full
   run ${R}_c2_bench.json bench.py $B
   run ${R}_c2_bench_lanes1.json bench.py --lanes 1 --inflight 2 $B
   echo "== rocprofv3 kernel stats: the default command, one lane"
