@@ -17,7 +17,7 @@ _LIB = None
 
 SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_index_info_get", "fs_index_destroy", "fs_corpus_create",
-           "fs_corpus_destroy", "fs_search_corpus", "fs_search",
+           "fs_corpus_destroy", "fs_corpus_view", "fs_search_corpus", "fs_search",
            "fs_scan_benchmark", "fs_corpus_update_begin", "fs_corpus_update_end",
            "fs_host_alloc", "fs_host_free", "fs_rows_unpack", "fs_rows_unpack8",
            "fs_reuse_histogram", "fs_reuse_histogram_rows",
@@ -118,6 +118,8 @@ def load():
     L.fs_corpus_create.argtypes = [
         C.c_void_p, u32p, u32p, u64p, C.c_uint64, u32p, u64p, C.c_uint64,
         C.POINTER(C.c_void_p)]
+    L.fs_corpus_view.restype = C.c_int
+    L.fs_corpus_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.fs_corpus_destroy.restype = None
     L.fs_corpus_destroy.argtypes = [C.c_void_p]
     L.fs_search_corpus.restype = C.c_int

@@ -8,6 +8,15 @@ import argparse
 import sys
 
 
+class _Scripts(argparse.Action):
+    """script [script ...]: args.scripts holds them all, args.script the first (what format,
+    validate and a one-script search read)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.scripts = list(values)
+        namespace.script = values[0]
+
+
 def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
@@ -23,8 +32,14 @@ def build_parser():
         'search', help='compare fanworks with the original script')
     search_parser.add_argument('fan_works', action='store',
                                help='directory of fanwork text files')
-    search_parser.add_argument('script', action='store',
-                               help='filename for markup version of script')
+    search_parser.add_argument('script', action=_Scripts, nargs='+', metavar='script',
+                               help='filename for markup version of script; with several, every '
+                                    'batch of fan works is read once and searched with each script, '
+                                    'whose files go to <out-dir>/<script name>/')
+    search_parser.add_argument('--out-dir', default=None,
+                               help='directory of the batch files and the dated file (default: the '
+                                    'working directory; with several scripts a directory per script '
+                                    'inside it)')
     search_parser.add_argument('-n', '--num-works', default=-1, type=int,
                                help="number of works to search (for subsampling)")
     search_parser.add_argument('-s', '--skip-works', default=0, type=int,
@@ -92,6 +107,10 @@ def _search(args):
         os.environ['FANDOM_SEARCH_UNIQUE_FILTER'] = str(args.unique_filter)
     if getattr(args, 'listing', None):
         os.environ['FANDOM_SEARCH_LISTING'] = args.listing
+    try:
+        search.check_scripts(args)          # (before the library loads or a work is read)
+    except ValueError as e:
+        sys.exit('ao3.py search: error: %s' % e)
     return search.analyze(args)
 
 

@@ -569,7 +569,8 @@ extern "C" int fs_index_share_counts(fs_index* ix, uint64_t* out8) {
 
 extern "C" const char* fs_search_kernel_name(fs_index* ix, fs_corpus* c) {
   static thread_local char name[64];
-  if (!ix || !c || c->ix != ix) return "";
+  if (!ix || !c || c->ix != ix || (c->is_view && !c->base)) return "";
+  if (c->is_view) fs_view_sync(c);
   const int n = (int)ix->cfg.window_size;
   const bool exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
   if (!exact) {
@@ -606,7 +607,35 @@ extern "C" void fs_index_destroy(fs_index* ix) {
   delete ix;
 }
 
+// A view's batch members are the base's buffers: refreshed from the base before every use
+// (its sizes, flags and buffers may have changed with an fs_corpus_update_begin), and let go
+// of before the view's own members are freed.
+void fs_view_sync(fs_corpus* v) {
+  const fs_corpus* b = v->base;
+  v->n_tok = b->n_tok; v->n_works = b->n_works; v->n_str = b->n_str;
+  v->windows = b->windows; v->has_oov = b->has_oov; v->has_str = b->has_str;
+  v->d_tok.p = b->d_tok.p; v->d_tok.n = b->d_tok.n;
+  v->d_str.p = b->d_str.p; v->d_str.n = b->d_str.n;
+  v->d_chars.p = b->d_chars.p; v->d_chars.n = b->d_chars.n;
+  v->d_blk_work.p = b->d_blk_work.p; v->d_blk_work.n = b->d_blk_work.n;
+  v->d_blk4.p = b->d_blk4.p; v->d_blk4.n = b->d_blk4.n;
+  v->d_work_off.p = b->d_work_off.p; v->d_work_off.n = b->d_work_off.n;
+  v->d_coff.p = b->d_coff.p; v->d_coff.n = b->d_coff.n;
+}
+
+static void fs_view_unalias(fs_corpus* v) {
+  v->d_tok.p = nullptr; v->d_tok.n = 0;
+  v->d_str.p = nullptr; v->d_str.n = 0;
+  v->d_chars.p = nullptr; v->d_chars.n = 0;
+  v->d_blk_work.p = nullptr; v->d_blk_work.n = 0;
+  v->d_blk4.p = nullptr; v->d_blk4.n = 0;
+  v->d_work_off.p = nullptr; v->d_work_off.n = 0;
+  v->d_coff.p = nullptr; v->d_coff.n = 0;
+  v->n_tok = v->n_works = v->n_str = v->windows = 0;
+}
+
 fs_corpus::~fs_corpus() {
+  if (is_view) fs_view_unalias(this);
   if (ev_ready) (void)hipEventDestroy(ev_ready);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (h_check) (void)hipHostFree(h_check);
@@ -620,6 +649,7 @@ extern "C" int fs_corpus_update_begin(fs_corpus* c, const uint32_t* tok_vec,
                                       const uint32_t* tok_str, const uint64_t* work_off,
                                       uint64_t n_works) {
   if (!c || !work_off) { fs_set_error("null argument"); return FS_E_INVALID; }
+  if (c->is_view) { fs_set_error("a view is updated through its base corpus"); return FS_E_INVALID; }
   fs_index* ix = c->ix;
   if (!ix) { fs_set_error("the corpus's index has been destroyed"); return FS_E_INVALID; }
   if (work_off[0] != 0) { fs_set_error("work_off[0] must be 0"); return FS_E_INVALID; }
@@ -645,7 +675,17 @@ extern "C" int fs_corpus_update_begin(fs_corpus* c, const uint32_t* tok_vec,
                    "before the corpus is updated");
       return FS_E_INVALID;
     }
+  // ... and so would one of a view of it, in its own index's slots
+  for (const fs_corpus* v : c->views)
+    if (v->ix)
+      for (int i = 0; i < FS_SEARCH_SLOTS; ++i)
+        if (v->ix->slots[i].busy && v->ix->slots[i].c == v) {
+          fs_set_error("a search of a view of this corpus is still in flight: finish it "
+                       "(fs_search_corpus_end) before the corpus is updated");
+          return FS_E_INVALID;
+        }
   if (c->pending) FS_HIP(hipEventSynchronize(c->ev_ready));
+  ++c->gen;                            // views rebuild their index-derived tables
   hipStream_t cs = c->copy_stream;
   c->n_tok = T; c->n_works = n_works; c->windows = windows;
   c->has_str = tok_str != nullptr;
@@ -678,12 +718,10 @@ extern "C" int fs_corpus_update_begin(fs_corpus* c, const uint32_t* tok_vec,
 
 // Wait for the upload, read the validation result, prepare what the search of
 // this batch needs (LSH structures for OOV ids, the per-n-gram Levenshtein table).
-extern "C" int fs_corpus_update_end(fs_corpus* c) {
-  if (!c) return FS_E_INVALID;
-  if (!c->pending) return FS_OK;
-  fs_index* ix = c->ix;
-  if (!ix) { fs_set_error("the corpus's index has been destroyed"); return FS_E_INVALID; }
-  FS_ENTER(ix->device);
+// The upload's half: wait for it and read the validation (ix: an index with the corpus's vector
+// count -- its own, or that of a view whose search comes first).
+static int corpus_finish_upload(fs_corpus* c, const fs_index* ix) {
+  c->prep_due = false;
   FS_HIP(hipEventSynchronize(c->ev_ready));
   c->pending = false;
   const uint32_t max_row_plus1 = c->h_check[0], any_oov = c->h_check[1], max_str_plus1 = c->h_check[2];
@@ -702,6 +740,13 @@ extern "C" int fs_corpus_update_end(fs_corpus* c) {
     return FS_E_INVALID;
   }
   c->has_oov = any_oov != 0;
+  c->prep_due = true;
+  return FS_OK;
+}
+
+// The index's half: the tables a search of this batch on `ix` needs.  An own corpus builds them
+// in fs_corpus_update_end, a view at its first search after the base's generation changed.
+static int corpus_prepare(fs_index* ix, fs_corpus* c) {
   // out-of-vocabulary vectors are outside the exact n-gram proof: such a batch
   // goes through the LSH pipeline (built now if the index did not need it before)
   if (c->has_oov && ix->info.path == FS_MODE_EXACT) FS_TRY(fs_lsh_build(ix));
@@ -777,6 +822,72 @@ extern "C" int fs_corpus_update_end(fs_corpus* c) {
   return FS_OK;
 }
 
+extern "C" int fs_corpus_update_end(fs_corpus* c) {
+  if (!c) return FS_E_INVALID;
+  if (c->is_view) { fs_set_error("a view is updated through its base corpus"); return FS_E_INVALID; }
+  if (!c->pending && !c->prep_due) return FS_OK;
+  fs_index* ix = c->ix;
+  if (!ix) { fs_set_error("the corpus's index has been destroyed"); return FS_E_INVALID; }
+  FS_ENTER(ix->device);
+  if (c->pending) FS_TRY(corpus_finish_upload(c, ix));
+  c->prep_due = false;
+  return corpus_prepare(ix, c);
+}
+
+// What a search of `c` on `ix` needs before it is queued.  An own corpus: its upload finished
+// (fs_corpus_update_end).  A view: the base's upload checked (the host wait an own corpus pays
+// there), the batch members taken from the base, and after a new batch of the base the
+// view's own tables, on its own index's stream behind the base's upload.
+static int corpus_ready(fs_index* ix, fs_corpus* c) {
+  if (!c->is_view) return fs_corpus_update_end(c);
+  fs_corpus* b = c->base;
+  if (!b) { fs_set_error("the base corpus of this view has been destroyed"); return FS_E_INVALID; }
+  if (b->pending) FS_TRY(corpus_finish_upload(b, ix));
+  fs_view_sync(c);
+  if (c->base_gen != b->gen) {
+    c->base_gen = b->gen;
+    FS_HIP(hipStreamWaitEvent(ix->stream, b->ev_ready, 0));
+    FS_TRY(corpus_prepare(ix, c));
+  }
+  return FS_OK;
+}
+
+extern "C" int fs_corpus_view(fs_index* ix, fs_corpus* base, fs_corpus** out) {
+  if (!ix || !base || !out) { fs_set_error("null argument"); return FS_E_INVALID; }
+  *out = nullptr;
+  if (base->is_view) { fs_set_error("the base must be a corpus of its own, not a view"); return FS_E_INVALID; }
+  const fs_index* bx = base->ix;
+  if (!bx) { fs_set_error("the base corpus's index has been destroyed"); return FS_E_INVALID; }
+  if (bx == ix) { fs_set_error("the base corpus belongs to this index: search it directly"); return FS_E_INVALID; }
+  if (bx->device != ix->device) {
+    fs_set_error("the base corpus is on device %d, the index on device %d", bx->device, ix->device);
+    return FS_E_INVALID;
+  }
+  if (bx->cfg.window_size != ix->cfg.window_size) {
+    fs_set_error("window size %u differs from the base corpus's index (%u)", ix->cfg.window_size,
+                 bx->cfg.window_size);
+    return FS_E_INVALID;
+  }
+  if (bx->cfg.emb_dim != ix->cfg.emb_dim) {
+    fs_set_error("emb_dim %u differs from the base corpus's index (%u)", ix->cfg.emb_dim, bx->cfg.emb_dim);
+    return FS_E_INVALID;
+  }
+  if (bx->n_vec != ix->n_vec) {
+    fs_set_error("vector count %llu differs from the base corpus's index (%llu)",
+                 (unsigned long long)ix->n_vec, (unsigned long long)bx->n_vec);
+    return FS_E_INVALID;
+  }
+  FS_ENTER(ix->device);
+  fs_corpus* v = new (std::nothrow) fs_corpus();
+  if (!v) return FS_E_NOMEM;
+  v->ix = ix; v->is_view = true; v->base = base;
+  v->base_gen = 0;                     // (a base's generation is 1 and up: the first search builds)
+  base->views.push_back(v);
+  ix->corpora.push_back(v);
+  *out = v;
+  return FS_OK;
+}
+
 extern "C" int fs_corpus_create(fs_index* ix, const uint32_t* tok_vec, const uint32_t* tok_str,
                                 const uint64_t* work_off, uint64_t n_works,
                                 const uint32_t* str_chars, const uint64_t* str_off, uint64_t n_str,
@@ -825,6 +936,24 @@ extern "C" void fs_host_free(void* p) {
 
 extern "C" void fs_corpus_destroy(fs_corpus* c) {
   if (!c) return;
+  if (c->is_view && c->base) {
+    std::vector<fs_corpus*>& vs = c->base->views;
+    for (size_t i = 0; i < vs.size(); ++i)
+      if (vs[i] == c) { vs.erase(vs.begin() + (long)i); break; }
+  }
+  // the views of this corpus are detached: their searches in flight are waited for (they read
+  // this corpus's buffers) and forgotten, every later call on them but fs_corpus_destroy is refused
+  for (fs_corpus* v : c->views) {
+    if (fs_index* vx = v->ix) {
+      (void)hipSetDevice(vx->device);
+      for (int l = 0; l < FS_LANES; ++l) (void)hipStreamSynchronize(vx->lanes[l].stream);
+      for (int i = 0; i < FS_SEARCH_SLOTS; ++i)
+        if (vx->slots[i].c == v) vx->slots[i].c = nullptr;
+    }
+    fs_view_unalias(v);
+    v->base = nullptr;
+  }
+  c->views.clear();
   if (c->ix) {                         // nullptr: the index went first (fs_index_destroy)
     fs_index* ix = c->ix;
     (void)hipSetDevice(ix->device);
@@ -1026,6 +1155,7 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
     fs_set_error("null or mismatched handle");
     return FS_E_INVALID;
   }
+  if (c->is_view && !c->base) { fs_set_error("the base corpus of this view has been destroyed"); return FS_E_INVALID; }
   const bool header = (rows_mode & FS_ROWS_HEADER) != 0;
   rows_mode &= ~FS_ROWS_HEADER;
   if (header && rows_mode == FS_ROWS_HOST) {
@@ -1041,7 +1171,7 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
   static const bool trace_begin = getenv("FS_TRACE_BEGIN") != nullptr;
   const auto tb0 = std::chrono::steady_clock::now();
   FS_ENTER(ix->device);
-  FS_TRY(fs_corpus_update_end(c));          // no-op unless an upload is in flight
+  FS_TRY(corpus_ready(ix, c));              // no-op unless an upload is in flight (own corpus)
   const uint32_t id = ix->next_slot % FS_SEARCH_SLOTS;
   fs_index::Slot& sl = ix->slots[id];
   if (sl.busy) {
@@ -1059,6 +1189,8 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
   sl.header = header;
   sl.lane = (int)(id % (uint32_t)ix->n_lanes);
   const fs_index::Lane& ln = ix->lanes[sl.lane];
+  // a view's search reads the base's ids: behind the base's upload on the device
+  if (c->is_view) FS_HIP(hipStreamWaitEvent(ln.stream, c->base->ev_ready, 0));
   sl.exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
   static const bool host8 = !getenv("FS_HOST_WIRE8") || atoi(getenv("FS_HOST_WIRE8")) != 0;
   sl.host_wire8 = rows_mode == FS_ROWS_HOST && sl.exact && ix->n_script < (1ull << 18) && host8;
@@ -1355,7 +1487,7 @@ extern "C" int fs_search_corpus_end(fs_index* ix, uint32_t ticket, uint64_t* n_r
         FS_HIP(hipMemcpyAsync(ix->h_stage, ln.w_rows.p, bytes, hipMemcpyDeviceToHost, ln.stream));
         FS_HIP(hipStreamSynchronize(ln.stream));
       }
-      fs_expand_rows8_host(ix, reinterpret_cast<const uint32_t*>(ix->h_stage), hs.n_rows, sl.c->h_work_off.data(),
+      fs_expand_rows8_host(ix, reinterpret_cast<const uint32_t*>(ix->h_stage), hs.n_rows, sl.c->host_work_off(),
                            sl.c->n_works, ix->h_selfdist.data(), sl.rows);
     } else {
       FS_HIP(hipMemcpyAsync(sl.rows, ln.w_rows.p, (size_t)hs.n_rows * sizeof(fs_row),
@@ -1405,6 +1537,7 @@ extern "C" int fs_debug_stamps(fs_index* ix, uint32_t lane, uint64_t* out, uint6
 extern "C" int fs_scan_benchmark(fs_index* ix, fs_corpus* c, uint32_t reps, double* avg_ms) {
   if (!ix || !c || c->ix != ix || !avg_ms || reps == 0) return FS_E_INVALID;
   FS_ENTER(ix->device);
+  if (c->is_view) FS_TRY(corpus_ready(ix, c));
   hipStream_t s = ix->stream;
   const int tpl = fs_scan_tpl(ix, c->n_tok);
   const uint32_t n_bm = (uint32_t)((c->n_tok + 64 * tpl - 1) / (64 * tpl));
@@ -1425,6 +1558,7 @@ extern "C" int fs_scan_benchmark(fs_index* ix, fs_corpus* c, uint32_t reps, doub
 extern "C" int fs_stream_floor(fs_index* ix, fs_corpus* c, uint32_t reps, double* avg_ms) {
   if (!ix || !c || c->ix != ix || !avg_ms || reps == 0) return FS_E_INVALID;
   FS_ENTER(ix->device);
+  if (c->is_view) FS_TRY(corpus_ready(ix, c));
   return fs_launch_stream_floor(ix, c, reps, avg_ms);
 }
 

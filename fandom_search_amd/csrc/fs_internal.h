@@ -366,6 +366,13 @@ struct fs_index {
   ~fs_index();
 };
 
+// Two kinds of member.  Batch data -- the sizes and flags of the works, the host work offsets,
+// d_tok, d_str, d_work_off, d_blk_work, d_blk4, d_check, the fan string table d_chars / d_coff /
+// n_str, the copy stream and its event -- belong to the corpus that uploads them.  Index-derived
+// data -- d_levtab, d_gbest, d_strrec, d_ctab, d_gramtab_*, d_ctok, d_selflev and their *_ready
+// flags -- are made for one index.  A view (fs_corpus_view) owns only the second kind: its batch
+// members alias the base's and are refreshed from it before every use (fs_view_sync), because
+// fs_corpus_update_begin on the base may reallocate them.
 struct fs_corpus {
   fs_index* ix = nullptr;
   uint64_t n_tok = 0, n_works = 0, n_str = 0;
@@ -393,9 +400,19 @@ struct fs_corpus {
   bool ctok_ready = false;
   DBuf<uint32_t> d_selflev;            // LSH pipeline, string id == vector id: Levenshtein of script window w
   bool selflev_ready = false;          // against the strings of its own ids (k_selflev), FS_NONE: not known
+  // views (fs_corpus_view)
+  bool is_view = false;                // stays set when the base goes (a detached view)
+  fs_corpus* base = nullptr;           // view: the corpus whose works it searches (nullptr: detached)
+  uint64_t base_gen = 0;               // view: the base generation its index-derived tables are for
+  uint64_t gen = 0;                    // own corpus: advanced by every fs_corpus_update_begin
+  bool prep_due = false;               // own corpus: upload checked (by a view's search), tables not built yet
+  std::vector<fs_corpus*> views;       // own corpus: its live views
+  const uint64_t* host_work_off() const { return is_view ? base->h_work_off.data() : h_work_off.data(); }
   CorpusDev dev() const;
   ~fs_corpus();
 };
+
+void fs_view_sync(fs_corpus* v);       // fs_api.hip: a view's batch members from its base
 
 // ---- kernel launchers (fs_scan.hip / fs_post.hip / fs_build.hip) ----------
 // What a scan launch may produce beyond the bitmap (eight-tokens-per-lane kernel only):

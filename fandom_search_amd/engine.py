@@ -54,6 +54,7 @@ class Corpus(object):
             abi.ptr(chars, C.c_uint32), abi.ptr(off, C.c_uint64),
             len(off) - 1, C.byref(self._h)), "fs_corpus_create")
         index._corpora.add(self)
+        self._views = weakref.WeakSet()        # live CorpusView objects of this corpus
         _LIVE.add(self)
 
     def update_begin(self, tok_vec, work_off, tok_str=None):
@@ -74,6 +75,48 @@ class Corpus(object):
         _lib.check(_lib.load().fs_corpus_update_end(self._h), "fs_corpus_update_end")
 
     def close(self):
+        """Closes the views of this corpus first (the library would only detach them)."""
+        for v in list(getattr(self, "_views", ())):
+            v.close()
+        if self._h:
+            _lib.load().fs_corpus_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CorpusView(object):
+    """The works of another index's Corpus, searched by `index` without a second upload
+    (fs_corpus_view): ScriptIndex.search / search_begin / search_end take it like a Corpus.
+    Sizes are the base's as they stand; a new batch goes in through the base's update_begin."""
+
+    def __init__(self, index, base):
+        if not isinstance(base, Corpus):
+            raise TypeError("the base of a view is a Corpus")
+        self.index = index
+        self.base = base
+        self._h = C.c_void_p()
+        _lib.check(_lib.load().fs_corpus_view(index._h, base._h, C.byref(self._h)), "fs_corpus_view")
+        index._corpora.add(self)
+        base._views.add(self)
+        _LIVE.add(self)
+
+    n_tok = property(lambda self: self.base.n_tok)
+    n_works = property(lambda self: self.base.n_works)
+    work_off = property(lambda self: self.base.work_off)
+
+    def update_begin(self, tok_vec, work_off, tok_str=None):
+        raise ValueError("a corpus view is updated through its base corpus")
+
+    def update_end(self):
+        raise ValueError("a corpus view is updated through its base corpus")
+
+    def close(self):
+        # (also after the base has gone: the library only frees the view's own tables)
         if self._h:
             _lib.load().fs_corpus_destroy(self._h)
             self._h = C.c_void_p()
@@ -195,6 +238,11 @@ class ScriptIndex(object):
 
     def corpus(self, tok_vec, work_off, str_chars, str_off, tok_str=None):
         return Corpus(self, tok_vec, work_off, str_chars, str_off, tok_str)
+
+    def corpus_view(self, base):
+        """A corpus of this index over the works of `base`, a Corpus of another index on the
+        same device with the same window size, emb_dim and vector table (fs_corpus_view)."""
+        return CorpusView(self, base)
 
     def search(self, corpus, cap=None, reuse=False):
         """Rows (numpy structured array, host) and stats of one batch.  `reuse`: the rows

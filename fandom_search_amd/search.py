@@ -606,6 +606,15 @@ class AnnIndexSearch(object):
         ht = self.__dict__.setdefault("host_times", {"encode": 0.0, "search": 0.0})
         t0 = time.perf_counter()
         tok_str, tok_vec, off, corpus = self._corpus_of_ids(tok_str, tok_vec, off)
+        ht["corpus to the GPU"] = ht.get("corpus to the GPU", 0.0) + time.perf_counter() - t0
+        return self._search_corpus(corpus, tok_str, off)
+
+    def _search_corpus(self, corpus, tok_str, off):
+        """(rows, fan words) of a batch already on the GPU (`corpus`: this index's corpus of the
+        batch or a view of another index's, ScriptSet)."""
+        import time
+        v = self.vocab
+        ht = self.__dict__.setdefault("host_times", {"encode": 0.0, "search": 0.0})
         t1 = time.perf_counter()
         rows, st = self.engine.search(corpus, reuse=True)
         rows = rows.copy()                        # (the engine's buffer is written by the next batch)
@@ -619,7 +628,7 @@ class AnnIndexSearch(object):
         words = list(map(v.strings.__getitem__, self.last_word_sids.tolist())) \
             if getattr(self, "want_words", True) else None
         t3 = time.perf_counter()
-        for k, dt in (("corpus to the GPU", t1 - t0), ("fs_search_corpus", t2 - t1), ("fan words of the records", t3 - t2)):
+        for k, dt in (("fs_search_corpus", t2 - t1), ("fan words of the records", t3 - t2)):
             ht[k] = ht.get(k, 0.0) + dt
         return rows, words
 
@@ -668,6 +677,53 @@ class AnnIndexSearch(object):
         script columns into the 12-field records of search.py:203-217."""
         return join_records(filenames, rows, words, self.word_lowercase,
                             self.orth_id, self.character, self.scene)
+
+
+class ScriptSet(object):
+    """Several scripts searched over one fan corpus: each batch is read, tokenised, encoded
+    and uploaded once, by the first searcher, and searched by every index -- the first on
+    its own corpus, the others on views of it (ScriptIndex.corpus_view).  The searchers are
+    built before the first batch (building one adds its script's words to the vocabulary)
+    and share one vocabulary."""
+
+    def __init__(self, searchers):
+        self.searchers = list(searchers)
+        if not self.searchers:
+            raise ValueError("a ScriptSet needs at least one searcher")
+        if any(s.vocab is not self.searchers[0].vocab for s in self.searchers):
+            raise ValueError("the searchers of a ScriptSet share one vocabulary")
+        self._base = None             # the first searcher's corpus the views are of
+        self._views = []
+
+    def search_rows(self, filenames):
+        """[(rows, fan word string ids, stats)] of one batch, one entry per script."""
+        import time
+        first = self.searchers[0]
+        t0 = time.perf_counter()
+        enc = first._encode_files(filenames)
+        t1 = time.perf_counter()
+        tok_str, tok_vec, off, base = first._corpus_of_ids(*enc)
+        ht = first.__dict__.setdefault("host_times", {"encode": 0.0, "search": 0.0})
+        ht["encode"] += t1 - t0
+        ht["corpus to the GPU"] = ht.get("corpus to the GPU", 0.0) + time.perf_counter() - t1
+        if base is not self._base:
+            # a new base corpus (the string table grew): new views of it
+            for v in self._views:
+                v.close()
+            self._views = [s.engine.corpus_view(base) for s in self.searchers[1:]]
+            self._base = base
+        out = []
+        for s, corpus in zip(self.searchers, [base] + self._views):
+            if s is not first:
+                s.last_oov_rate = first.last_oov_rate
+            rows, _ = s._search_corpus(corpus, tok_str, off)
+            out.append((rows, s.last_word_sids, s.last_stats))
+        return out
+
+    def close(self):
+        for v in self._views:
+            v.close()
+        self._views, self._base = [], None
 
 
 def join_records(filenames, rows, words, word_lowercase, orth_id, character,
@@ -754,6 +810,42 @@ def unused_result_name(filename_base):
     return name_check
 
 
+def script_stem(script_filename):
+    """sw-new-hope for scripts/sw-new-hope.txt: the name of a script's output directory."""
+    return os.path.splitext(os.path.basename(script_filename))[0]
+
+
+def script_out_dirs(scripts, out_dir=None):
+    """Where `ao3.py search` writes the files of each script: one script writes into `out_dir`
+    ('' without one: the working directory, as the reference does); several write into
+    <out_dir or .>/<script stem>/ each.  Two scripts with the same stem are refused."""
+    scripts = list(scripts)
+    if not scripts:
+        raise ValueError("no script given")
+    if len(scripts) == 1:
+        return [out_dir or '']
+    seen = {}
+    for sc in scripts:
+        stem = script_stem(sc)
+        if stem in seen:
+            raise ValueError("scripts %r and %r would both write to %r: every script of one "
+                             "search needs a file name of its own" % (seen[stem], sc, stem))
+        seen[stem] = sc
+    return [os.path.join(out_dir or '.', script_stem(sc)) for sc in scripts]
+
+
+def check_scripts(args):
+    """(scripts, output directory of each) of a search, refused before any file is read or the
+    library is loaded: duplicate stems, or several scripts under a launcher."""
+    scripts = list(getattr(args, 'scripts', None) or [args.script])
+    dirs = script_out_dirs(scripts, getattr(args, 'out_dir', None))
+    from . import dist
+    if len(scripts) > 1 and dist.env_world()[2] > 1:
+        raise ValueError("several scripts in one search run in a single process: under a launcher "
+                         "(WORLD_SIZE > 1) give one script per run")
+    return scripts, dirs
+
+
 _startup = []
 
 
@@ -778,7 +870,14 @@ def analyze(args,
     Launched under torch.distributed.run (WORLD_SIZE > 1) every cluster is
     split over the ranks, one GPU each, and rank 0 writes the files: the bytes
     are the same for any number of GPUs.  `searcher` (tests) replaces the
-    AnnIndexSearch instance; it needs search_rows() and the script columns."""
+    AnnIndexSearch instance; it needs search_rows() and the script columns.
+
+    Several scripts (args.scripts): every batch is read and uploaded once and searched with
+    each script (ScriptSet); each script's files go to a directory of its own
+    (script_out_dirs), and the dated names come back as a list in argument order."""
+    scripts, dirs = check_scripts(args)     # (before the library loads or a work is listed)
+    if len(scripts) > 1 and searcher is not None:
+        raise ValueError("a replacement searcher serves one script")
     from . import dist
     # the tokeniser processes are forked before anything touches the GPU (the process group
     # of a multi-GPU run does); they read and tokenise cluster i + 1 while the GPU searches
@@ -817,15 +916,124 @@ def analyze(args,
             pool.native = textenc.TextEncoder(get_vocab(), default_text_threads(dist.env_world()[2]))
             _startup_lap("native text encoder")
     try:
+        if len(scripts) > 1:
+            return _analyze_multi(args, scripts, dirs, window_size, number_of_hashes, hash_dimensions,
+                                  distance_threshold, chunk_size, pool)
         return _analyze(args, window_size, number_of_hashes, hash_dimensions, distance_threshold,
-                        chunk_size, searcher, pool)
+                        chunk_size, searcher, pool, out_dir=dirs[0])
     finally:
         if pool is not None:
             pool.close()
 
 
+def _analyze_multi(args, scripts, dirs, window_size, number_of_hashes, hash_dimensions,
+                   distance_threshold, chunk_size, pool):
+    """analyze() with several scripts, one process: the listing, the -n/-s window, reading,
+    tokenising and the upload of each cluster are shared (ScriptSet); every script has its own
+    batch writer, batch files and dated file in its own directory."""
+    fan_works = list_fan_works(args.fan_works, args.skip_works, args.num_works)
+    window_size = getattr(args, 'window_size', None) or window_size
+    device = getattr(args, 'device', 0) or 0
+    fan_clusters = [fan_works[i:i + chunk_size]
+                    for i in range(0, len(fan_works), chunk_size)]
+    if pool is not None and fan_clusters:
+        pool.start(fan_clusters[0])                 # beside the index builds
+    # every index before the first batch is encoded: building one adds its script's words to
+    # the vocabulary, and the batches are encoded against the vocabulary as it then is
+    searchers = [AnnIndexSearch(sc, window_size, number_of_hashes, hash_dimensions, distance_threshold,
+                                device=device) for sc in scripts]
+    sset = ScriptSet(searchers)
+    if pool is not None:
+        searchers[0].token_pool = pool
+    import time
+    timing = {} if os.environ.get("FANDOM_SEARCH_TIMING") else None
+    t_last = [time.perf_counter()]
+
+    def lap(what):
+        if timing is not None:
+            now = time.perf_counter()
+            timing[what] = timing.get(what, 0.0) + now - t_last[0]
+            t_last[0] = now
+
+    for d in dirs:
+        os.makedirs(d, exist_ok=True)
+    bases = [os.path.join(d, 'match-{}gram{{}}'.format(window_size)) for d in dirs]
+    batch_names = [b.format('-batch-{}.csv') for b in bases]
+    from . import csvw
+    writers = None
+    if csvw.enabled():
+        writers = [csvw.CsvWriter(a.word_lowercase, a.orth_id, a.character, a.scene, a.vocab.strings)
+                   for a in searchers]
+        for a in searchers:
+            a.want_words = False
+    lap("index")
+    _startup_lap("script indexes on the GPU (library load, HIP start-up, fs_index_create)")
+    n_batches = 0
+    strings = searchers[0].vocab.strings
+    try:
+        for i, fan_cluster in enumerate(fan_clusters):
+            if pool is not None and i + 1 < len(fan_clusters):
+                pool.start(fan_clusters[i + 1])
+                if pool.native is not None and i + 2 < len(fan_clusters):
+                    pool.start(fan_clusters[i + 2])
+            print('Processing cluster {} ({}-{})'.format(i, chunk_size * i, chunk_size * (i + 1)))
+            results = sset.search_rows(fan_cluster)
+            lap("tokens + search")
+            oov = searchers[0].last_oov_rate
+            if oov is not None and oov > 0.2:
+                import sys
+                print('warning: {:.0%} of the fan tokens of this batch have no row in the vector '
+                      'table (out-of-vocabulary 3-hot vectors, search.py:79-83); check '
+                      'FANDOM_SEARCH_VECTORS'.format(oov), file=sys.stderr)
+            n_batches = i + 1
+            for k, (rows, sids, _st) in enumerate(results):
+                name = batch_names[k].format(i)
+                if writers is not None:
+                    writers[k].write_async(name, fan_cluster, rows, sids)
+                    continue
+                words = list(map(strings.__getitem__, sids.tolist()))
+                if pool is not None and pool.pool is not None:
+                    pool.write_async(_write_batch, (scripts[k], name, list(fan_cluster),
+                                                    np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).tobytes(),
+                                                    words))
+                    continue
+                a = searchers[k]
+                write_records(join_records(fan_cluster, rows, words, a.word_lowercase, a.orth_id,
+                                           a.character, a.scene), name)
+            lap("hand batches to the writers")
+        if writers is not None:
+            for w in writers:
+                w.finish()                          # (raises what a write raised)
+        if pool is not None:
+            pool.finish_writes()
+        lap("wait for the writers")
+    finally:
+        sset.close()
+        for w in writers or ():
+            w.close()
+        for a in searchers:
+            a.want_words = True
+            a.token_pool = None
+    names = []
+    for k in range(len(scripts)):
+        name = unused_result_name(bases[k])
+        write_records([new_record_structure['fields']], name)
+        with open(name, 'ab') as out:
+            for i in range(n_batches):
+                with open(batch_names[k].format(i), 'rb') as part:
+                    shutil.copyfileobj(part, out)
+        names.append(name)
+    lap("write dated csvs")
+    if timing is not None:
+        import sys
+        if _startup:
+            print("since process start: " + ", ".join("%s %.3f s" % kv for kv in _startup), file=sys.stderr)
+        print("analyze: " + ", ".join("%s %.3f s" % kv for kv in timing.items()), file=sys.stderr)
+    return names
+
+
 def _analyze(args, window_size, number_of_hashes, hash_dimensions, distance_threshold,
-             chunk_size, searcher, pool):
+             chunk_size, searcher, pool, out_dir=''):
     from . import dist
     rank, local_rank, world = dist.init_from_env()
     fan_works = list_fan_works(args.fan_works, args.skip_works, args.num_works)
@@ -845,6 +1053,9 @@ def _analyze(args, window_size, number_of_hashes, hash_dimensions, distance_thre
                     for i in range(0, len(fan_works), chunk_size)]
 
     filename_base = 'match-{}gram{{}}'.format(window_size)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        filename_base = os.path.join(out_dir, filename_base)
     batch_filename = filename_base.format('-batch-{}.csv')
 
     n_batches = 0

@@ -162,6 +162,20 @@ int fs_corpus_create(fs_index* ix,
  * the corpora that are still alive (a detached corpus can only be destroyed). */
 void fs_corpus_destroy(fs_corpus* c);
 
+/* A corpus of `ix` that searches the works of `base` (a corpus of another index on the same
+ * device, with the same window size, emb_dim and vector count) without copying them: the token,
+ * string-id, work-offset and block tables are base's, every per-index table is the view's own.
+ * One batch searched with several scripts is uploaded once (`ao3.py search` with several
+ * scripts).  A view reads the base's buffers and sizes at every search, so it follows
+ * fs_corpus_update_begin/_end on the base, and rebuilds its own tables at its first search after
+ * one, on its own index's stream, behind the base's upload (a device-side wait on the base's
+ * copy).  The base cannot be updated while a search of one of its views is in flight.
+ * fs_corpus_update_begin/_end on a view are refused.  A view may be destroyed at any time;
+ * destroying the base detaches its views (a detached view can only be destroyed).
+ * FS_E_INVALID for a base of `ix` itself, a view as base, another device, or a different
+ * window size, emb_dim or vector count (fs_last_error says which). */
+int fs_corpus_view(fs_index* ix, fs_corpus* base, fs_corpus** out);
+
 /* Streaming (BASELINE configs[4]: corpora larger than one batch, streamed from
  * pinned host memory).  fs_corpus_update_begin replaces the works of `c` with a
  * new batch: the copies, the block->work table and a device-side validation of
