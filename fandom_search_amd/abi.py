@@ -82,6 +82,12 @@ ROW_DTYPE = np.dtype([("work", np.uint32), ("fan_ix", np.uint32),
 assert ROW_DTYPE.itemsize == 32
 
 
+# fs_passage: 48 bytes
+PASSAGE_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32), ("n_exact", np.uint32),
+                          ("dist_sum", np.float64), ("dist_max", np.float64),
+                          ("comb_sum", np.float64), ("comb_max", np.float64)])
+assert PASSAGE_DTYPE.itemsize == 48
+
 def default_unique_filter():
     """Whether a query's bucket contents go through NearPy's UniqueFilter before the
     distances are taken.  OFF by default: the reference calls `engine.neighbours(row)`

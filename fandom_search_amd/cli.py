@@ -1,6 +1,8 @@
 """Command line of the search path: the `search`, `format`, `matrix` and
 `validate` sub-commands of the reference's ao3.py (/root/reference/ao3.py:509-526
-and _deprecated.py:83-89), same positionals, flags and output files.  The
+and _deprecated.py:83-89), same positionals, flags and output files, and
+`passages`, which joins a match CSV's per-word records into passages of reuse
+(fandom_search_amd/passages.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -21,7 +23,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -88,6 +90,21 @@ def build_parser():
     matrix_parser.add_argument('-n', action='store', default=6, type=int,
                                help='n-gram size, default is 6-grams')
     matrix_parser.set_defaults(func=_matrix)
+
+    passages_parser = subparsers.add_parser(
+        'passages', help='joins the per-word records of a match csv into passages of reuse')
+    passages_parser.add_argument('matches', action='store',
+                                 help='filename for search output (dated or batch file)')
+    passages_parser.add_argument('-o', '--output', action='store', default=None,
+                                 help='filename for the passages csv (default: the input name '
+                                      'with .csv replaced by -passages.csv)')
+    passages_parser.add_argument('--min-words', default=6, type=int,
+                                 help='fewest matched words a passage has, default 6')
+    passages_parser.add_argument('--max-gap', default=0, type=int,
+                                 help='words without a record a passage may step over on each '
+                                      'side at once, default 0')
+    passages_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    passages_parser.set_defaults(func=_passages)
     return parser
 
 
@@ -122,6 +139,13 @@ def _format(args):
 def _matrix(args):
     from . import matrix
     return matrix.process(args)
+
+
+def _passages(args):
+    from . import passages
+    if args.min_words < 1 or args.max_gap < 0:
+        sys.exit('ao3.py passages: error: --min-words must be at least 1, --max-gap at least 0')
+    return passages.process(args)
 
 
 def main(argv=None):

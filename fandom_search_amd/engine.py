@@ -411,6 +411,32 @@ class ScriptIndex(object):
         return out.cpu().numpy().view(np.uint32)[:n_script * (len(thr) + 1)] \
             .reshape(n_script, len(thr) + 1)
 
+    def passages_device(self, rows_ptr, n_rows, min_words=6, max_gap=0, out_ptr=None, cap=0):
+        """`passages` over device-resident fs_row records sorted by (work, fan_ix) (after a
+        search or a gather; fs_passages_rows).  Without `out_ptr`: the passages as a host
+        abi.PASSAGE_DTYPE array.  With `out_ptr` (a device buffer of `cap` passages): their
+        number; FsError(FS_E_CAPACITY) with .required when the buffer is too small.  A buffer
+        torch has only just produced goes in after torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+        if out_ptr is not None:
+            rc = L.fs_passages_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(min_words),
+                                    int(max_gap), C.c_void_p(out_ptr), int(cap), C.byref(n))
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_passages_rows", "passage buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_passages_rows")
+            return int(n.value)
+        import torch
+        cap = int(n_rows) // max(1, int(min_words)) + 1      # passages never outnumber this
+        out = torch.empty(cap * abi.PASSAGE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch_ready()
+        _lib.check(L.fs_passages_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(min_words),
+                                      int(max_gap), C.c_void_p(out.data_ptr()), cap, C.byref(n)),
+                   "fs_passages_rows")
+        return out[:n.value * abi.PASSAGE_DTYPE.itemsize].cpu().numpy().view(abi.PASSAGE_DTYPE)
+
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""
         ms = C.c_double(0)

@@ -266,6 +266,34 @@ int fs_reuse_histogram(int device, const uint32_t* orig_ix, const double* comb, 
 int fs_reuse_histogram_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows,
                             const double* thresholds, uint32_t n_thr, uint32_t* d_counts);
 
+/* `ao3.py passages`: match records joined into passages of reuse.  Records are sorted by
+ * (work, fan_ix) (what fs_search_corpus returns); record s continues the run of the record r
+ * just before it when s.work == r.work, 1 <= s.fan_ix - r.fan_ix <= 1 + max_gap and
+ * 1 <= s.orig_ix - r.orig_ix <= 1 + max_gap (signed differences; a repeated fan_ix ends a run).
+ * Runs of at least min_words records are passages, in record order.  Sums start at +0.0 and
+ * add the records in order; maxima are over non-NaN values, the earlier record kept on a tie
+ * (NaN only when every value is NaN); n_exact counts comb <= 0 (NaN never). */
+typedef struct fs_passage {
+  uint64_t first;      /* index of the passage's first record                  */
+  uint32_t n_words;    /* records in the passage                               */
+  uint32_t n_exact;    /* records with comb <= 0                               */
+  double   dist_sum, dist_max;
+  double   comb_sum, comb_max;
+} fs_passage;          /* 48 bytes                                             */
+
+/* Host columns in, `cap` host passages out, on HIP device `device`.  Both entry points:
+ * FS_E_INVALID for min_words == 0 or records out of (work, fan_ix) order, FS_E_UNSUPPORTED
+ * for n_rows >= 2^32, FS_E_CAPACITY with *n_out = passages required when cap is smaller,
+ * FS_OK with *n_out = 0 and no device work for n_rows == 0. */
+int fs_passages(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+                const double* dist, const double* comb, uint64_t n_rows, uint32_t min_words,
+                uint32_t max_gap, fs_passage* out, uint64_t cap, uint64_t* n_out);
+/* The same over device-resident fs_row records (16-byte aligned, e.g. straight after a
+ * search) into a device buffer of `cap` passages, on the index's device and stream;
+ * returns when they are written. */
+int fs_passages_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t min_words,
+                     uint32_t max_gap, fs_passage* d_out, uint64_t cap, uint64_t* n_out);
+
 /* Timing events ride on every `period`-th scan launch only (default 1 = every
  * launch); searches in between report scan_ms = 0.  The events cost a few
  * microseconds of stream time per launch, which matters for sub-100 us searches. */
