@@ -337,6 +337,12 @@ static int prove_exact(fs_index* ix, const uint32_t* stok) {
   inf.cos_bound = (n1 * qmax + c * qmin) / (n1 * qmax + qmin);
   inf.proof_ok = inf.cos_bound < 1.0 - ix->cfg.distance_threshold - 1e-6 ? 1u : 0u;
   if (V > FS_MAX_EXACT_ID) inf.proof_ok = 0;   // the scan's 24-bit premix needs ids < 2^24
+  // an id-identical window's record has dist = selfdist of its script window, rounding noise
+  // around 0 that the exact kernels never compare with the threshold: the
+  // reference keeps it only when dist < threshold (search.py:184), so every window must pass
+  // (h_selfdist: copied on this stream before k_cmax, complete after the synchronize above)
+  for (uint64_t w = 0; w < ix->n_windows && inf.proof_ok; ++w)
+    if (!(ix->h_selfdist[w] < ix->cfg.distance_threshold)) { inf.proof_ok = 0; ix->selfdist_fail = (int64_t)w; }
   return FS_OK;
 }
 
@@ -518,8 +524,13 @@ extern "C" int fs_index_create(const fs_config* cfg, const uint32_t* script_vec,
   ix->info.n_windows = ix->n_windows;
   const bool exact = ix->info.proof_ok && cfg->mode != FS_MODE_GENERAL;
   if (cfg->mode == FS_MODE_EXACT && !ix->info.proof_ok) {
-    fs_set_error("exact mode requested but cos bound %.6f >= 1 - threshold (c_max %.6f)",
-                 ix->info.cos_bound, ix->info.c_max);
+    if (ix->selfdist_fail >= 0)
+      fs_set_error("exact mode requested but script window %lld's distance to itself %.3g is not below "
+                   "the threshold %.3g (the exact path keeps every verbatim window)",
+                   (long long)ix->selfdist_fail, ix->h_selfdist[ix->selfdist_fail], cfg->distance_threshold);
+    else
+      fs_set_error("exact mode requested but cos bound %.6f >= 1 - threshold (c_max %.6f)",
+                   ix->info.cos_bound, ix->info.c_max);
     return FS_E_UNPROVEN;
   }
   ix->info.path = exact ? FS_MODE_EXACT : FS_MODE_GENERAL;

@@ -235,6 +235,7 @@ struct fs_index {
   bool strfast_ok = false;
   DBuf<double> d_q, d_selfdist;
   std::vector<double> h_selfdist;   // host copy (host-row searches expand 8-byte records on the host)
+  int64_t selfdist_fail = -1;       // prove_exact: a script window whose selfdist is not below the threshold (-1: none)
   void* h_stage = nullptr;          // pinned landing buffer of those records
   size_t h_stage_bytes = 0;
   void* d_stage = nullptr;          // the same buffer as the device sees it (records stored there by the search itself)

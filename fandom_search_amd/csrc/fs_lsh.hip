@@ -2156,8 +2156,9 @@ __global__ __launch_bounds__(256, 5) void k_lsh_verify(CorpusDev c, LshDev L, Gr
 constexpr int kBatchW = 8;                // windows per wave and step
 constexpr int kBatchCap = 32;             // members within the threshold kept per window
 constexpr int kBatchH = 16;               // tables (number_of_hashes) this form serves
+constexpr int kBatchBal = (kBatchH * 24 + 63) / 64 + 1;   // words per window: C <= 16 * 24 columns + a zero word
 struct alignas(16) BatchLds {             // per wave
-  uint64_t bal[kBatchW][6];               // sign bits of the projection columns (C <= 256), + a zero word
+  uint64_t bal[kBatchW][kBatchBal];       // sign bits of the projection columns, + a zero word
   double qf[kBatchW][FS_MAX_WINDOW];      // q of the windows' slots
   double ff[kBatchW], rff[kBatchW];
   double vd[kBatchW][kBatchCap];          // members within the threshold, arrival order: distance ...
@@ -2522,7 +2523,7 @@ __global__ __launch_bounds__(256, 5) void k_lsh_batch(CorpusDev c, LshDev L, Gra
 constexpr int kEnumNN = 10;               // NearestFilter sizes k_lsh_enum serves
 constexpr int kEnumG = 4;                 // script n-grams one slot away from a window that it takes
 struct alignas(16) PkeysLds {             // per wave
-  uint64_t bal[kBatchW][6];
+  uint64_t bal[kBatchW][kBatchBal];
   uint32_t f[kBatchW][FS_MAX_WINDOW];
   uint32_t pos[kBatchW], ok[kBatchW], work[kBatchW];
   float bnd[kBatchW];

@@ -100,7 +100,7 @@ def _windows(vectors, window_size):
 
 
 def build_lsh_engine(orig, window_size, number_of_hashes, hash_dimensions,
-                     normals, oov_hash, arith, unique_filter=False):
+                     normals, oov_hash, arith, unique_filter=False, nearest=10):
     """search.py:86-124.  `orig` is the list of lower-cased script tokens
     (the reference's Doc(vocab, word_lowercase), search.py:151);
     normals[h] is the (hash_dimensions, D*n) matrix of hash h."""
@@ -113,7 +113,8 @@ def build_lsh_engine(orig, window_size, number_of_hashes, hash_dimensions,
                                            normals[i], arith)
         hashes.append(h)
 
-    engine = nearpy.Engine(hashes, arith, unique_filter=unique_filter)
+    engine = nearpy.Engine(hashes, arith, unique_filter=unique_filter,
+                           nearest=nearest)
 
     for ix, row in enumerate(orig_win_vectors):
         # str(Doc[ix:ix+n]) == tokens joined by single spaces
@@ -128,11 +129,14 @@ class AnnIndexSearch(object):
     script_rows: list of [LOWERCASE, SPACY_ORTH_ID, SCENE, CHARACTER]
                  (load_markup_script output without its header, search.py:302)
     script_toks: lower-cased script tokens (vectors for the index)
+    nearest:     N of the engine's NearestFilter(N); the reference keeps
+                 NearPy's default of 10 (search.py:118-123)
     """
 
     def __init__(self, script_rows, script_toks, window_size,
                  number_of_hashes, hash_dimensions, distance_threshold,
-                 normals, oov_hash=None, arith=None, unique_filter=False):
+                 normals, oov_hash=None, arith=None, unique_filter=False,
+                 nearest=10):
         orig_csv = [[i] + list(r) for i, r in enumerate(script_rows)]
         (self.word_index,
          self.word_lowercase,
@@ -147,7 +151,7 @@ class AnnIndexSearch(object):
         self.engine = build_lsh_engine(script_toks, window_size,
                                        number_of_hashes, hash_dimensions,
                                        normals, self.oov_hash, self.arith,
-                                       unique_filter)
+                                       unique_filter, nearest)
         self.reset_stats()
 
     def reset_stats(self):
