@@ -88,6 +88,21 @@ PASSAGE_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32), ("n_exac
                           ("comb_sum", np.float64), ("comb_max", np.float64)])
 assert PASSAGE_DTYPE.itemsize == 48
 
+# fs_work: 56 bytes; fs_work_cell: 16 bytes
+WORK_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32), ("fan_first", np.uint32),
+                       ("fan_last", np.uint32), ("n_script_words", np.uint32),
+                       ("n_passages", np.uint32), ("passage_words", np.uint32),
+                       ("longest", np.uint32), ("n_groups_hit", np.uint32),
+                       ("top_group", np.uint32), ("top_group_words", np.uint32),
+                       ("reserved", np.uint32), ("reserved2", np.uint32)])
+assert WORK_DTYPE.itemsize == 56
+WORK_CELL_DTYPE = np.dtype([("work", np.uint32), ("group", np.uint32), ("n_words", np.uint32),
+                            ("n_exact", np.uint32)])
+assert WORK_CELL_DTYPE.itemsize == 16
+FS_NONE = 0xFFFFFFFF
+FS_WORKS_MAX_SCRIPT = 1 << 19
+FS_WORKS_MAX_GROUPS = 4096
+
 def default_unique_filter():
     """Whether a query's bucket contents go through NearPy's UniqueFilter before the
     distances are taken.  OFF by default: the reference calls `engine.neighbours(row)`

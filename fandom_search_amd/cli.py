@@ -2,7 +2,8 @@
 `validate` sub-commands of the reference's ao3.py (/root/reference/ao3.py:509-526
 and _deprecated.py:83-89), same positionals, flags and output files, and
 `passages`, which joins a match CSV's per-word records into passages of reuse
-(fandom_search_amd/passages.py).  The
+(fandom_search_amd/passages.py), and `works`, which summarises them by fan work
+(fandom_search_amd/works.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -23,7 +24,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -105,6 +106,23 @@ def build_parser():
                                       'side at once, default 0')
     passages_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
     passages_parser.set_defaults(func=_passages)
+
+    works_parser = subparsers.add_parser(
+        'works', help='summarises the records of a match csv by fan work: how much each work '
+                      'reuses, and from which scenes and characters')
+    works_parser.add_argument('matches', action='store',
+                              help='filename for search output (dated or batch file)')
+    works_parser.add_argument('-o', '--output', action='store', default=None,
+                              help='prefix of the three csv files, PREFIX-works.csv, '
+                                   'PREFIX-works-scenes.csv and PREFIX-works-characters.csv '
+                                   '(default: the input name without .csv)')
+    works_parser.add_argument('--min-words', default=6, type=int,
+                              help='fewest matched words a passage has, default 6')
+    works_parser.add_argument('--max-gap', default=0, type=int,
+                              help='words without a record a passage may step over on each '
+                                   'side at once, default 0')
+    works_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    works_parser.set_defaults(func=_works)
     return parser
 
 
@@ -146,6 +164,16 @@ def _passages(args):
     if args.min_words < 1 or args.max_gap < 0:
         sys.exit('ao3.py passages: error: --min-words must be at least 1, --max-gap at least 0')
     return passages.process(args)
+
+
+def _works(args):
+    from . import works
+    if args.min_words < 1 or args.max_gap < 0:
+        sys.exit('ao3.py works: error: --min-words must be at least 1, --max-gap at least 0')
+    try:
+        return works.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py works: error: %s' % e)
 
 
 def main(argv=None):

@@ -493,6 +493,15 @@ int fs_launch_histogram(const uint32_t* d_orig, const double* d_comb, const fs_r
 int fs_launch_blk_work(const uint64_t* work_off, uint32_t n_works, uint32_t n_blocks,
                        uint2* blk_work, uint4* blk4, hipStream_t s);
 
+// fs_passages.hip: run heads of records sorted by (work, fan_ix) as fs_passages joins them
+// (d_heads[k] = first record of run k, d_heads[n_runs] = n; FS_E_INVALID when out of order);
+// the scratch behind d_heads lives until fs_runs_free.  Synchronises `s`.
+struct fs_runs;
+int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d_fan,
+                 const uint32_t* d_orig, uint32_t n, uint32_t min_words, uint32_t max_gap,
+                 hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs);
+void fs_runs_free(fs_runs* r);
+
 void fs_host_pool_free(struct fs_host_pool* p);
 int fs_launch_levtab(fs_index* ix, fs_corpus* c, hipStream_t s);
 int fs_launch_strrec(fs_index* ix, fs_corpus* c, hipStream_t s);

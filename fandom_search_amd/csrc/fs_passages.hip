@@ -370,6 +370,31 @@ int pass_check(uint64_t n_rows, uint32_t min_words, const void* out, uint64_t ca
 
 }  // namespace
 
+// The runs of records sorted by (work, fan_ix), exactly as the passages join them, for
+// fs_works.hip (declared in fs_internal.h): rows, or the three key columns when d_rows is null.
+struct fs_runs {
+  PassWork w;
+};
+
+int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d_fan,
+                 const uint32_t* d_orig, uint32_t n, uint32_t min_words, uint32_t max_gap,
+                 hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
+  fs_runs* r = new fs_runs;
+  const int rc = d_rows ? pass_count(RowsSrc{d_rows}, n, min_words, max_gap, r->w, s)
+                        : pass_count(ColsSrc{d_work, d_fan, d_orig, nullptr, nullptr}, n,
+                                     min_words, max_gap, r->w, s);
+  if (rc != FS_OK) {
+    delete r;
+    return rc;
+  }
+  *runs = r;
+  *d_heads = r->w.heads.p;
+  *n_runs = r->w.n_runs;
+  return FS_OK;
+}
+
+void fs_runs_free(fs_runs* r) { delete r; }
+
 extern "C" int fs_passages(int device, const uint32_t* work, const uint32_t* fan_ix,
                            const uint32_t* orig_ix, const double* dist, const double* comb,
                            uint64_t n_rows, uint32_t min_words, uint32_t max_gap, fs_passage* out,

@@ -437,6 +437,53 @@ class ScriptIndex(object):
                    "fs_passages_rows")
         return out[:n.value * abi.PASSAGE_DTYPE.itemsize].cpu().numpy().view(abi.PASSAGE_DTYPE)
 
+    def works_device(self, rows_ptr, n_rows, n_works, group_of=None, n_groups=0, min_words=6,
+                     max_gap=0, thresholds=None, out_ptrs=None, cap=0):
+        """`works` over device-resident fs_row records sorted by (work, fan_ix) (after a search
+        or a gather; fs_works_rows): per-work summaries, threshold counts and the (work, group)
+        cells for the host map `group_of` (script word -> group id < n_groups; None: no
+        groups).  Without `out_ptrs`: (abi.WORK_DTYPE[n_works], counts[n_works][n_thr + 1],
+        abi.WORK_CELL_DTYPE[n_cells]) on the host.  With `out_ptrs` = device addresses
+        (summaries, counts, cells; the last a buffer of `cap` cells): the number of cells;
+        FsError(FS_E_CAPACITY) with .required when that buffer is too small.  Buffers torch
+        has only just produced go in after torch_ready()."""
+        from .format import THRESHOLDS
+        L = _lib.load()
+        thr = np.ascontiguousarray(THRESHOLDS if thresholds is None else thresholds,
+                                   dtype=np.float64)
+        gmap = None if group_of is None else abi.as_u32(group_of)
+        n = C.c_uint64(0)
+
+        def call(out, counts, cells, cap):
+            return L.fs_works_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                   abi.ptr(gmap, C.c_uint32), int(n_groups), int(min_words),
+                                   int(max_gap), abi.ptr(thr, C.c_double), len(thr),
+                                   C.c_void_p(out), C.c_void_p(counts), C.c_void_p(cells),
+                                   int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], out_ptrs[2], cap)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_works_rows", "cell buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_works_rows")
+            return int(n.value)
+        import torch
+        n_works, cols = int(n_works), len(thr) + 1
+        out = torch.empty(max(1, n_works) * abi.WORK_DTYPE.itemsize, dtype=torch.uint8,
+                          device="cuda")
+        counts = torch.empty(max(1, n_works * cols), dtype=torch.int32, device="cuda")
+        cap = min(int(n_rows), n_works * int(n_groups))      # a record makes at most one cell
+        cells = torch.empty(max(1, cap) * abi.WORK_CELL_DTYPE.itemsize, dtype=torch.uint8,
+                            device="cuda")
+        torch_ready()
+        _lib.check(call(out.data_ptr(), counts.data_ptr(), cells.data_ptr(), cap),
+                   "fs_works_rows")
+        return (out[:n_works * abi.WORK_DTYPE.itemsize].cpu().numpy().view(abi.WORK_DTYPE),
+                counts[:n_works * cols].cpu().numpy().view(np.uint32).reshape(n_works, cols),
+                cells[:n.value * abi.WORK_CELL_DTYPE.itemsize].cpu().numpy()
+                .view(abi.WORK_CELL_DTYPE))
+
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""
         ms = C.c_double(0)

@@ -294,6 +294,58 @@ int fs_passages(int device, const uint32_t* work, const uint32_t* fan_ix, const 
 int fs_passages_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t min_words,
                      uint32_t max_gap, fs_passage* d_out, uint64_t cap, uint64_t* n_out);
 
+/* `ao3.py works`: the same records reduced by work.  Records are sorted by (work, fan_ix) as
+ * for fs_passages; group_of[n_script] (host memory in both entry points, or NULL with
+ * n_groups = 0) maps a script word to a group id < n_groups, e.g. its scene or its character.
+ * Every output is an integer, so the result does not depend on the order in which the
+ * kernels combine records.  A work without records gets zeros and top_group = 0xFFFFFFFF. */
+typedef struct fs_work {
+  uint64_t first;            /* index of the work's first record                        */
+  uint32_t n_words;          /* its records                                             */
+  uint32_t fan_first;        /* fan_ix of its first ...                                 */
+  uint32_t fan_last;         /* ... and last record (the smallest and largest)          */
+  uint32_t n_script_words;   /* distinct orig_ix among its records                      */
+  uint32_t n_passages;       /* passages under (min_words, max_gap) as fs_passages      */
+  uint32_t passage_words;    /* records inside them                                     */
+  uint32_t longest;          /* records in the longest                                  */
+  uint32_t n_groups_hit;     /* distinct groups among its records (= its cells)         */
+  uint32_t top_group;        /* group with the most records, the smallest id on a tie   */
+  uint32_t top_group_words;  /* records of that group                                   */
+  uint32_t reserved, reserved2;   /* 0                                                  */
+} fs_work;                   /* 56 bytes                                                */
+
+/* one (work, group) pair that has a record; the list is sorted by (work, group) */
+typedef struct fs_work_cell {
+  uint32_t work, group;
+  uint32_t n_words;          /* records of the pair                                     */
+  uint32_t n_exact;          /* ... with comb <= 0 (NaN never)                          */
+} fs_work_cell;              /* 16 bytes                                                */
+
+#define FS_WORKS_MAX_SCRIPT (1u << 19)   /* n_script and n_groups up to these; beyond them     */
+#define FS_WORKS_MAX_GROUPS 4096u        /* both entry points return FS_E_UNSUPPORTED          */
+
+/* Host columns in; out[n_works], counts[n_works][n_thr + 1] (records with comb <= each of the
+ * n_thr ascending thresholds, NaN never, as fs_reuse_histogram; column n_thr = all records of
+ * the work) and `cap` cells out, on HIP device `device`.  Both entry points: FS_E_INVALID for
+ * min_words == 0, n_thr outside 1..64, thresholds that do not ascend, records out of
+ * (work, fan_ix) order, a work >= n_works, an orig_ix >= n_script or a group_of entry >=
+ * n_groups; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or n_groups >
+ * FS_WORKS_MAX_GROUPS; FS_E_CAPACITY with *n_cells = cells required when cap is smaller (out
+ * and counts are complete then).  n_rows == 0: empty summaries, zero counts, *n_cells = 0
+ * (fs_works: without device work). */
+int fs_works(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+             const double* comb, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+             const uint32_t* group_of, uint32_t n_groups, uint32_t min_words, uint32_t max_gap,
+             const double* thresholds, uint32_t n_thr, fs_work* out, uint32_t* counts,
+             fs_work_cell* cells, uint64_t cap, uint64_t* n_cells);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (d_out
+ * 8-byte, d_cells 16-byte aligned), n_script taken from the index, on the index's device and
+ * stream; returns when they are written. */
+int fs_works_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                  const uint32_t* group_of, uint32_t n_groups, uint32_t min_words,
+                  uint32_t max_gap, const double* thresholds, uint32_t n_thr, fs_work* d_out,
+                  uint32_t* d_counts, fs_work_cell* d_cells, uint64_t cap, uint64_t* n_cells);
+
 /* Timing events ride on every `period`-th scan launch only (default 1 = every
  * launch); searches in between report scan_ms = 0.  The events cost a few
  * microseconds of stream time per launch, which matters for sub-100 us searches. */
