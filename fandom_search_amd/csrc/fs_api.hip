@@ -127,6 +127,7 @@ void fs_read_switches(fs_switches* sw) {
   sw->lsh_batch = !getenv("FS_LSH_BATCH") || num("FS_LSH_BATCH") != 0;
   sw->lsh_emap = !getenv("FS_LSH_EMAP") || num("FS_LSH_EMAP") != 0;
   if (getenv("FS_LSH_DEFER_MIN")) sw->lsh_defer_min = num("FS_LSH_DEFER_MIN");
+  sw->lsh_full_grid = num("FS_LSH_FULL_GRID") != 0;
   sw->end_query = !getenv("FS_END_QUERY") || num("FS_END_QUERY") != 0;
   sw->lsh_no_gtab = getenv("FS_LSH_NO_GTAB") != nullptr;
   sw->lsh_serial = getenv("FS_LSH_SERIAL") != nullptr;

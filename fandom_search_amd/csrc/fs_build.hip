@@ -101,10 +101,10 @@ __global__ __launch_bounds__(256) void k_cmax(const float* __restrict__ emb,
 }
 
 // Pairs (script vector u, table vector v) that are *near*: cos(u, v) > 1 - coef / (|u| |v|), with
-// coef = n * thr * a_max^2 / 2 (fs_lsh.hip, component ids): same tiling as k_cmax, the pairs
+// coef = n * thr * a_max^2 / 2 (fs_lsh_build.hip, component ids): same tiling as k_cmax, the pairs
 // appended to a list (float32 cosines, 1e-4 of slack towards more pairs).  With gamma > -1.5 the
 // relation is angular instead: cos(u, v) > gamma, and a vector of norm 0 is near nothing (the
-// share rule of fs_lsh.hip, where a far slot's dot product is bounded by gamma |u| |v|: 0 for it).
+// share rule of fs_lsh_share.hip, where a far slot's dot product is bounded by gamma |u| |v|: 0 for it).
 __global__ __launch_bounds__(256) void k_near_pairs(const float* __restrict__ emb,
                                                     const float* __restrict__ embT, uint32_t n_vec,
                                                     int D, const double* __restrict__ q,
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_near_pairs(const float* __restrict__ em
   }
 }
 
-// max over the script's vectors u (rows_u; nullptr: the n_u rows of the table) of max_d |u[d]| / |u| (the share rule of fs_lsh.hip: the cosine of a
+// max over the script's vectors u (rows_u; nullptr: the n_u rows of the table) of max_d |u[d]| / |u| (the share rule of fs_lsh_build.hip, fs_build_share: the cosine of a
 // vector with at most three non-zero coordinates, all 1, to u is at most sqrt(3) times that)
 __global__ void k_coordmax(const float* __restrict__ emb, int D, const double* __restrict__ q,
                            const uint32_t* __restrict__ rows_u, uint32_t n_u, int* __restrict__ out_bits) {

@@ -1,4 +1,4 @@
-// fs_device.h -- device helpers shared by fs_post.hip and fs_lsh.hip.
+// fs_device.h -- device helpers shared by fs_post.hip and the fs_lsh*.hip units.
 #pragma once
 #include "fs_internal.h"
 #include <type_traits>

@@ -171,7 +171,7 @@ FS_HD uint32_t fs_wild_fbit(uint32_t h, int i) { return (h >> (8 * i)) & 31u; } 
 // fan window in all slots but one can be enumerated, not just shown to be possible.
 FS_HD uint32_t fs_wmap_slot(uint32_t h, int log2_slots) { return (h * 0x9E3779B1u) >> (32 - log2_slots); }
 
-// Subset keys of the share rule (fs_lsh.hip, "windows on tables that are not unit length"): a key
+// Subset keys of the share rule (fs_lsh_share.hip, "windows on tables that are not unit length"): a key
 // names the slots of a subset (`mask`) and the component ids the window holds there -- the fold of
 // the subset's terms, mixed with the mask.  A blocked Bloom filter (one 32-bit word, three bits:
 // fs_bloom_word / fs_bloom_test) holds the keys of every script window.
@@ -185,7 +185,7 @@ FS_HD uint32_t fs_share_key(uint32_t fold, uint32_t mask) { return fs_share_fini
 // ... and the few bits of a component id the pairs' test compares: n of them in a 64-bit word
 FS_HD int fs_share_sig_bits(int n) { return 64 / n > 10 ? 10 : 64 / n; }
 FS_HD uint32_t fs_share_sig(uint32_t comp, int n) { return (fs_mix24(comp) >> 7) & ((1u << fs_share_sig_bits(n)) - 1u); }
-// Windows of more than six slots take the share rule block by block (fs_lsh.hip): the slots in two or
+// Windows of more than six slots take the share rule block by block (fs_lsh_share.hip): the slots in two or
 // three runs of at most five, the subsets and their keys inside a run.  Run r of a window of n slots
 // starts at fs_share_block_start(n, r) (r = fs_share_blocks(n): the window's end).
 FS_HDC int fs_share_blocks(int n) { return n <= 6 ? 1 : n <= 10 ? 2 : 3; }

@@ -196,11 +196,12 @@ struct fs_switches {
   bool lsh_wmap = true;           // FS_LSH_WMAP=0: windows one slot away from a script n-gram always take the full LSH path
   bool lsh_keys6 = true;          // FS_LSH_KEYS6=0: n = 6 over component ids without the middle-slot key filter in k_scan_near
   bool lsh_syn = true;            // FS_LSH_SYN=0: no component-id prefilter for tables with near-synonyms
-  int lsh_share = 35;             // FS_LSH_SHARE: the share rule (fs_lsh.hip) on tables no integer prefilter applies to; bit 5 k_share_scan -- the script windows behind a window's keys instead of the key scan --, else bit 0 a gate kernel in front of k_lsh_scan (k_share_gate) and bit 1 the pairs' test inside it; bit 2 the gate asks for every heavy subset (the script's filter holds its heavy subsets only; n <= 6, without bit 5), bit 3 out-of-vocabulary fan tokens count as possibly near; 0: off.  Read when the index is built
+  int lsh_share = 35;             // FS_LSH_SHARE: the share rule (fs_lsh_share.hip) on tables no integer prefilter applies to; bit 5 k_share_scan -- the script windows behind a window's keys instead of the key scan --, else bit 0 a gate kernel in front of k_lsh_scan (k_share_gate) and bit 1 the pairs' test inside it; bit 2 the gate asks for every heavy subset (the script's filter holds its heavy subsets only; n <= 6, without bit 5), bit 3 out-of-vocabulary fan tokens count as possibly near; 0: off.  Read when the index is built
   double share_gamma = 0.7;       // FS_SHARE_GAMMA: cosine above which two vectors are near in the share rule
   bool lsh_emap = true;           // FS_LSH_EMAP=0: k_lsh_batch walks the buckets of every pending window instead of enumerating the script n-grams one slot away
   bool lsh_batch = true;          // FS_LSH_BATCH=0: the pending windows a wave each (k_lsh_verify) instead of eight per wave level by level (k_lsh_batch)
   int lsh_defer_min = 8192;       // FS_LSH_DEFER_MIN: pending windows of the lane's last search from which on the kept matches' Levenshtein distances go to k_lsh_lev (and the windows to k_lsh_batch)
+  bool lsh_full_grid = false;     // FS_LSH_FULL_GRID=1: the kernels behind the prefilter launched with kNB workgroups instead of one resident set (tools/collect_profiles.sh)
   bool near_fused = true;         // FS_NEAR_FUSED=0: k_scan_near8 + k_expand + k_lsh_sift (round 4's chain) instead of k_near_sift + k_lsh_sift2; read when the index is built (n = 6: which prefilter kernel the 3-gram filter is laid out for)
   bool lsh_gramtab = true;        // FS_LSH_GRAMTAB=0: no per-n-gram records (k_lsh_gramtab): every window with a script n-gram's ids walks the buckets
   int rows_waves = 0;             // FS_ROWS_WAVES: waves per workgroup of k_scan_rows (experiments)
@@ -265,7 +266,7 @@ struct fs_index {
   int log2_wmap = 0;
   // Tables with near-synonyms (the proof fails by more than one slot): the same two filters
   // over *component ids* -- connected components of "near" pairs of table vectors, at most one
-  // slot of a neighbour within the threshold joins two components (fs_lsh.hip)
+  // slot of a neighbour within the threshold joins two components (fs_lsh_build.hip)
   DBuf<uint32_t> d_comp;     // [V] component id of a table vector
   DBuf<uint32_t> d_compa;    // [V] component id of a table vector under the angular relation of the share rule
   DBuf<uint64_t> d_ssig;     // [W] the script windows' component signatures (fs_share_sig)

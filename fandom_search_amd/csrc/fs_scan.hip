@@ -577,7 +577,7 @@ __global__ __launch_bounds__(1024) void k_scan_near8(const uint32_t* __restrict_
 // byte} to its wave's queue in LDS (k_scan_rows' record), and whenever 64 candidates are queued
 // the wave takes one each: the n ids (the stream it has just read: L2), the grouped wildcard
 // filter's three 16-byte blocks, requested together, the n key tests.  The survivors go to the
-// wave range's own list in memory, in position order; k_lsh_sift2 (fs_lsh.hip) numbers them
+// wave range's own list in memory, in position order; k_lsh_sift2 (fs_lsh_sift.hip) numbers them
 // across the ranges and takes the deeper steps.  No bitmap, no k_expand, no global atomics, and
 // everything behind this kernel runs over an eighth of the entries.
 constexpr uint32_t kSiftQueue = 128;            // queued records per wave: < 64 left over + <= 64 of a sub-tile
@@ -1529,7 +1529,7 @@ int fs_launch_stream_floor(fs_index* ix, fs_corpus* c, uint32_t reps, double* av
 
 // ---- k_scan_near (integer prefilter of the LSH pipeline) --------------------------------
 // 0: none; 1: at most one slot of a neighbour may differ in its vector id (k_scan_near over
-// the vector ids); 2: tables with near-synonyms, the same over component ids (fs_lsh.hip)
+// the vector ids); 2: tables with near-synonyms, the same over component ids (fs_lsh_build.hip)
 int fs_lsh_prefilter_mode(const fs_index* ix, const fs_corpus* c) {
   const int n = (int)ix->cfg.window_size;
   if (!ix->sw.lsh_prefilter || c->has_oov || ix->script_oov) return 0;

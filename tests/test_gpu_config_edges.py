@@ -4,7 +4,7 @@ and thresholds at and below the rounding noise of a window's distance to itself.
 is bit-compared with the plain-C oracle, and names the kernel it is there for: a case that
 stops reaching its branch fails.
 
-Boundaries (fs_lsh.hip, fs_api.hip) and the cases on either side of them:
+Boundaries (fs_lsh*.hip, fs_api.hip) and the cases on either side of them:
   float32 keys iff C = H * B <= 256          c256 (16 x 16)      | c272 (16 x 17)
   k_lsh_batch / k_lsh_pkeys ballot words     c256, c272          | c336, enum_c336 (16 x 21: a
     (5 words up to C = 320, 6 up to 384)                            sixth word and the zero word)

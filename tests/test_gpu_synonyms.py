@@ -1,5 +1,5 @@
 """Tables with near-synonyms (the shape of every real embedding table): the LSH pipeline
-behind the component-id prefilters (fs_lsh.hip: connected components of "near" pairs of
+behind the component-id prefilters (fs_lsh_build.hip: connected components of "near" pairs of
 vectors, at most one slot of a neighbour within the threshold joins two components).
 Records must equal the oracle's -- which has no shortcut at all -- and the unfiltered LSH
 pipeline's byte for byte; a table whose components are too coarse must fall back."""

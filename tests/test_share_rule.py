@@ -1,4 +1,4 @@
-"""The share rule of the LSH pipeline (csrc/fs_lsh.hip) as arithmetic, on the
+"""The share rule of the LSH pipeline (csrc/fs_lsh_share.hip) as arithmetic, on the
 CPU: the inequality its two skips rest on, and the two properties of the gate's subsets --
 on random tables with norms spread by a factor of thirty.  (That the kernels apply it to the
 reference's records without changing them is tests/test_gpu_realistic_table.py and
