@@ -103,6 +103,18 @@ FS_NONE = 0xFFFFFFFF
 FS_WORKS_MAX_SCRIPT = 1 << 19
 FS_WORKS_MAX_GROUPS = 4096
 
+# fs_quote_word: 24 bytes; fs_quote_region: 40 bytes
+QUOTE_WORD_DTYPE = np.dtype([("n_words", np.uint32), ("n_exact", np.uint32),
+                             ("n_works", np.uint32), ("n_passages", np.uint32),
+                             ("n_passage_works", np.uint32), ("region", np.uint32)])
+assert QUOTE_WORD_DTYPE.itemsize == 24
+QUOTE_REGION_DTYPE = np.dtype([("first", np.uint32), ("last", np.uint32),
+                               ("n_passages", np.uint32), ("n_works", np.uint32),
+                               ("n_words", np.uint32), ("n_exact", np.uint32),
+                               ("peak", np.uint32), ("peak_first", np.uint32),
+                               ("peak_last", np.uint32), ("reserved", np.uint32)])
+assert QUOTE_REGION_DTYPE.itemsize == 40
+
 def default_unique_filter():
     """Whether a query's bucket contents go through NearPy's UniqueFilter before the
     distances are taken.  OFF by default: the reference calls `engine.neighbours(row)`

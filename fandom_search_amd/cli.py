@@ -3,7 +3,8 @@
 and _deprecated.py:83-89), same positionals, flags and output files, and
 `passages`, which joins a match CSV's per-word records into passages of reuse
 (fandom_search_amd/passages.py), and `works`, which summarises them by fan work
-(fandom_search_amd/works.py).  The
+(fandom_search_amd/works.py), and `quotes`, which ranks the stretches of the script by the works
+that reuse them (fandom_search_amd/quotes.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -24,7 +25,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -123,6 +124,26 @@ def build_parser():
                                    'side at once, default 0')
     works_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
     works_parser.set_defaults(func=_works)
+
+    quotes_parser = subparsers.add_parser(
+        'quotes', help='ranks the stretches of the script by the fan works that quote them: '
+                       'per script word and per quoted region, how many works and passages')
+    quotes_parser.add_argument('matches', action='store',
+                               help='filename for search output (dated or batch file)')
+    quotes_parser.add_argument('-o', '--output', action='store', default=None,
+                               help='prefix of the two csv files, PREFIX-quotes.csv and '
+                                    'PREFIX-quotes-words.csv (default: the input name without '
+                                    '.csv)')
+    quotes_parser.add_argument('--min-words', default=6, type=int,
+                               help='fewest matched words a passage has, default 6')
+    quotes_parser.add_argument('--max-gap', default=0, type=int,
+                               help='words without a record a passage may step over on each '
+                                    'side at once, default 0')
+    quotes_parser.add_argument('--min-works', default=1, type=int,
+                               help='fewest different works whose passages cover every word of '
+                                    'a region, default 1')
+    quotes_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    quotes_parser.set_defaults(func=_quotes)
     return parser
 
 
@@ -174,6 +195,17 @@ def _works(args):
         return works.process(args)
     except ValueError as e:
         sys.exit('ao3.py works: error: %s' % e)
+
+
+def _quotes(args):
+    from . import quotes
+    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0:
+        sys.exit('ao3.py quotes: error: --min-words and --min-works must be at least 1, '
+                 '--max-gap at least 0')
+    try:
+        return quotes.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py quotes: error: %s' % e)
 
 
 def main(argv=None):

@@ -484,6 +484,44 @@ class ScriptIndex(object):
                 cells[:n.value * abi.WORK_CELL_DTYPE.itemsize].cpu().numpy()
                 .view(abi.WORK_CELL_DTYPE))
 
+    def quotes_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_works=1,
+                      out_ptrs=None, cap=0):
+        """`quotes` over device-resident fs_row records sorted by (work, fan_ix) (after a search
+        or a gather; fs_quotes_rows): the script's words with the works and passages behind
+        them, and the regions of depth >= min_works.  Without `out_ptrs`:
+        (abi.QUOTE_WORD_DTYPE[n_script], abi.QUOTE_REGION_DTYPE[n_regions]) on the host.  With
+        `out_ptrs` = device addresses (words; regions, a buffer of `cap` of them): the number of
+        regions; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the words
+        are complete then).  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+
+        def call(words, regions, cap):
+            return L.fs_quotes_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    int(min_words), int(max_gap), int(min_works),
+                                    C.c_void_p(words), C.c_void_p(regions), int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_quotes_rows", "region buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_quotes_rows")
+            return int(n.value)
+        import torch
+        n_script = int(self.info["n_script"])
+        cap = min(int(n_rows), (n_script + 1) // 2)          # regions lie a word apart at least
+        words = torch.empty(max(1, n_script) * abi.QUOTE_WORD_DTYPE.itemsize, dtype=torch.uint8,
+                            device="cuda")
+        regions = torch.empty(max(1, cap) * abi.QUOTE_REGION_DTYPE.itemsize, dtype=torch.uint8,
+                              device="cuda")
+        torch_ready()
+        _lib.check(call(words.data_ptr(), regions.data_ptr(), cap), "fs_quotes_rows")
+        return (words[:n_script * abi.QUOTE_WORD_DTYPE.itemsize].cpu().numpy()
+                .view(abi.QUOTE_WORD_DTYPE),
+                regions[:n.value * abi.QUOTE_REGION_DTYPE.itemsize].cpu().numpy()
+                .view(abi.QUOTE_REGION_DTYPE))
+
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""
         ms = C.c_double(0)

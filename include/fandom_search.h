@@ -346,6 +346,52 @@ int fs_works_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t 
                   uint32_t max_gap, const double* thresholds, uint32_t n_thr, fs_work* d_out,
                   uint32_t* d_counts, fs_work_cell* d_cells, uint64_t cap, uint64_t* n_cells);
 
+/* `ao3.py quotes`: the same records seen from the script's side.  Records are sorted by
+ * (work, fan_ix) as for fs_passages, and a passage is what fs_passages keeps under
+ * (min_words, max_gap).  Its span is [orig_ix of its first record, orig_ix of its last]; it
+ * covers every script word in the span, the words it bridges under max_gap too.  Every output
+ * is an integer, so the result does not depend on the order in which the kernels combine
+ * records or passages. */
+typedef struct fs_quote_word {
+  uint32_t n_words;          /* records with orig_ix == this word, in a passage or not  */
+  uint32_t n_exact;          /* ... with comb <= 0 (NaN never)                          */
+  uint32_t n_works;          /* distinct works with a record at the word                */
+  uint32_t n_passages;       /* passages covering the word                              */
+  uint32_t n_passage_works;  /* distinct works with a passage covering it: its depth    */
+  uint32_t region;           /* index of the region holding the word, or 0xFFFFFFFF     */
+} fs_quote_word;             /* 24 bytes                                                */
+
+/* A region: a maximal run of consecutive script words of depth >= min_works; regions are
+ * numbered in script order.  Its first and last word always carry a record. */
+typedef struct fs_quote_region {
+  uint32_t first, last;      /* script word indices, inclusive                          */
+  uint32_t n_passages;       /* passages whose span intersects [first, last]            */
+  uint32_t n_works;          /* distinct works with such a passage                      */
+  uint32_t n_words, n_exact; /* sums of the words' n_words and n_exact                  */
+  uint32_t peak;             /* largest depth in the region                             */
+  uint32_t peak_first;       /* smallest word index at the peak                         */
+  uint32_t peak_last;        /* end of the run of words at the peak that starts there   */
+  uint32_t reserved;         /* 0                                                       */
+} fs_quote_region;           /* 40 bytes                                                */
+
+/* Host columns in; words[n_script] and `cap` regions out, on HIP device `device`.  Both entry
+ * points: FS_E_INVALID for min_words == 0, min_works == 0, records out of (work, fan_ix)
+ * order, a work >= n_works or an orig_ix >= n_script; FS_E_UNSUPPORTED for n_rows >= 2^32 or
+ * n_script > FS_WORKS_MAX_SCRIPT; FS_E_CAPACITY with *n_regions = regions required when cap is
+ * smaller (words is complete then).  n_rows == 0: zeroed words with region = 0xFFFFFFFF,
+ * *n_regions = 0 (fs_quotes: without device work). */
+int fs_quotes(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              const double* comb, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+              uint32_t min_words, uint32_t max_gap, uint32_t min_works, fs_quote_word* words,
+              fs_quote_region* regions, uint64_t cap, uint64_t* n_regions);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (4-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_quotes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   uint32_t min_words, uint32_t max_gap, uint32_t min_works,
+                   fs_quote_word* d_words, fs_quote_region* d_regions, uint64_t cap,
+                   uint64_t* n_regions);
+
 /* Timing events ride on every `period`-th scan launch only (default 1 = every
  * launch); searches in between report scan_ms = 0.  The events cost a few
  * microseconds of stream time per launch, which matters for sub-100 us searches. */
