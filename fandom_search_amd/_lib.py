@@ -28,7 +28,9 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_textenc_create", "fs_textenc_destroy", "fs_textenc_add", "fs_textenc_encode_files",
            "fs_textenc_encode_files_vec",
            "fs_csvw_create", "fs_csvw_destroy", "fs_csvw_set_script", "fs_csvw_add_strings", "fs_csvw_strings",
-           "fs_csvw_format")
+           "fs_csvw_format",
+           "fs_matches_open", "fs_matches_read", "fs_matches_labels", "fs_matches_close",
+           "fs_matches_parse_double")
 
 
 class FsError(RuntimeError):
@@ -173,6 +175,19 @@ def load():
     L.fs_quotes_rows.restype = C.c_int
     L.fs_quotes_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_matches_open.restype = C.c_int
+    L.fs_matches_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p),
+                                  C.POINTER(abi.FsMatchesInfo)]
+    L.fs_matches_read.restype = C.c_int
+    L.fs_matches_read.argtypes = [C.c_void_p, u32p, u32p, u32p, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), C.c_void_p, C.c_uint64, C.c_void_p,
+                                  C.c_uint64]
+    L.fs_matches_labels.restype = C.c_int
+    L.fs_matches_labels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p, u64p]
+    L.fs_matches_close.restype = None
+    L.fs_matches_close.argtypes = [C.c_void_p]
+    L.fs_matches_parse_double.restype = C.c_int
+    L.fs_matches_parse_double.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_double)]
     L.fs_search_corpus_begin.restype = C.c_int
     L.fs_search_corpus_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                          C.POINTER(C.c_uint32)]

@@ -115,6 +115,36 @@ QUOTE_REGION_DTYPE = np.dtype([("first", np.uint32), ("last", np.uint32),
                                ("peak_last", np.uint32), ("reserved", np.uint32)])
 assert QUOTE_REGION_DTYPE.itemsize == 40
 
+# the match CSV reader (fs_matches_*): fs_match_ix 64 bytes, fs_match_defer 8, fs_matches_info 96
+FS_MATCH_FIELDS = 12
+FS_MATCHES_PARSED = 0
+FS_MATCHES_DEFERRED = 1
+FS_MATCHES_OUTSIDE = 2
+FS_MATCH_BAD_NUL, FS_MATCH_BAD_OPEN, FS_MATCH_BAD_CLOSE, FS_MATCH_BAD_CR = 1, 2, 4, 8
+FS_MATCH_BAD_FIELDS, FS_MATCH_BAD_INT, FS_MATCH_BAD_UTF8, FS_MATCH_BAD_ROW = 16, 32, 64, 128
+FS_MATCH_BAD_DEFER = 256
+MATCH_IX_DTYPE = np.dtype([("start", np.uint64), ("end", np.uint32, (FS_MATCH_FIELDS,)),
+                           ("quoted", np.uint32), ("head", np.uint32)])
+assert MATCH_IX_DTYPE.itemsize == 64
+MATCH_DEFER_DTYPE = np.dtype([("row", np.uint32), ("col", np.uint32)])
+assert MATCH_DEFER_DTYPE.itemsize == 8
+FS_DEC_SURE = 0
+FS_DEC_NOT_MINE = 1
+
+
+class FsMatchesInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64),
+                ("n_deferred", C.c_uint64),
+                ("status", C.c_uint32),
+                ("reason", C.c_uint32),
+                ("has_header", C.c_uint32),
+                ("reserved", C.c_uint32),
+                ("ms", C.c_double * 8)]
+
+
+MATCHES_MS_NAMES = ("upload", "parity", "classify", "place", "header", "rows", "device_total")
+
+
 def default_unique_filter():
     """Whether a query's bucket contents go through NearPy's UniqueFilter before the
     distances are taken.  OFF by default: the reference calls `engine.neighbours(row)`

@@ -106,6 +106,9 @@ def build_parser():
                                  help='words without a record a passage may step over on each '
                                       'side at once, default 0')
     passages_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    passages_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                 help='who reads the match csv: the GPU (default) or csv.reader; also '
+                                      'FANDOM_SEARCH_READER')
     passages_parser.set_defaults(func=_passages)
 
     works_parser = subparsers.add_parser(
@@ -123,6 +126,9 @@ def build_parser():
                               help='words without a record a passage may step over on each '
                                    'side at once, default 0')
     works_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    works_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                              help='who reads the match csv: the GPU (default) or csv.reader; also '
+                                   'FANDOM_SEARCH_READER')
     works_parser.set_defaults(func=_works)
 
     quotes_parser = subparsers.add_parser(
@@ -143,6 +149,9 @@ def build_parser():
                                help='fewest different works whose passages cover every word of '
                                     'a region, default 1')
     quotes_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    quotes_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                               help='who reads the match csv: the GPU (default) or csv.reader; also '
+                                    'FANDOM_SEARCH_READER')
     quotes_parser.set_defaults(func=_quotes)
     return parser
 

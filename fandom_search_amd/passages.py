@@ -103,14 +103,53 @@ def passage_rows(rows, min_words=6, max_gap=0, device=0):
     return out
 
 
+def passage_rows_device(mf, min_words=6, max_gap=0, device=0):
+    """passage_rows over a matches.MatchFile: the same rows, decoding only the fields of the
+    records inside passages."""
+    order, work, fan, orig, dist, comb = mf.sorted()
+    found = find_passages(work, fan, orig, dist, comb, min_words, max_gap, device)
+    first = found['first'].astype(np.int64)
+    count = found['n_words'].astype(np.int64)
+    ends = np.cumsum(count)
+    # the records of every kept passage, passage after passage
+    pos = np.repeat(first - (ends - count), count) + np.arange(ends[-1] if len(ends) else 0)
+    recs = order[pos]
+    fan_words, orig_words = mf.text(_FAN_WORD, recs), mf.text(_ORIG_WORD, recs)
+    heads = order[first]
+    names, chars, scenes = (mf.text(c, heads) for c in (_FNAME, _CHAR, _SCENE))
+    out = []
+    for j, p in enumerate(found):
+        a, k = int(p['first']), int(p['n_words'])
+        lo, hi = int(ends[j]) - k, int(ends[j])
+        out.append([names[j], int(fan[a]), int(fan[a + k - 1]), int(orig[a]),
+                    int(orig[a + k - 1]), k, int(p['n_exact']), chars[j], scenes[j],
+                    float(p['dist_sum']) / k, float(p['dist_max']),
+                    float(p['comb_sum']) / k, float(p['comb_max']),
+                    ' '.join(fan_words[lo:hi]), ' '.join(orig_words[lo:hi])])
+    return out
+
+
+def body_rows(path, reader, min_words=6, max_gap=0, device=0):
+    """The passage CSV's rows of the match file `path` under `reader` ('device' or 'python');
+    a file the device reader does not take goes through read_matches like any file did."""
+    if reader == 'device':
+        from .matches import MatchFile
+        with MatchFile(path, device) as mf:
+            if not mf.outside:
+                return passage_rows_device(mf, min_words, max_gap, device)
+    return passage_rows(read_matches(path), min_words, max_gap, device)
+
+
 def output_name(matches):
     return (matches[:-4] if matches.endswith('.csv') else matches) + '-passages.csv'
 
 
 def process(args):
-    """`ao3.py passages matches [-o OUTPUT] [--min-words M] [--max-gap G] [--device D]`."""
+    """`ao3.py passages matches [-o OUTPUT] [--min-words M] [--max-gap G] [--device D]
+    [--reader {device,python}]`."""
+    from .matches import reader_of
     out = args.output or output_name(args.matches)
-    body = passage_rows(read_matches(args.matches), args.min_words, args.max_gap, args.device)
+    body = body_rows(args.matches, reader_of(args), args.min_words, args.max_gap, args.device)
     with open(out, 'w', newline='', encoding='utf-8') as fh:
         w = csv.writer(fh)
         w.writerow(PASSAGE_FIELDS)

@@ -81,6 +81,25 @@ def tables(rows, min_words=6, max_gap=0, min_works=1, device=0):
     _, work, fan, orig, _, comb = sort_records(rows)
     n_works = len(set(r[_FNAME] for r in rows))
     n_script = int(orig.max()) + 1 if len(orig) else 0
+    return _tables(labels, work, fan, orig, comb, n_works, n_script, min_words, max_gap,
+                   min_works, device)
+
+
+def tables_device(mf, min_words=6, max_gap=0, min_works=1, device=0):
+    """tables over a matches.MatchFile, the three labels decoded once per script word; None
+    when a script word's records spell one in two ways (tables() then decides)."""
+    _, work, fan, orig, _, comb = mf.sorted()
+    n_script = int(orig.max()) + 1 if len(orig) else 0
+    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
+    if any(c is None for c in cols):
+        return None
+    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
+    return _tables(labels, work, fan, orig, comb, len(mf.names), n_script, min_words, max_gap,
+                   min_works, device)
+
+
+def _tables(labels, work, fan, orig, comb, n_works, n_script, min_words, max_gap, min_works,
+            device):
     words, regions = find_quotes(work, fan, orig, comb, n_works, n_script, min_words, max_gap,
                                  min_works, device)
     unknown = (UNKNOWN_WORD, '', '')
@@ -110,10 +129,18 @@ def output_names(matches, prefix=None):
 
 def process(args):
     """`ao3.py quotes matches [-o PREFIX] [--min-words M] [--max-gap G] [--min-works K]
-    [--device D]`."""
+    [--device D] [--reader {device,python}]`."""
+    from .matches import MatchFile, reader_of
     outs = output_names(args.matches, args.output)
-    body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.min_works,
-                  args.device)
+    body = None
+    if reader_of(args) == 'device':
+        with MatchFile(args.matches, args.device) as mf:
+            if not mf.outside:
+                body = tables_device(mf, args.min_words, args.max_gap, args.min_works,
+                                     args.device)
+    if body is None:        # the python reader, or a file the device reader does not take
+        body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.min_works,
+                      args.device)
     for path, head, part in zip(outs, (REGION_FIELDS, WORD_FIELDS), body):
         with open(path, 'w', newline='', encoding='utf-8') as fh:
             w = csv.writer(fh)

@@ -92,6 +92,19 @@ def label_groups(orig, labels, what):
     return group_of, names
 
 
+def groups_of_labels(label_at, n_script):
+    """label_groups' result for {script word: label}."""
+    ids, names = {}, []
+    group_of = np.zeros(n_script, dtype=np.uint32)
+    for o in sorted(label_at):
+        lab = label_at[o]
+        if lab not in ids:
+            ids[lab] = len(names)
+            names.append(lab)
+        group_of[o] = ids[lab]
+    return group_of, names
+
+
 def tables(rows, min_words=6, max_gap=0, device=0):
     """(works, scenes, characters): the three CSVs' rows, without headers, for the records
     `rows` (read_matches)."""
@@ -99,9 +112,29 @@ def tables(rows, min_words=6, max_gap=0, device=0):
     names = list(dict.fromkeys(r[_FNAME] for r in rows))
     srt = [rows[i] for i in order]
     n_script = int(orig.max()) + 1 if len(orig) else 0
+    groups = [label_groups(orig, [r[col] for r in srt], what)
+              for col, what in ((_SCENE, 'scene'), (_CHAR, 'character'))]
+    return _tables(names, work, fan, orig, comb, n_script, groups, min_words, max_gap, device)
+
+
+def tables_device(mf, min_words=6, max_gap=0, device=0):
+    """tables over a matches.MatchFile, one label decoded per script word; None when a script
+    word's records spell a label in two ways (tables() then says what is wrong, or finds the
+    two spellings equal)."""
+    _, work, fan, orig, _, comb = mf.sorted()
+    n_script = int(orig.max()) + 1 if len(orig) else 0
+    groups = []
+    for col in (_SCENE, _CHAR):
+        label_at = mf.labels(col, n_script)
+        if label_at is None:
+            return None
+        groups.append(groups_of_labels(label_at, n_script))
+    return _tables(mf.names, work, fan, orig, comb, n_script, groups, min_words, max_gap, device)
+
+
+def _tables(names, work, fan, orig, comb, n_script, groups, min_words, max_gap, device):
     res = []
-    for col, what in ((_SCENE, 'scene'), (_CHAR, 'character')):
-        group_of, labels = label_groups(orig, [r[col] for r in srt], what)
+    for group_of, labels in groups:
         res.append((labels,) + summarise(work, fan, orig, comb, len(names), n_script, group_of,
                                          len(labels), min_words, max_gap, THRESHOLDS, device))
     (scenes, ws, counts, scells), (chars, wc, _, ccells) = res
@@ -130,9 +163,17 @@ def output_names(matches, prefix=None):
 
 
 def process(args):
-    """`ao3.py works matches [-o PREFIX] [--min-words M] [--max-gap G] [--device D]`."""
+    """`ao3.py works matches [-o PREFIX] [--min-words M] [--max-gap G] [--device D]
+    [--reader {device,python}]`."""
+    from .matches import MatchFile, reader_of
     outs = output_names(args.matches, args.output)
-    body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.device)
+    body = None
+    if reader_of(args) == 'device':
+        with MatchFile(args.matches, args.device) as mf:
+            if not mf.outside:
+                body = tables_device(mf, args.min_words, args.max_gap, args.device)
+    if body is None:        # the python reader, or a file the device reader does not take
+        body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.device)
     for path, head, part in zip(outs, (WORK_FIELDS, SCENE_FIELDS, CHARACTER_FIELDS), body):
         with open(path, 'w', newline='', encoding='utf-8') as fh:
             w = csv.writer(fh)

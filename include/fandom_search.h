@@ -392,6 +392,86 @@ int fs_quotes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t
                    fs_quote_word* d_words, fs_quote_region* d_regions, uint64_t cap,
                    uint64_t* n_regions);
 
+/* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
+ * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
+ * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
+ * columns fs_passages / fs_works / fs_quotes take, and a head flag per row.  The reader does not
+ * guess.  A '"' toggles quoting, ',' outside quotes ends a field, '\n' outside quotes ends a row
+ * (a '\r' directly in front belongs to the terminator, a last row needs none); this equals
+ * csv.reader when every opening quote starts a field, every closing quote is followed by ',',
+ * a terminator, the end of the file or the second quote of a "" pair, no '\r' stands outside
+ * quotes without its '\n', no NUL occurs and every non-empty row has twelve fields.  fan_ix,
+ * orig_ix and lev are unquoted runs of 1..10 digits below 2^32.  A file that breaks any of this,
+ * or is not UTF-8, is FS_MATCHES_OUTSIDE (info.reason: FS_MATCH_BAD_* bits) and nothing of it is
+ * returned.  dist and comb: the empty field (NaN), nan, inf, -inf or a decimal of repr's shape
+ * with up to 17 significant digits, converted to the bits float() gives; a field of another
+ * shape is listed as deferred {row, column}, holds NaN, and is the host's to convert
+ * (FS_MATCHES_DEFERRED; more than max(4096, n_rows / 16) of them: FS_MATCHES_OUTSIDE). */
+#define FS_MATCH_FIELDS 12
+enum { FS_MATCHES_PARSED = 0, FS_MATCHES_DEFERRED = 1, FS_MATCHES_OUTSIDE = 2 };
+enum {
+  FS_MATCH_BAD_NUL = 1,     /* a NUL byte                                               */
+  FS_MATCH_BAD_OPEN = 2,    /* an opening quote inside a field                          */
+  FS_MATCH_BAD_CLOSE = 4,   /* text behind a closing quote, or the file ends in quotes  */
+  FS_MATCH_BAD_CR = 8,      /* '\r' outside quotes without '\n'                         */
+  FS_MATCH_BAD_FIELDS = 16, /* a row without twelve fields                              */
+  FS_MATCH_BAD_INT = 32,    /* fan_ix, orig_ix or lev is not 1..10 plain digits < 2^32  */
+  FS_MATCH_BAD_UTF8 = 64,   /* malformed UTF-8                                          */
+  FS_MATCH_BAD_ROW = 128,   /* a row of 2^32 bytes or more                              */
+  FS_MATCH_BAD_DEFER = 256  /* too many numeric fields left to the host                 */
+};
+
+/* Where the fields of row r lie: field f is bytes[start + (f ? end[f - 1] + 1 : 0) ..
+ * start + end[f]), for a quoted field (bit f of `quoted`) with its quotes, "" pairs as
+ * written.  head: FAN_WORK_FILENAME's bytes differ from those of the row in front (1 for the
+ * first row); equal names written differently both count as heads, the host merges them. */
+typedef struct fs_match_ix {
+  uint64_t start;                /* offset of the row's first byte in the file           */
+  uint32_t end[FS_MATCH_FIELDS]; /* end of every field, relative to start                */
+  uint32_t quoted;
+  uint32_t head;
+} fs_match_ix;                   /* 64 bytes                                             */
+
+typedef struct fs_match_defer {
+  uint32_t row, col;             /* col: 9 BEST_MATCH_DISTANCE, 11 BEST_COMBINED_DISTANCE */
+} fs_match_defer;
+
+typedef struct fs_matches_info {
+  uint64_t n_rows;       /* non-empty rows, the header row not counted                   */
+  uint64_t n_deferred;
+  uint32_t status;       /* FS_MATCHES_*                                                 */
+  uint32_t reason;       /* FS_MATCH_BAD_* bits when outside                             */
+  uint32_t has_header;   /* the first non-empty row is the header row, byte for byte     */
+  uint32_t reserved;
+  double   ms[8];        /* HIP-event times: upload, quote parity + scan, classify, row scan
+                            + placement, header look + buffers, rows, all of them, 0     */
+} fs_matches_info;       /* 96 bytes                                                     */
+
+/* The file's bytes (host memory) read on HIP device `device`; the handle keeps the bytes and
+ * the results on the device until fs_matches_close.  An empty file or the header alone: zero
+ * rows, no device work.  FS_E_UNSUPPORTED for 2^32 rows or more.  A handle is returned for an
+ * outside file too (only its info is of use). */
+typedef struct fs_matches fs_matches;
+int fs_matches_open(int device, const uint8_t* bytes, uint64_t n_bytes, fs_matches** out,
+                    fs_matches_info* info);
+/* The columns and the index of the info.n_rows rows and the deferred fields (in no order) into
+ * host buffers of `cap` rows and `defer_cap` entries; FS_E_CAPACITY when either is too small
+ * (the info says what is needed), FS_E_INVALID for an outside file. */
+int fs_matches_read(fs_matches* m, uint32_t* fan_ix, uint32_t* orig_ix, uint32_t* lev,
+                    double* dist, double* comb, fs_match_ix* ix, uint64_t cap,
+                    fs_match_defer* deferred, uint64_t defer_cap);
+/* The label check of `works` and `quotes`: first[w] = smallest row whose orig_ix is w
+ * (0xFFFFFFFF: none), *n_differ = rows whose field `column` differs in its bytes from that of
+ * first[their orig_ix].  0: the column is a function of the script word and first[] names one
+ * row to decode per word; otherwise two spellings occur (two labels, or one quoted two ways)
+ * and the host decides.  FS_E_INVALID for an orig_ix >= n_script or column >= 12. */
+int fs_matches_labels(fs_matches* m, uint32_t column, uint32_t n_script, uint32_t* first,
+                      uint64_t* n_differ);
+void fs_matches_close(fs_matches* m);
+/* The conversion the reader applies to dist and comb, on the host (no GPU involved): 0 and
+ * *out = float(text) bit for bit, or 1 ("not mine": *out untouched) as described above. */
+int fs_matches_parse_double(const uint8_t* bytes, uint64_t len, double* out);
+
 /* Timing events ride on every `period`-th scan launch only (default 1 = every
  * launch); searches in between report scan_ms = 0.  The events cost a few
  * microseconds of stream time per launch, which matters for sub-100 us searches. */
