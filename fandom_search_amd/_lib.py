@@ -21,7 +21,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_scan_benchmark", "fs_corpus_update_begin", "fs_corpus_update_end",
            "fs_host_alloc", "fs_host_free", "fs_rows_unpack", "fs_rows_unpack8",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
-           "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows",
+           "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_debug_stamps",
            "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_stream_floor",
@@ -30,6 +30,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_csvw_create", "fs_csvw_destroy", "fs_csvw_set_script", "fs_csvw_add_strings", "fs_csvw_strings",
            "fs_csvw_format",
            "fs_matches_open", "fs_matches_read", "fs_matches_labels", "fs_matches_close",
+           "fs_matches_intern", "fs_matches_intern_times",
            "fs_matches_parse_double")
 
 
@@ -184,6 +185,13 @@ def load():
                                   C.c_uint64]
     L.fs_matches_labels.restype = C.c_int
     L.fs_matches_labels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p, u64p]
+    L.fs_variants.restype = C.c_int
+    L.fs_variants.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_matches_intern.restype = C.c_int
+    L.fs_matches_intern.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint64, u64p]
+    L.fs_matches_intern_times.restype = C.c_int
+    L.fs_matches_intern_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.fs_matches_close.restype = None
     L.fs_matches_close.argtypes = [C.c_void_p]
     L.fs_matches_parse_double.restype = C.c_int

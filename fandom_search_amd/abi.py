@@ -115,6 +115,14 @@ QUOTE_REGION_DTYPE = np.dtype([("first", np.uint32), ("last", np.uint32),
                                ("peak_last", np.uint32), ("reserved", np.uint32)])
 assert QUOTE_REGION_DTYPE.itemsize == 40
 
+# fs_variant_cell, fs_variant_word: 16 bytes each
+VARIANT_CELL_DTYPE = np.dtype([("orig_ix", np.uint32), ("spell", np.uint32),
+                               ("n_records", np.uint32), ("n_works", np.uint32)])
+assert VARIANT_CELL_DTYPE.itemsize == 16
+VARIANT_WORD_DTYPE = np.dtype([("n_records", np.uint32), ("n_spellings", np.uint32),
+                               ("n_works", np.uint32), ("first_cell", np.uint32)])
+assert VARIANT_WORD_DTYPE.itemsize == 16
+
 # the match CSV reader (fs_matches_*): fs_match_ix 64 bytes, fs_match_defer 8, fs_matches_info 96
 FS_MATCH_FIELDS = 12
 FS_MATCHES_PARSED = 0
@@ -143,6 +151,7 @@ class FsMatchesInfo(C.Structure):
 
 
 MATCHES_MS_NAMES = ("upload", "parity", "classify", "place", "header", "rows", "device_total")
+INTERN_MS_NAMES = ("clear", "insert", "number", "copy", "device_total")   # fs_matches_intern_times
 
 
 def default_unique_filter():

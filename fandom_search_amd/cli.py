@@ -4,7 +4,8 @@ and _deprecated.py:83-89), same positionals, flags and output files, and
 `passages`, which joins a match CSV's per-word records into passages of reuse
 (fandom_search_amd/passages.py), and `works`, which summarises them by fan work
 (fandom_search_amd/works.py), and `quotes`, which ranks the stretches of the script by the works
-that reuse them (fandom_search_amd/quotes.py).  The
+that reuse them (fandom_search_amd/quotes.py), and `variants`, which ranks the fan spellings
+under each script word (fandom_search_amd/variants.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -25,7 +26,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -153,6 +154,29 @@ def build_parser():
                                help='who reads the match csv: the GPU (default) or csv.reader; also '
                                     'FANDOM_SEARCH_READER')
     quotes_parser.set_defaults(func=_quotes)
+
+    variants_parser = subparsers.add_parser(
+        'variants', help='ranks, under each script word, the spellings fans wrote there: per '
+                         'script word and fan spelling, how many records and works')
+    variants_parser.add_argument('matches', action='store',
+                                 help='filename for search output (dated or batch file)')
+    variants_parser.add_argument('-o', '--output', action='store', default=None,
+                                 help='prefix of the two csv files, PREFIX-variants.csv and '
+                                      'PREFIX-variants-words.csv (default: the input name '
+                                      'without .csv)')
+    variants_parser.add_argument('--top', default=10, type=int,
+                                 help='spellings listed per script word, the most frequent '
+                                      'first; 0: all; default 10')
+    variants_parser.add_argument('--min-records', default=1, type=int,
+                                 help='fewest records a listed spelling has, default 1')
+    variants_parser.add_argument('--fold-case', action='store_true',
+                                 help='spellings equal when lower-cased are one spelling, shown '
+                                      'as its first appearance wrote it')
+    variants_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    variants_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                 help='who reads the match csv: the GPU (default) or csv.reader; '
+                                      'also FANDOM_SEARCH_READER')
+    variants_parser.set_defaults(func=_variants)
     return parser
 
 
@@ -215,6 +239,16 @@ def _quotes(args):
         return quotes.process(args)
     except ValueError as e:
         sys.exit('ao3.py quotes: error: %s' % e)
+
+
+def _variants(args):
+    from . import variants
+    if args.top < 0 or args.min_records < 1:
+        sys.exit('ao3.py variants: error: --top must be at least 0, --min-records at least 1')
+    try:
+        return variants.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py variants: error: %s' % e)
 
 
 def main(argv=None):

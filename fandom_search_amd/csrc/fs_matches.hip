@@ -16,8 +16,17 @@
 //                  and the head flag (FAN_WORK_FILENAME's bytes differ from the row in front);
 //                  the bytes come from global memory or, staged by the wave, from LDS
 //   k_mt_first / k_mt_differ   the label check of `works` and `quotes`
+// fs_matches_intern numbers the distinct spellings of one text column (`ao3.py variants`):
+//   k_in_insert    one lane per row: hash of its field, a slot of an open-addressing table of
+//                  {tag, row} claimed or found (fs_probe.h; equal tags are compared byte for
+//                  byte), atomicMin of the row into the slot's first row
+//   k_in_count     rows that are their slot's first row, per 256 rows
+//   k_mt_scan      over those counts
+//   k_in_number    a first row's rank is its spelling's id: first-appearance order, no sort
+//   k_in_ids       every row takes the id of its slot
 #include "fs_internal.h"
 #include "fs_dec.h"
+#include "fs_probe.h"
 
 #include <stdlib.h>
 
@@ -458,6 +467,105 @@ __global__ __launch_bounds__(kBlock) void k_mt_differ(const uint8_t* __restrict_
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_differ, (unsigned long long)__popcll(b));
 }
 
+// ---- interning a text column ----
+
+struct InternArgs {
+  const uint8_t* d;
+  const fs_match_ix* ix;
+  uint32_t n, col;
+  uint64_t mask;                 // slots - 1
+  uint64_t hash_mask;            // FS_INTERN_HASH_BITS: the bits of the hash that are kept
+  unsigned long long* slots;     // {tag << 32 | row that claimed the slot}
+  uint32_t* first;               // [slots] smallest row of the slot's spelling
+  uint32_t* slot_of;             // [n]
+  uint32_t* slot_id;             // [slots] id of the slot's spelling
+  uint32_t* cnt;                 // [blocks] first rows per block, then their exclusive scan
+  uint32_t* list;                // [n_distinct] first rows, ascending
+  uint32_t* id;                  // [n]
+};
+
+// where field `col` of row r lies: any offset, any length
+__device__ inline const uint8_t* intern_field(const InternArgs& a, uint32_t r, uint32_t* len) {
+  const fs_match_ix* __restrict__ x = a.ix + r;
+  const uint32_t b = a.col ? x->end[a.col - 1] + 1 : 0;
+  *len = x->end[a.col] - b;
+  return a.d + x->start + b;
+}
+
+__global__ __launch_bounds__(kBlock) void k_in_insert(InternArgs a) {
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  if (r >= a.n) return;
+  uint32_t len;
+  const uint8_t* __restrict__ p = intern_field(a, r, &len);
+  uint64_t h = 0xCBF29CE484222325ull;                       // FNV-1a over the bytes
+  for (uint32_t k = 0; k < len; ++k) h = (h ^ p[k]) * 0x100000001B3ull;
+  h = fs_mix64(fs_mix64(h ^ len) & a.hash_mask);            // the kept bits decide slot and tag
+  const uint32_t tag = (uint32_t)(h >> 32);
+  const auto same = [&](unsigned long long cur) -> bool {
+    if ((uint32_t)(cur >> 32) != tag) return false;
+    uint32_t lj;
+    const uint8_t* __restrict__ q = intern_field(a, (uint32_t)cur, &lj);
+    if (lj != len) return false;
+    for (uint32_t k = 0; k < len; ++k)
+      if (p[k] != q[k]) return false;
+    return true;
+  };
+  bool inserted;
+  const uint64_t slot = fs_probe_insert(a.slots, a.mask, h, (unsigned long long)tag << 32 | r,
+                                        same, &inserted);
+  a.slot_of[r] = (uint32_t)slot;
+  // a value read here is never below the slot's final one: a row at or above it need not try
+  if (r < __hip_atomic_load(&a.first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMin(&a.first[slot], r);
+}
+
+// this row is the first of its spelling; its rank among such rows of the workgroup in *rank,
+// their number in *total
+__device__ inline bool intern_head(const InternArgs& a, uint32_t* rank, uint32_t* total) {
+  __shared__ uint32_t s_w[kBlock / 64];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  const bool head = r < a.n && a.first[a.slot_of[r]] == r;
+  const uint64_t b = __ballot(head);
+  if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
+  __syncthreads();
+  uint32_t pre = (uint32_t)__popcll(b & ((1ull << lane) - 1)), tot = 0;
+  for (uint32_t w = 0; w < kBlock / 64; ++w) {
+    if (w < wave) pre += s_w[w];
+    tot += s_w[w];
+  }
+  *rank = pre;
+  *total = tot;
+  return head;
+}
+
+__global__ __launch_bounds__(kBlock) void k_in_count(InternArgs a) {
+  uint32_t rank, total;
+  intern_head(a, &rank, &total);
+  if (threadIdx.x == 0) a.cnt[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void k_in_number(InternArgs a) {
+  uint32_t rank, total;
+  if (!intern_head(a, &rank, &total)) return;
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t k = a.cnt[blockIdx.x] + rank;
+  a.slot_id[a.slot_of[r]] = k;
+  a.list[k] = r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_in_ids(InternArgs a) {
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  if (r < a.n) a.id[r] = a.slot_id[a.slot_of[r]];
+}
+
+uint64_t intern_hash_mask() {
+  const char* e = getenv("FS_INTERN_HASH_BITS");   // diagnostic: k bits of the hash, 0: all collide
+  if (!e || !*e) return ~0ull;
+  const long k = strtol(e, nullptr, 10);
+  return k <= 0 ? 0ull : k >= 64 ? ~0ull : (1ull << k) - 1;
+}
+
 uint32_t tiles(uint64_t n_bytes) { return (uint32_t)((n_bytes + kTile - 1) / kTile); }
 
 bool staged_default() {
@@ -486,6 +594,10 @@ struct fs_matches {
   DBuf<fs_match_ix> ix;
   DBuf<fs_match_defer> defer;
   uint32_t defer_cap = 0;
+  // fs_matches_intern
+  DBuf<unsigned long long> in_slots;
+  DBuf<uint32_t> in_first, in_slot_of, in_slot_id, in_cnt, in_list, in_id;
+  double in_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -704,6 +816,96 @@ extern "C" int fs_matches_labels(fs_matches* m, uint32_t column, uint32_t n_scri
                         hipMemcpyDeviceToHost, nullptr));
   FS_HIP(hipMemcpyAsync(n_differ, m->total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
   FS_HIP(hipStreamSynchronize(nullptr));
+  return FS_OK;
+}
+
+extern "C" int fs_matches_intern(fs_matches* m, uint32_t column, uint32_t* id, uint32_t* first,
+                                 uint64_t cap, uint64_t* n_distinct) {
+  if (!m || !n_distinct) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  if (m->info.status == FS_MATCHES_OUTSIDE || column >= kFields) {
+    fs_set_error("no parsed file, or column %u of %u", column, kFields);
+    return FS_E_INVALID;
+  }
+  *n_distinct = 0;
+  for (double& t : m->in_ms) t = 0.0;
+  const uint32_t n = (uint32_t)m->info.n_rows;
+  if (!n) return FS_OK;
+  if (!id || (cap && !first)) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  FS_ENTER(m->device);
+  hipEvent_t ev[5];
+  for (auto& e : ev) FS_HIP(hipEventCreate(&e));
+  struct Drop {
+    hipEvent_t* ev;
+    ~Drop() { for (int k = 0; k < 5; ++k) (void)hipEventDestroy(ev[k]); }
+  } drop{ev};
+  uint64_t slots = fs_probe_slots(n);
+  if (slots > (1ull << 32)) slots = 1ull << 32;              // (slot numbers are 32 bits)
+  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  FS_TRY(m->in_slots.reserve(slots));
+  FS_TRY(m->in_first.reserve(slots));
+  FS_TRY(m->in_slot_id.reserve(slots));
+  FS_TRY(m->in_slot_of.reserve(n));
+  FS_TRY(m->in_id.reserve(n));
+  FS_TRY(m->in_cnt.reserve(blocks));
+  InternArgs a{};
+  a.d = m->bytes.p;
+  a.ix = m->ix.p;
+  a.n = n;
+  a.col = column;
+  a.mask = slots - 1;
+  a.hash_mask = intern_hash_mask();
+  a.slots = m->in_slots.p;
+  a.first = m->in_first.p;
+  a.slot_of = m->in_slot_of.p;
+  a.slot_id = m->in_slot_id.p;
+  a.cnt = m->in_cnt.p;
+  a.id = m->in_id.p;
+  FS_HIP(hipEventRecord(ev[0], nullptr));
+  FS_HIP(hipMemsetAsync(a.slots, 0xFF, slots * sizeof(unsigned long long), nullptr));
+  FS_HIP(hipMemsetAsync(a.first, 0xFF, slots * sizeof(uint32_t), nullptr));
+  FS_HIP(hipEventRecord(ev[1], nullptr));
+  hipLaunchKernelGGL(k_in_insert, dim3(blocks), dim3(kBlock), 0, nullptr, a);
+  FS_HIP(hipEventRecord(ev[2], nullptr));
+  hipLaunchKernelGGL(k_in_count, dim3(blocks), dim3(kBlock), 0, nullptr, a);
+  hipLaunchKernelGGL(k_mt_scan, dim3(1), dim3(kScanBlock), 0, nullptr, a.cnt, blocks, m->total.p);
+  FS_HIP(hipGetLastError());
+  uint64_t total = 0;
+  FS_HIP(hipMemcpy(&total, m->total.p, sizeof total, hipMemcpyDeviceToHost));
+  FS_TRY(m->in_list.reserve(total));
+  a.list = m->in_list.p;
+  hipLaunchKernelGGL(k_in_number, dim3(blocks), dim3(kBlock), 0, nullptr, a);
+  hipLaunchKernelGGL(k_in_ids, dim3(blocks), dim3(kBlock), 0, nullptr, a);
+  FS_HIP(hipEventRecord(ev[3], nullptr));
+  FS_HIP(hipGetLastError());
+  FS_HIP(hipMemcpyAsync(id, a.id, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+  if (total <= cap)
+    FS_HIP(hipMemcpyAsync(first, a.list, total * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+  FS_HIP(hipEventRecord(ev[4], nullptr));
+  FS_HIP(hipStreamSynchronize(nullptr));
+  float t;
+  for (int k = 0; k < 4; ++k)
+    if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess) m->in_ms[k] = t;
+  if (hipEventElapsedTime(&t, ev[0], ev[4]) == hipSuccess) m->in_ms[4] = t;
+  *n_distinct = total;
+  if (total > cap) {
+    fs_set_error("%llu spellings need room", (unsigned long long)total);
+    return FS_E_CAPACITY;
+  }
+  return FS_OK;
+}
+
+extern "C" int fs_matches_intern_times(const fs_matches* m, double* ms) {
+  if (!m || !ms) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  for (int k = 0; k < 8; ++k) ms[k] = m->in_ms[k];
   return FS_OK;
 }
 

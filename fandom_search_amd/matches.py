@@ -3,7 +3,8 @@
 `MatchFile` hands the file's bytes to fs_matches_open (csrc/fs_matches.hip), which splits rows
 and fields, converts the five numeric columns and flags the rows whose FAN_WORK_FILENAME
 differs from the row in front.  The host numbers the works from those head rows alone, checks
-the (work, fan_ix) order and decodes only the fields an output row shows (`text`).  The columns
+the (work, fan_ix) order and decodes only the fields an output row shows (`text`); `intern`
+numbers the spellings of a text column on the device (fs_matches_intern), for `variants`.  The columns
 come back in passages.sort_records' form; that function and passages.read_matches stay the
 `python` reader and this one's oracle.
 
@@ -174,6 +175,22 @@ class MatchFile:
         for k in np.flatnonzero(quoted).tolist():
             out[k] = data[a[k] + 1:b[k] - 1].tobytes().replace(b'""', b'"').decode('utf-8')
         return out
+
+    def intern(self, column):
+        """(id, first) of fs_matches_intern: per record the number of its field's spelling (the
+        bytes as written), in first-appearance order, and the first record of every spelling.
+        `intern_ms`: the call's HIP-event times."""
+        L = _lib.load()
+        ids = np.empty(self.n, dtype=np.uint32)
+        first = np.empty(self.n, dtype=np.uint32)            # a spelling has a record
+        got = C.c_uint64(0)
+        _lib.check(L.fs_matches_intern(self._h, int(column), abi.ptr(ids, C.c_uint32),
+                                       abi.ptr(first, C.c_uint32), self.n, C.byref(got)),
+                   "fs_matches_intern")
+        ms = (C.c_double * 8)()
+        _lib.check(L.fs_matches_intern_times(self._h, ms), "fs_matches_intern_times")
+        self.intern_ms = dict(zip(abi.INTERN_MS_NAMES, ms))
+        return ids, first[:got.value]
 
     def label_rows(self, column, n_script):
         """(first, n_differ) of fs_matches_labels: per script word the smallest record that

@@ -392,6 +392,36 @@ int fs_quotes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t
                    fs_quote_word* d_words, fs_quote_region* d_regions, uint64_t cap,
                    uint64_t* n_regions);
 
+/* `ao3.py variants`: what fans wrote at every script word.  A record is (work, orig_ix, spell),
+ * spell the id of its fan word's spelling (fs_matches_intern, or any dense numbering); records
+ * come in any order, every output is a count or a distinct count.  A cell is a (script word,
+ * spelling) pair that has a record. */
+typedef struct fs_variant_cell {
+  uint32_t orig_ix, spell;
+  uint32_t n_records;        /* records of the pair                                     */
+  uint32_t n_works;          /* distinct works among them                               */
+} fs_variant_cell;           /* 16 bytes                                                */
+
+typedef struct fs_variant_word {
+  uint32_t n_records;        /* records with orig_ix == this word                       */
+  uint32_t n_spellings;      /* distinct spellings among them (= its cells)             */
+  uint32_t n_works;          /* distinct works among them                               */
+  uint32_t first_cell;       /* index of its first cell, its top spelling; 0xFFFFFFFF for
+                                a word without records                                  */
+} fs_variant_word;           /* 16 bytes                                                */
+
+/* Host columns in; words[n_script] and `cap` cells out, on HIP device `device`.  The cells are
+ * sorted by orig_ix ascending, then n_records descending, then n_works descending, then spell
+ * ascending: a total order, so the output does not depend on the order of the records.
+ * FS_E_INVALID for a work >= n_works, an orig_ix >= n_script or a spell >= n_spell;
+ * FS_E_UNSUPPORTED for n >= 2^32 or n_script > FS_WORKS_MAX_SCRIPT; FS_E_CAPACITY with *n_cells
+ * = cells required when cap is smaller (words is complete then).  n == 0: zeroed words with
+ * first_cell = 0xFFFFFFFF, *n_cells = 0, without device work.  There is no _rows twin: fs_row
+ * carries no fan word, so records a search left on the device cannot feed this. */
+int fs_variants(int device, const uint32_t* work, const uint32_t* orig_ix, const uint32_t* spell,
+                uint64_t n, uint32_t n_works, uint32_t n_script, uint32_t n_spell,
+                fs_variant_word* words, fs_variant_cell* cells, uint64_t cap, uint64_t* n_cells);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
@@ -467,6 +497,23 @@ int fs_matches_read(fs_matches* m, uint32_t* fan_ix, uint32_t* orig_ix, uint32_t
  * and the host decides.  FS_E_INVALID for an orig_ix >= n_script or column >= 12. */
 int fs_matches_labels(fs_matches* m, uint32_t column, uint32_t n_script, uint32_t* first,
                       uint64_t* n_differ);
+/* The distinct spellings of text column `column`, numbered on the device (`ao3.py variants`):
+ * id[info.n_rows], and the first row of every spelling into first[cap].  Two rows get the same
+ * id exactly when the bytes of the field are equal, quotes and "" pairs as written (bytes are
+ * compared, never hashes alone); a field quoted in one row and bare in another is two
+ * spellings, and the host merges the spellings that decode to the same text.  Ids are in
+ * first-appearance order: id[r] = the distinct spellings whose first row lies before the first
+ * row of r's spelling, what ids.setdefault(text, len(ids)) gives over the rows in file order;
+ * first[k] = the smallest row with spelling k, ascending in k.  FS_E_CAPACITY with *n_distinct =
+ * spellings when cap is smaller (id is complete then, first untouched); FS_E_INVALID for
+ * column >= 12 or an outside file.  Zero rows: *n_distinct = 0, no device work.  The table and
+ * the ids stay behind the handle until fs_matches_close.  FS_INTERN_HASH_BITS=k in the
+ * environment (read per call; diagnostic) keeps k bits of the hash, 0: every string collides. */
+int fs_matches_intern(fs_matches* m, uint32_t column, uint32_t* id, uint32_t* first,
+                      uint64_t cap, uint64_t* n_distinct);
+/* HIP-event times of the handle's last fs_matches_intern into ms[8]: clearing the table,
+ * insert, numbering (count, scan, number, ids), copies out, all of them, 0, 0, 0. */
+int fs_matches_intern_times(const fs_matches* m, double* ms);
 void fs_matches_close(fs_matches* m);
 /* The conversion the reader applies to dist and comb, on the host (no GPU involved): 0 and
  * *out = float(text) bit for bit, or 1 ("not mine": *out untouched) as described above. */
