@@ -22,6 +22,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_host_alloc", "fs_host_free", "fs_rows_unpack", "fs_rows_unpack8",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
+           "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_debug_stamps",
            "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_stream_floor",
@@ -176,6 +177,15 @@ def load():
     L.fs_quotes_rows.restype = C.c_int
     L.fs_quotes_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_pairs.restype = C.c_int
+    L.fs_pairs.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                           u64p]
+    L.fs_pairs_rows.restype = C.c_int
+    L.fs_pairs_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_pairs_times.restype = C.c_int
+    L.fs_pairs_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_open.restype = C.c_int
     L.fs_matches_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p),
                                   C.POINTER(abi.FsMatchesInfo)]

@@ -115,6 +115,16 @@ QUOTE_REGION_DTYPE = np.dtype([("first", np.uint32), ("last", np.uint32),
                                ("peak_last", np.uint32), ("reserved", np.uint32)])
 assert QUOTE_REGION_DTYPE.itemsize == 40
 
+# fs_pair_work: 16 bytes; fs_pair: 32 bytes
+PAIR_WORK_DTYPE = np.dtype([("covered", np.uint32), ("partners", np.uint32),
+                            ("best", np.uint32), ("best_shared", np.uint32)])
+assert PAIR_WORK_DTYPE.itemsize == 16
+PAIR_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("shared", np.uint32),
+                       ("first", np.uint32), ("last", np.uint32), ("run_first", np.uint32),
+                       ("run_words", np.uint32), ("reserved", np.uint32)])
+assert PAIR_DTYPE.itemsize == 32
+FS_PAIRS_MAX_BYTES = 1 << 30
+
 # fs_variant_cell, fs_variant_word: 16 bytes each
 VARIANT_CELL_DTYPE = np.dtype([("orig_ix", np.uint32), ("spell", np.uint32),
                                ("n_records", np.uint32), ("n_works", np.uint32)])

@@ -5,7 +5,8 @@ and _deprecated.py:83-89), same positionals, flags and output files, and
 (fandom_search_amd/passages.py), and `works`, which summarises them by fan work
 (fandom_search_amd/works.py), and `quotes`, which ranks the stretches of the script by the works
 that reuse them (fandom_search_amd/quotes.py), and `variants`, which ranks the fan spellings
-under each script word (fandom_search_amd/variants.py).  The
+under each script word (fandom_search_amd/variants.py), and `pairs`, which ranks the pairs of fan
+works by the script words both quote (fandom_search_amd/pairs.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -26,7 +27,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -177,6 +178,29 @@ def build_parser():
                                  help='who reads the match csv: the GPU (default) or csv.reader; '
                                       'also FANDOM_SEARCH_READER')
     variants_parser.set_defaults(func=_variants)
+
+    pairs_parser = subparsers.add_parser(
+        'pairs', help='ranks the pairs of fan works by the script words both quote: per pair '
+                      'the shared words and their longest run, per work its closest partner')
+    pairs_parser.add_argument('matches', action='store',
+                              help='filename for search output (dated or batch file)')
+    pairs_parser.add_argument('-o', '--output', action='store', default=None,
+                              help='prefix of the two csv files, PREFIX-pairs.csv and '
+                                   'PREFIX-pairs-works.csv (default: the input name without '
+                                   '.csv)')
+    pairs_parser.add_argument('--min-words', default=6, type=int,
+                              help='fewest matched words a passage has, default 6')
+    pairs_parser.add_argument('--max-gap', default=0, type=int,
+                              help='words without a record a passage may step over on each '
+                                   'side at once, default 0')
+    pairs_parser.add_argument('--min-shared', default=6, type=int,
+                              help='fewest script words the passages of both works of a listed '
+                                   'pair cover, default 6')
+    pairs_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    pairs_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                              help='who reads the match csv: the GPU (default) or csv.reader; also '
+                                   'FANDOM_SEARCH_READER')
+    pairs_parser.set_defaults(func=_pairs)
     return parser
 
 
@@ -249,6 +273,17 @@ def _variants(args):
         return variants.process(args)
     except ValueError as e:
         sys.exit('ao3.py variants: error: %s' % e)
+
+
+def _pairs(args):
+    from . import pairs
+    if args.min_words < 1 or args.min_shared < 1 or args.max_gap < 0:
+        sys.exit('ao3.py pairs: error: --min-words and --min-shared must be at least 1, '
+                 '--max-gap at least 0')
+    try:
+        return pairs.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py pairs: error: %s' % e)
 
 
 def main(argv=None):

@@ -1,0 +1,624 @@
+// fs_pairs.hip -- `ao3.py pairs`: fan works related by the script words both quote (fs_pairs,
+// fs_pairs_rows in include/fandom_search.h).  The coverage of a work is a row of bits over the
+// script; a pair's shared words are the popcount of the AND of two rows.
+//
+// Every output is an integer, so partial results merge in any order.  Separate launches; no
+// workgroup waits on another:
+//   fs_runs_find     the run heads of fs_passages.hip (and its sortedness check)
+//   k_pairs_check    one lane per record: a work >= n_works, an orig_ix >= n_script
+//   k_pairs_flag     one lane per run: a kept run flags its work as active
+//   k_pairs_scan     one workgroup: active works numbered in work order; later the offsets
+//   k_pairs_list     one lane per work: the work of an active number
+//   k_pairs_cover    one lane per run: a kept run's span ORed into its work's row, a 64-bit
+//                    word at a time
+//   k_pairs_covered  one lane per active work: the popcount of its row
+//   k_pairs_tiles<0> the count pass.  A workgroup takes a row tile of 64 active works and a
+//                    chunk of kChunk column tiles from the upper triangle; per column tile it
+//                    walks the script in K-slices staged in LDS, every thread a 4 x 4 block of
+//                    pair counts; kept pairs per (row, chunk), partners and best of both works
+//   k_pairs_scan     offsets in (row, chunk) order: the pairs come out in (a, b) order
+//   k_pairs_works    one lane per work: its fs_pair_work
+//   k_pairs_tiles<1> the place pass: the column tiles that keep a pair computed again, in
+//                    order, each row's kept pairs placed behind its cursor in ascending b
+//   k_pairs_detail   one lane per kept pair: first, last and the longest run of the AND
+//
+// The matrix is stored by tiles of 64 active works, k-major: word k of row r of tile t is at
+// cov[(t * nk + k) * 64 + r].  A K-slice of a tile is one contiguous piece, staged by a straight
+// coalesced copy; in LDS the four adjacent rows a thread takes are 32 contiguous bytes, two
+// 128-bit reads, and the lanes of a wave read 16 different such pieces (column side) or 4
+// (row side, the others broadcast): no bank is asked twice.  The detail pass reads neighbouring
+// pairs, same a and adjacent b, from adjacent addresses.  Rows past the last active work are
+// zero and share nothing.
+#include "fs_internal.h"
+
+namespace {
+
+constexpr uint32_t kTile = 64;              // active works per tile (tests: TILE)
+constexpr uint32_t kChunk = 8;              // column tiles a workgroup takes (tests: CHUNK)
+constexpr uint32_t kSlice = 32;             // 64-bit words per K-slice (tests: K_SLICE)
+constexpr uint32_t kBlock = 256;            // 16 x 16 threads, 4 x 4 pairs each
+constexpr uint32_t kRunBlock = 256;
+constexpr uint32_t kScanBlock = 1024;
+constexpr uint32_t kShStride = kTile + 1;   // of the tile of counts in LDS
+
+struct RowsSrc {
+  const fs_row* rows;
+  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
+};
+
+struct ColsSrc {
+  const uint32_t* work;
+  const uint32_t* fan;
+  const uint32_t* orig;
+  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
+};
+
+struct PairsArgs {
+  uint32_t n, n_works, n_script, nk, n_runs, min_words, min_shared;
+  uint32_t n_active, n_tiles, n_chunks;
+  const uint32_t* heads;        // [n_runs + 1] first record of a run
+  uint32_t* act;                // [n_works] active flag, then the active number (scanned)
+  uint32_t* work_of;            // [n_tiles * 64] work of an active number (FS_NONE: padding)
+  unsigned long long* cov;      // [n_tiles][nk][64] the coverage matrix
+  uint32_t* covered;            // [n_tiles * 64]
+  uint32_t* partners;           // [n_tiles * 64]
+  unsigned long long* best;     // [n_tiles * 64] shared << 32 | (0xFFFFFFFF - partner)
+  uint32_t* cnt;                // [n_tiles * 64][n_chunks] kept pairs of a row in a chunk
+  unsigned long long* off;      // the same, scanned
+  uint32_t* any;                // [n_tiles][n_chunks] bit t: column tile t of the chunk keeps a pair
+  uint32_t* status;             // [0] invalid input, [1] active works
+  unsigned long long* total;    // kept pairs
+  fs_pair_work* works;
+  fs_pair* pairs;
+};
+
+template <class Src>
+__global__ __launch_bounds__(kRunBlock) void k_pairs_check(Src src, PairsArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  bool bad = false;
+  if (i < a.n) {
+    const uint4 k = src.key(i);
+    bad = k.x >= a.n_works || k.z >= a.n_script;
+  }
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.status[0], 1u);
+}
+
+// one lane per run (after k_pairs_check found nothing: every work and word is inside)
+template <class Src>
+__global__ __launch_bounds__(kRunBlock) void k_pairs_flag(Src src, PairsArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  if (r >= a.n_runs) return;
+  const uint32_t h = a.heads[r], e = a.heads[r + 1];
+  if (e - h < a.min_words) return;
+  const uint32_t w = src.key(h).x;
+  if (w < a.n_works) a.act[w] = 1u;
+}
+
+// exclusive scan of in[0..nb) into out, *total = sum (one workgroup, chunks of 1024 in turn)
+template <class Out>
+__global__ __launch_bounds__(kScanBlock) void k_pairs_scan(const uint32_t* in, uint64_t nb,
+                                                           Out* out, Out* __restrict__ total) {
+  __shared__ Out s_w[kScanBlock / 64];
+  __shared__ Out s_carry;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_carry = 0;
+  __syncthreads();
+  for (uint64_t c = 0; c < nb; c += kScanBlock) {
+    const uint64_t j = c + threadIdx.x;
+    const Out x = j < nb ? (Out)in[j] : (Out)0;
+    Out inc = x;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const Out y = __shfl_up(inc, d);
+      if (lane >= d) inc += y;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    Out pre = 0, tot = 0;
+    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
+      const Out t = s_w[w];
+      if (w < wave) pre += t;
+      tot += t;
+    }
+    const Out carry = s_carry;
+    if (j < nb) out[j] = carry + pre + inc - x;
+    __syncthreads();                       // s_w and s_carry read by every wave
+    if (threadIdx.x == 0) s_carry = carry + tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = s_carry;
+}
+
+// one lane per work, before the scan's numbers replace the flags: flag[w] is kept in `flag`
+__global__ __launch_bounds__(kRunBlock) void k_pairs_list(PairsArgs a, const uint32_t* flag) {
+  const uint64_t w = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  if (w < a.n_works && flag[w]) a.work_of[a.act[w]] = (uint32_t)w;
+}
+
+template <class Src>
+__global__ __launch_bounds__(kRunBlock) void k_pairs_cover(Src src, PairsArgs a,
+                                                           const uint32_t* flag) {
+  const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  if (r >= a.n_runs) return;
+  const uint32_t h = a.heads[r], e = a.heads[r + 1];
+  if (e - h < a.min_words) return;
+  const uint4 k = src.key(h);
+  const uint32_t o0 = k.z, o1 = src.key((uint64_t)e - 1).z;     // o0 <= o1: a run steps forward
+  if (k.x >= a.n_works || !flag[k.x] || o1 >= a.n_script || o0 > o1) return;
+  const uint32_t ai = a.act[k.x];
+  unsigned long long* row = a.cov + (size_t)(ai / kTile) * a.nk * kTile + ai % kTile;
+  const uint32_t k0 = o0 >> 6, k1 = o1 >> 6;
+  for (uint32_t w = k0; w <= k1; ++w) {
+    unsigned long long m = ~0ull;
+    if (w == k0) m &= ~0ull << (o0 & 63);
+    if (w == k1) m &= ~0ull >> (63 - (o1 & 63));
+    atomicOr(&row[(size_t)w * kTile], m);
+  }
+}
+
+// a workgroup of 64 lanes per tile: lane r sums row r (adjacent lanes, adjacent addresses)
+__global__ __launch_bounds__(kTile) void k_pairs_covered(PairsArgs a) {
+  const unsigned long long* t = a.cov + (size_t)blockIdx.x * a.nk * kTile + threadIdx.x;
+  uint32_t c = 0;
+  for (uint32_t k = 0; k < a.nk; ++k) c += (uint32_t)__popcll(t[(size_t)k * kTile]);
+  a.covered[(size_t)blockIdx.x * kTile + threadIdx.x] = c;
+}
+
+__device__ inline unsigned long long wave_max(unsigned long long v) {
+  for (uint32_t d = 32; d; d >>= 1) {
+    const unsigned long long o = __shfl_xor(v, d);
+    if (o > v) v = o;
+  }
+  return v;
+}
+
+// The 64 x 64 counts of row tile ti against column tile tj into s_sh (stride kShStride); the
+// workgroup is synchronised on return.
+__device__ inline void tile_counts(const PairsArgs& a, uint32_t ti, uint32_t tj,
+                                   unsigned long long* s_a, unsigned long long* s_b,
+                                   uint32_t* s_sh) {
+  const uint32_t ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  uint32_t acc[4][4] = {};
+  const unsigned long long* ga = a.cov + (size_t)ti * a.nk * kTile;
+  const unsigned long long* gb = a.cov + (size_t)tj * a.nk * kTile;
+  for (uint32_t k0 = 0; k0 < a.nk; k0 += kSlice) {
+    const uint32_t kc = a.nk - k0 < kSlice ? a.nk - k0 : kSlice;
+    const ulonglong2* va = reinterpret_cast<const ulonglong2*>(ga + (size_t)k0 * kTile);
+    const ulonglong2* vb = reinterpret_cast<const ulonglong2*>(gb + (size_t)k0 * kTile);
+    for (uint32_t v = threadIdx.x; v < kc * (kTile / 2); v += kBlock) {
+      reinterpret_cast<ulonglong2*>(s_a)[v] = va[v];
+      reinterpret_cast<ulonglong2*>(s_b)[v] = vb[v];
+    }
+    __syncthreads();
+    for (uint32_t k = 0; k < kc; ++k) {
+      const ulonglong2* pa = reinterpret_cast<const ulonglong2*>(s_a + k * kTile + ty * 4);
+      const ulonglong2* pb = reinterpret_cast<const ulonglong2*>(s_b + k * kTile + tx * 4);
+      const ulonglong2 a01 = pa[0], a23 = pa[1], b01 = pb[0], b23 = pb[1];
+      const unsigned long long ra[4] = {a01.x, a01.y, a23.x, a23.y};
+      const unsigned long long rb[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+      for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) acc[i][j] += (uint32_t)__popcll(ra[i] & rb[j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) s_sh[(ty * 4 + i) * kShStride + tx * 4 + j] = acc[i][j];
+  __syncthreads();
+}
+
+// blockIdx.x = row tile * n_chunks + chunk.  kPlace 0: counts, partners, best; 1: the pairs.
+template <int kPlace>
+__global__ __launch_bounds__(kBlock) void k_pairs_tiles(PairsArgs a) {
+  __shared__ __align__(16) unsigned long long s_a[kSlice * kTile];
+  __shared__ __align__(16) unsigned long long s_b[kSlice * kTile];
+  __shared__ uint32_t s_sh[kTile * kShStride];
+  __shared__ uint32_t s_wa[kTile], s_wb[kTile], s_rowcnt[kTile];
+  __shared__ unsigned long long s_cur[kTile];
+  __shared__ uint32_t s_any;
+  const uint32_t ti = blockIdx.x / a.n_chunks, c = blockIdx.x % a.n_chunks;
+  const uint32_t tj0 = ti > c * kChunk ? ti : c * kChunk;
+  const uint32_t tj1 = (c + 1) * kChunk < a.n_tiles ? (c + 1) * kChunk : a.n_tiles;
+  if (tj0 >= tj1) return;                                // below the diagonal
+  const uint32_t mask = kPlace ? a.any[blockIdx.x] : 0u;
+  if (kPlace && !mask) return;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x < kTile) {
+    s_wa[threadIdx.x] = a.work_of[(size_t)ti * kTile + threadIdx.x];
+    s_rowcnt[threadIdx.x] = 0;
+    if (kPlace)
+      s_cur[threadIdx.x] = a.off[((size_t)ti * kTile + threadIdx.x) * a.n_chunks + c];
+  }
+  if (threadIdx.x == 0) s_any = 0;
+  for (uint32_t tj = tj0; tj < tj1; ++tj) {
+    if (kPlace && !((mask >> (tj - c * kChunk)) & 1)) continue;
+    __syncthreads();                                     // s_wb and s_sh of the tile before
+    if (threadIdx.x < kTile) s_wb[threadIdx.x] = a.work_of[(size_t)tj * kTile + threadIdx.x];
+    tile_counts(a, ti, tj, s_a, s_b, s_sh);
+    const bool diag = tj == ti;
+    // rows: wave w takes rows 16 w .. 16 w + 15, a lane per column
+    bool kept_any = false;
+    for (uint32_t rr = 0; rr < kTile / 4; ++rr) {
+      const uint32_t r = wave * (kTile / 4) + rr;
+      const uint32_t sh = s_sh[r * kShStride + lane];
+      const bool keep = sh >= a.min_shared && (!diag || r < lane);
+      const uint64_t m = __ballot(keep);
+      if (!m) continue;
+      kept_any = true;
+      const uint32_t cn = (uint32_t)__popcll(m);
+      if (kPlace) {
+        const unsigned long long pos = s_cur[r] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+        if (keep) {
+          uint4* p = reinterpret_cast<uint4*>(a.pairs + pos);
+          p[0] = make_uint4(s_wa[r], s_wb[lane], sh, 0u);
+          p[1] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        if (lane == 0) s_cur[r] += cn;
+      } else {
+        const unsigned long long key =
+            wave_max(keep ? ((unsigned long long)sh << 32) | (0xFFFFFFFFu - s_wb[lane]) : 0ull);
+        if (lane == 0) {
+          s_rowcnt[r] += cn;
+          atomicAdd(&a.partners[(size_t)ti * kTile + r], cn);
+          atomicMax(&a.best[(size_t)ti * kTile + r], key);
+        }
+      }
+    }
+    if (kPlace) continue;
+    if (kept_any && lane == 0) atomicOr(&s_any, 1u << (tj - c * kChunk));
+    // columns: wave w takes columns 16 w .. 16 w + 15, a lane per row
+    if (!__syncthreads_or(kept_any)) continue;
+    for (uint32_t cc = 0; cc < kTile / 4; ++cc) {
+      const uint32_t col = wave * (kTile / 4) + cc;
+      const uint32_t sh = s_sh[lane * kShStride + col];
+      const bool keep = sh >= a.min_shared && (!diag || lane < col);
+      const uint64_t m = __ballot(keep);
+      if (!m) continue;
+      const unsigned long long key =
+          wave_max(keep ? ((unsigned long long)sh << 32) | (0xFFFFFFFFu - s_wa[lane]) : 0ull);
+      if (lane == 0) {
+        atomicAdd(&a.partners[(size_t)tj * kTile + col], (uint32_t)__popcll(m));
+        atomicMax(&a.best[(size_t)tj * kTile + col], key);
+      }
+    }
+  }
+  if (kPlace) return;
+  __syncthreads();
+  if (threadIdx.x < kTile)
+    a.cnt[((size_t)ti * kTile + threadIdx.x) * a.n_chunks + c] = s_rowcnt[threadIdx.x];
+  if (threadIdx.x == 0) a.any[blockIdx.x] = s_any;
+}
+
+// one lane per work
+__global__ __launch_bounds__(kRunBlock) void k_pairs_works(PairsArgs a, const uint32_t* flag) {
+  const uint64_t w = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  if (w >= a.n_works) return;
+  uint4 o = make_uint4(0u, 0u, FS_NONE, 0u);
+  if (flag && flag[w]) {
+    const uint32_t ai = a.act[w];
+    const unsigned long long b = a.best[ai];
+    o.x = a.covered[ai];
+    o.y = a.partners[ai];
+    if (o.y) {
+      o.z = 0xFFFFFFFFu - (uint32_t)b;
+      o.w = (uint32_t)(b >> 32);
+    }
+  }
+  reinterpret_cast<uint4*>(a.works)[w] = o;
+}
+
+// One lane per kept pair: the AND of the two rows walked a 64-bit word at a time, the open
+// run's start and length carried from word to word.
+__global__ __launch_bounds__(kRunBlock) void k_pairs_detail(PairsArgs a, uint64_t n_pairs) {
+  const uint64_t p = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+  if (p >= n_pairs) return;
+  const uint4 head = reinterpret_cast<const uint4*>(a.pairs + p)[0];
+  const uint32_t ia = a.act[head.x], ib = a.act[head.y];
+  const unsigned long long* ra = a.cov + (size_t)(ia / kTile) * a.nk * kTile + ia % kTile;
+  const unsigned long long* rb = a.cov + (size_t)(ib / kTile) * a.nk * kTile + ib % kTile;
+  uint32_t first = FS_NONE, last = 0, best_s = 0, best_n = 0, cur_s = 0, cur_n = 0;
+  for (uint32_t k = 0; k < a.nk; ++k) {
+    unsigned long long x = ra[(size_t)k * kTile] & rb[(size_t)k * kTile];
+    const uint32_t base = k * 64;
+    if (x == 0) {
+      if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+      cur_n = 0;
+      continue;
+    }
+    if (first == FS_NONE) first = base + (uint32_t)__builtin_ctzll(x);
+    last = base + 63 - (uint32_t)__builtin_clzll(x);
+    if (x == ~0ull) {
+      if (!cur_n) cur_s = base;
+      cur_n += 64;
+      continue;
+    }
+    const uint32_t t = (uint32_t)__builtin_ctzll(~x);      // ones from bit 0 on: the open run goes on
+    if (t) {
+      if (!cur_n) cur_s = base;
+      cur_n += t;
+      x &= ~0ull << t;
+    }
+    if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+    cur_n = 0;
+    while (x) {
+      const uint32_t s = (uint32_t)__builtin_ctzll(x);     // s >= 1: bit t is clear
+      const uint32_t l = (uint32_t)__builtin_ctzll(~(x >> s));
+      if (s + l == 64) {                                   // up to the word's last bit: left open
+        cur_s = base + s;
+        cur_n = l;
+        break;
+      }
+      if (l > best_n) { best_n = l; best_s = base + s; }
+      x &= ~0ull << (s + l);
+    }
+  }
+  if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+  reinterpret_cast<uint4*>(a.pairs + p)[1] = make_uint4(last, best_s, best_n, 0u);
+  a.pairs[p].first = first;
+}
+
+thread_local double t_ms[4];    // coverage, count, place, detail of the last call
+
+// one call: count() through the per-work results and the number of pairs, then write()
+struct PairsJob {
+  DBuf<uint32_t> flag, act, work_of, covered, partners, cnt, any, status;
+  DBuf<unsigned long long> cov, best, off, total;
+  fs_runs* runs = nullptr;
+  hipEvent_t ev[6] = {};
+  PairsArgs a{};
+  uint64_t n_pairs = 0;
+  ~PairsJob() {
+    if (runs) fs_runs_free(runs);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+
+  int mark(int k, hipStream_t s) {
+    if (!ev[k]) FS_HIP(hipEventCreate(&ev[k]));
+    FS_HIP(hipEventRecord(ev[k], s));
+    return FS_OK;
+  }
+  void elapsed(int k, int from, int to) {
+    float ms = 0.f;
+    t_ms[k] = hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess ? (double)ms : 0.0;
+  }
+
+  // d_works written, n_pairs set (all on `s`, finished on return)
+  template <class Src>
+  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
+            uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
+            uint32_t min_shared, fs_pair_work* d_works, hipStream_t s) {
+    for (double& t : t_ms) t = 0.0;
+    a.n = n;
+    a.n_works = n_works;
+    a.n_script = n_script;
+    a.nk = (n_script + 63) / 64;
+    a.min_words = min_words;
+    a.min_shared = min_shared;
+    a.works = d_works;
+    const dim3 work_grid((n_works + kRunBlock - 1) / kRunBlock), blk(kRunBlock);
+    if (!n) {
+      if (n_works) hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
+      FS_HIP(hipGetLastError());
+      FS_HIP(hipStreamSynchronize(s));
+      return FS_OK;
+    }
+    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &runs,
+                        &a.heads, &a.n_runs));
+    if (!n_works || !n_script) return invalid();
+    FS_TRY(flag.reserve(n_works));
+    FS_TRY(act.reserve(n_works));
+    FS_TRY(status.reserve(4));
+    FS_HIP(hipMemsetAsync(flag.p, 0, (size_t)n_works * sizeof(uint32_t), s));
+    FS_HIP(hipMemsetAsync(status.p, 0, 4 * sizeof(uint32_t), s));
+    a.act = flag.p;                                  // k_pairs_flag writes the flags
+    a.status = status.p;
+    const dim3 run_grid((a.n_runs + kRunBlock - 1) / kRunBlock);
+    hipLaunchKernelGGL(k_pairs_check<Src>, dim3((n + kRunBlock - 1) / kRunBlock), blk, 0, s, src, a);
+    hipLaunchKernelGGL(k_pairs_flag<Src>, run_grid, blk, 0, s, src, a);
+    hipLaunchKernelGGL(k_pairs_scan<uint32_t>, dim3(1), dim3(kScanBlock), 0, s, flag.p,
+                       (uint64_t)n_works, act.p, status.p + 1);
+    FS_HIP(hipGetLastError());
+    uint32_t st[2];
+    FS_HIP(hipMemcpyAsync(st, status.p, sizeof st, hipMemcpyDeviceToHost, s));
+    FS_HIP(hipStreamSynchronize(s));
+    if (st[0]) return invalid();
+    a.act = act.p;
+    a.n_active = st[1];
+    if (!a.n_active) {
+      hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
+      FS_HIP(hipGetLastError());
+      FS_HIP(hipStreamSynchronize(s));
+      return FS_OK;
+    }
+    if ((uint64_t)a.n_active * a.nk * 8 > FS_PAIRS_MAX_BYTES) {
+      fs_set_error("%u works with a passage over %u script words: a coverage matrix of more "
+                   "than %u bytes", a.n_active, n_script, FS_PAIRS_MAX_BYTES);
+      return FS_E_UNSUPPORTED;
+    }
+    a.n_tiles = (a.n_active + kTile - 1) / kTile;
+    a.n_chunks = (a.n_tiles + kChunk - 1) / kChunk;
+    const size_t rows = (size_t)a.n_tiles * kTile, cells = rows * a.n_chunks;
+    const uint64_t blocks = (uint64_t)a.n_tiles * a.n_chunks;
+    if (blocks > 0x7FFFFFFFull) {
+      fs_set_error("%u works with a passage: more tiles of pairs than a launch takes",
+                   a.n_active);
+      return FS_E_UNSUPPORTED;
+    }
+    FS_TRY(work_of.reserve(rows));
+    FS_TRY(covered.reserve(rows));
+    FS_TRY(partners.reserve(rows));
+    FS_TRY(best.reserve(rows));
+    FS_TRY(cov.reserve(rows * a.nk));
+    FS_TRY(cnt.reserve(cells));
+    FS_TRY(off.reserve(cells));
+    FS_TRY(any.reserve((size_t)blocks));
+    FS_TRY(total.reserve(1));
+    FS_HIP(hipMemsetAsync(work_of.p, 0xFF, rows * sizeof(uint32_t), s));
+    FS_HIP(hipMemsetAsync(partners.p, 0, rows * sizeof(uint32_t), s));
+    FS_HIP(hipMemsetAsync(best.p, 0, rows * sizeof(unsigned long long), s));
+    FS_HIP(hipMemsetAsync(cov.p, 0, rows * a.nk * sizeof(unsigned long long), s));
+    FS_HIP(hipMemsetAsync(cnt.p, 0, cells * sizeof(uint32_t), s));
+    FS_HIP(hipMemsetAsync(any.p, 0, (size_t)blocks * sizeof(uint32_t), s));
+    a.work_of = work_of.p;
+    a.covered = covered.p;
+    a.partners = partners.p;
+    a.best = best.p;
+    a.cov = cov.p;
+    a.cnt = cnt.p;
+    a.off = off.p;
+    a.any = any.p;
+    a.total = total.p;
+    FS_TRY(mark(0, s));
+    hipLaunchKernelGGL(k_pairs_list, work_grid, blk, 0, s, a, flag.p);
+    hipLaunchKernelGGL(k_pairs_cover<Src>, run_grid, blk, 0, s, src, a, flag.p);
+    hipLaunchKernelGGL(k_pairs_covered, dim3(a.n_tiles), dim3(kTile), 0, s, a);
+    FS_TRY(mark(1, s));
+    hipLaunchKernelGGL(k_pairs_tiles<0>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL(k_pairs_scan<unsigned long long>, dim3(1), dim3(kScanBlock), 0, s, cnt.p,
+                       (uint64_t)cells, off.p, total.p);
+    hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, flag.p);
+    FS_TRY(mark(2, s));
+    FS_HIP(hipGetLastError());
+    unsigned long long tot = 0;
+    FS_HIP(hipMemcpyAsync(&tot, total.p, sizeof tot, hipMemcpyDeviceToHost, s));
+    FS_HIP(hipStreamSynchronize(s));
+    n_pairs = tot;
+    elapsed(0, 0, 1);
+    elapsed(1, 1, 2);
+    return FS_OK;
+  }
+
+  // the n_pairs pairs into d_pairs (finished on return)
+  int write(fs_pair* d_pairs, hipStream_t s) {
+    if (!n_pairs) return FS_OK;
+    a.pairs = d_pairs;
+    FS_TRY(mark(3, s));
+    hipLaunchKernelGGL(k_pairs_tiles<1>, dim3(a.n_tiles * a.n_chunks), dim3(kBlock), 0, s, a);
+    FS_TRY(mark(4, s));
+    hipLaunchKernelGGL(k_pairs_detail, dim3((uint32_t)((n_pairs + kRunBlock - 1) / kRunBlock)),
+                       dim3(kRunBlock), 0, s, a, (uint64_t)n_pairs);
+    FS_TRY(mark(5, s));
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipStreamSynchronize(s));
+    elapsed(2, 3, 4);
+    elapsed(3, 4, 5);
+    return FS_OK;
+  }
+
+  static int invalid() {
+    fs_set_error("a work >= n_works or an orig_ix >= n_script");
+    return FS_E_INVALID;
+  }
+};
+
+// the rules both entry points share
+int pairs_check(uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t min_words,
+                uint32_t min_shared, const void* works, const void* pairs, uint64_t cap,
+                uint64_t* n_pairs) {
+  if (!n_pairs || (n_works && !works) || (cap && !pairs)) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  if (min_words == 0 || min_shared == 0) {
+    fs_set_error("min_words and min_shared must be at least 1");
+    return FS_E_INVALID;
+  }
+  if (n_rows >= (1ull << 32)) {
+    fs_set_error("%llu records: pairs take fewer than 2^32", (unsigned long long)n_rows);
+    return FS_E_UNSUPPORTED;
+  }
+  if (n_script > FS_WORKS_MAX_SCRIPT) {
+    fs_set_error("n_script %u: pairs take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
+    return FS_E_UNSUPPORTED;
+  }
+  *n_pairs = 0;
+  return FS_OK;
+}
+
+}  // namespace
+
+extern "C" int fs_pairs(int device, const uint32_t* work, const uint32_t* fan_ix,
+                        const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works,
+                        uint32_t n_script, uint32_t min_words, uint32_t max_gap,
+                        uint32_t min_shared, fs_pair_work* works, fs_pair* pairs, uint64_t cap,
+                        uint64_t* n_pairs) {
+  FS_TRY(pairs_check(n_rows, n_works, n_script, min_words, min_shared, works, pairs, cap,
+                     n_pairs));
+  if (!n_rows) {
+    const fs_pair_work none{0u, 0u, FS_NONE, 0u};
+    for (uint32_t w = 0; w < n_works; ++w) works[w] = none;
+    return FS_OK;
+  }
+  if (!work || !fan_ix || !orig_ix) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  FS_ENTER(device);
+  const uint32_t n = (uint32_t)n_rows;
+  DBuf<uint32_t> d_work, d_fan, d_orig;
+  DBuf<fs_pair_work> d_works;
+  DBuf<fs_pair> d_pairs;
+  FS_TRY(d_work.upload(work, n, nullptr));
+  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
+  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(d_works.reserve(n_works));
+  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  PairsJob job;
+  FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_shared,
+                   d_works.p, nullptr));
+  if (n_works)
+    FS_HIP(hipMemcpy(works, d_works.p, (size_t)n_works * sizeof(fs_pair_work),
+                     hipMemcpyDeviceToHost));
+  *n_pairs = job.n_pairs;
+  if (job.n_pairs > cap) return FS_E_CAPACITY;
+  if (job.n_pairs) {
+    FS_TRY(d_pairs.reserve(job.n_pairs));
+    FS_TRY(job.write(d_pairs.p, nullptr));
+    FS_HIP(hipMemcpy(pairs, d_pairs.p, (size_t)job.n_pairs * sizeof(fs_pair),
+                     hipMemcpyDeviceToHost));
+  }
+  FS_HIP(hipDeviceSynchronize());
+  return FS_OK;
+}
+
+extern "C" int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                             uint32_t min_words, uint32_t max_gap, uint32_t min_shared,
+                             fs_pair_work* d_works, fs_pair* d_pairs, uint64_t cap,
+                             uint64_t* n_pairs) {
+  if (!ix) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  if (ix->n_script > FS_WORKS_MAX_SCRIPT) {
+    fs_set_error("a script of %llu words: pairs take up to %u", (unsigned long long)ix->n_script,
+                 FS_WORKS_MAX_SCRIPT);
+    return FS_E_UNSUPPORTED;
+  }
+  FS_TRY(pairs_check(n_rows, n_works, (uint32_t)ix->n_script, min_words, min_shared, d_works,
+                     d_pairs, cap, n_pairs));
+  if ((n_rows && (!d_rows || ((uintptr_t)d_rows & 15))) || ((uintptr_t)d_works & 15) ||
+      ((uintptr_t)d_pairs & 15)) {
+    fs_set_error("d_rows, d_works and d_pairs must be 16-byte aligned device pointers");
+    return FS_E_INVALID;
+  }
+  FS_ENTER(ix->device);
+  const RowsSrc src{d_rows};
+  PairsJob job;
+  FS_TRY(job.count(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
+                   min_words, max_gap, min_shared, d_works, ix->stream));
+  *n_pairs = job.n_pairs;
+  if (job.n_pairs > cap) return FS_E_CAPACITY;
+  return job.write(d_pairs, ix->stream);
+}
+
+extern "C" int fs_pairs_times(double* ms) {
+  if (!ms) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  for (int k = 0; k < 4; ++k) ms[k] = t_ms[k];
+  return FS_OK;
+}

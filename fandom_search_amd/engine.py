@@ -522,6 +522,47 @@ class ScriptIndex(object):
                 regions[:n.value * abi.QUOTE_REGION_DTYPE.itemsize].cpu().numpy()
                 .view(abi.QUOTE_REGION_DTYPE))
 
+    def pairs_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_shared=6,
+                     out_ptrs=None, cap=None):
+        """`pairs` over device-resident fs_row records sorted by (work, fan_ix) (after a search
+        or a gather; fs_pairs_rows): per work its coverage, partners and best partner, and the
+        pairs of works sharing >= min_shared script words, in (a, b) order.  Without
+        `out_ptrs`: (abi.PAIR_WORK_DTYPE[n_works], abi.PAIR_DTYPE[n_pairs]) on the host.  With
+        `out_ptrs` = device addresses (works; pairs, a buffer of `cap` of them): the number of
+        pairs; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the works
+        are complete then).  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+
+        def call(works, pairs, cap):
+            return L.fs_pairs_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                   int(min_words), int(max_gap), int(min_shared),
+                                   C.c_void_p(works), C.c_void_p(pairs), int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_pairs_rows", "pair buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_pairs_rows")
+            return int(n.value)
+        import torch
+        works = torch.empty(max(1, int(n_works)) * abi.PAIR_WORK_DTYPE.itemsize,
+                            dtype=torch.uint8, device="cuda")
+        cap = 4096 if cap is None else int(cap)
+        while True:
+            pairs = torch.empty(max(1, cap) * abi.PAIR_DTYPE.itemsize, dtype=torch.uint8,
+                                device="cuda")
+            torch_ready()
+            rc = call(works.data_ptr(), pairs.data_ptr(), cap)
+            if rc == abi.FS_E_CAPACITY:                  # (the count pass says how many)
+                cap = int(n.value)
+                continue
+            _lib.check(rc, "fs_pairs_rows")
+            return (works[:int(n_works) * abi.PAIR_WORK_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.PAIR_WORK_DTYPE),
+                    pairs[:n.value * abi.PAIR_DTYPE.itemsize].cpu().numpy().view(abi.PAIR_DTYPE))
+
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""
         ms = C.c_double(0)

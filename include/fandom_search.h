@@ -392,7 +392,56 @@ int fs_quotes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t
                    fs_quote_word* d_words, fs_quote_region* d_regions, uint64_t cap,
                    uint64_t* n_regions);
 
-/* `ao3.py variants`: what fans wrote at every script word.  A record is (work, orig_ix, spell),
+/* `ao3.py pairs`: fan works related by the script words both quote.  Records and passages as
+ * for fs_quotes.  The coverage C_w of work w is the union, over its passages, of every script
+ * word from the passage's first record to its last (bridged words too); a work without a
+ * passage has none.  For works a < b, shared = |C_a & C_b|; the pair is kept when shared >=
+ * min_shared.  Every output is an integer. */
+typedef struct fs_pair_work {
+  uint32_t covered;          /* |C_w|; 0 for a work without a passage                   */
+  uint32_t partners;         /* kept pairs the work is in                               */
+  uint32_t best;             /* the partner with the largest shared, the smaller work
+                                number on a tie; 0xFFFFFFFF without partners            */
+  uint32_t best_shared;      /* its shared; 0 without partners                          */
+} fs_pair_work;              /* 16 bytes                                                */
+
+typedef struct fs_pair {
+  uint32_t a, b;             /* work numbers, a < b                                     */
+  uint32_t shared;           /* script words in both coverages                          */
+  uint32_t first, last;      /* smallest and largest of them                            */
+  uint32_t run_first;        /* start of the longest run of consecutive script words in
+                                both coverages, the first one among equals              */
+  uint32_t run_words;        /* its length                                              */
+  uint32_t reserved;         /* 0                                                       */
+} fs_pair;                   /* 32 bytes                                                */
+
+/* The coverage matrix is a row of ceil(n_script / 64) 64-bit words per active work (a work
+ * with a passage): active_works * ceil(n_script / 64) * 8 bytes may be up to this. */
+#define FS_PAIRS_MAX_BYTES (1u << 30)
+
+/* Host columns in; works[n_works] and `cap` pairs out, on HIP device `device`.  The pairs come
+ * in (a, b) ascending order.  Both entry points: FS_E_INVALID for min_words == 0, min_shared ==
+ * 0, records out of (work, fan_ix) order, a work >= n_works or an orig_ix >= n_script;
+ * FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or a coverage matrix
+ * above FS_PAIRS_MAX_BYTES; FS_E_CAPACITY with *n_pairs = pairs required when cap is smaller
+ * (works is complete then, pairs untouched).  n_rows == 0: works without coverage, *n_pairs = 0
+ * (fs_pairs: without device work). */
+int fs_pairs(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+             uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t min_words,
+             uint32_t max_gap, uint32_t min_shared, fs_pair_work* works, fs_pair* pairs,
+             uint64_t cap, uint64_t* n_pairs);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                  uint32_t min_words, uint32_t max_gap, uint32_t min_shared,
+                  fs_pair_work* d_works, fs_pair* d_pairs, uint64_t cap, uint64_t* n_pairs);
+/* HIP-event milliseconds of the last fs_pairs / fs_pairs_rows call on this thread: coverage
+ * matrix, count pass (with its scan), place pass, detail pass; 0 for a pass that did not run.
+ * tools/pairs_bench.py. */
+int fs_pairs_times(double* ms);
+
+/* `ao3.py variants`: what fans wrote at every script word. A record is (work, orig_ix, spell),
  * spell the id of its fan word's spelling (fs_matches_intern, or any dense numbering); records
  * come in any order, every output is a count or a distinct count.  A cell is a (script word,
  * spelling) pair that has a record. */
