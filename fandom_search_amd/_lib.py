@@ -23,6 +23,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
+           "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_debug_stamps",
            "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_stream_floor",
@@ -186,6 +187,18 @@ def load():
                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_pairs_times.restype = C.c_int
     L.fs_pairs_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_groups.restype = C.c_int
+    L.fs_groups.argtypes = [C.c_int, u32p, u32p, u32p, C.POINTER(C.c_uint8), C.c_uint64,
+                            C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, C.c_uint32,
+                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                            C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_groups_rows.restype = C.c_int
+    L.fs_groups_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u32p,
+                                 C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64,
+                                 u64p]
+    L.fs_groups_times.restype = C.c_int
+    L.fs_groups_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_open.restype = C.c_int
     L.fs_matches_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p),
                                   C.POINTER(abi.FsMatchesInfo)]

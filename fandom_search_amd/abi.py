@@ -125,6 +125,25 @@ PAIR_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("shared", np.uint32)
 assert PAIR_DTYPE.itemsize == 32
 FS_PAIRS_MAX_BYTES = 1 << 30
 
+# fs_group: 64 bytes; fs_group_cell: 24 bytes; fs_group_word: 16 bytes
+GROUP_DTYPE = np.dtype([("n_works", np.uint32), ("n_passage_works", np.uint32),
+                        ("n_words", np.uint32), ("n_exact", np.uint32),
+                        ("n_passages", np.uint32), ("passage_words", np.uint32),
+                        ("longest", np.uint32), ("covered", np.uint32), ("peak", np.uint32),
+                        ("peak_first", np.uint32), ("top_label", np.uint32),
+                        ("top_label_words", np.uint32), ("n_cells", np.uint32),
+                        ("n_word_rows", np.uint32), ("reserved", np.uint32),
+                        ("reserved2", np.uint32)])
+assert GROUP_DTYPE.itemsize == 64
+GROUP_CELL_DTYPE = np.dtype([("group", np.uint32), ("label", np.uint32), ("n_words", np.uint32),
+                             ("n_exact", np.uint32), ("n_works", np.uint32),
+                             ("reserved", np.uint32)])
+assert GROUP_CELL_DTYPE.itemsize == 24
+GROUP_WORD_DTYPE = np.dtype([("group", np.uint32), ("orig_ix", np.uint32),
+                             ("n_works", np.uint32), ("reserved", np.uint32)])
+assert GROUP_WORD_DTYPE.itemsize == 16
+FS_GROUPS_MAX_BYTES = 1 << 30
+
 # fs_variant_cell, fs_variant_word: 16 bytes each
 VARIANT_CELL_DTYPE = np.dtype([("orig_ix", np.uint32), ("spell", np.uint32),
                                ("n_records", np.uint32), ("n_works", np.uint32)])

@@ -6,7 +6,8 @@ and _deprecated.py:83-89), same positionals, flags and output files, and
 (fandom_search_amd/works.py), and `quotes`, which ranks the stretches of the script by the works
 that reuse them (fandom_search_amd/quotes.py), and `variants`, which ranks the fan spellings
 under each script word (fandom_search_amd/variants.py), and `pairs`, which ranks the pairs of fan
-works by the script words both quote (fandom_search_amd/pairs.py).  The
+works by the script words both quote (fandom_search_amd/pairs.py), and `groups`, which reduces
+the reuse by year, author, language or tag of the works (fandom_search_amd/groups.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -27,7 +28,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -201,6 +202,36 @@ def build_parser():
                               help='who reads the match csv: the GPU (default) or csv.reader; also '
                                    'FANDOM_SEARCH_READER')
     pairs_parser.set_defaults(func=_pairs)
+
+    groups_parser = subparsers.add_parser(
+        'groups', help='reduces the reuse by groups of fan works taken from the metadata csv '
+                       '(year, month, author, language or tag): per group its works, passages '
+                       'and covered script words, per scene and per script word the works')
+    groups_parser.add_argument('matches', action='store',
+                               help='filename for search output (dated or batch file)')
+    groups_parser.add_argument('meta', action='store',
+                               help='filename for the metadata csv (FILENAME, TITLE, AUTHOR, '
+                                    'SUMMARY, NOTES, PUBLICATION_DATE, LANGUAGE, TAGS)')
+    groups_parser.add_argument('--by', default='year',
+                               help='what groups the works: year, month, author, language, tag '
+                                    'or tag:<Category>; default year')
+    groups_parser.add_argument('-o', '--output', action='store', default=None,
+                               help='prefix of the three csv files, PREFIX-groups.csv, '
+                                    'PREFIX-groups-scenes.csv and PREFIX-groups-words.csv '
+                                    '(default: the input name without .csv)')
+    groups_parser.add_argument('--min-words', default=6, type=int,
+                               help='fewest matched words a passage has, default 6')
+    groups_parser.add_argument('--max-gap', default=0, type=int,
+                               help='words without a record a passage may step over on each '
+                                    'side at once, default 0')
+    groups_parser.add_argument('--min-works', default=1, type=int,
+                               help='fewest works of a group whose passages cover a listed '
+                                    'script word, default 1')
+    groups_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    groups_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                               help='who reads the match csv: the GPU (default) or csv.reader; '
+                                    'also FANDOM_SEARCH_READER')
+    groups_parser.set_defaults(func=_groups)
     return parser
 
 
@@ -284,6 +315,18 @@ def _pairs(args):
         return pairs.process(args)
     except ValueError as e:
         sys.exit('ao3.py pairs: error: %s' % e)
+
+
+def _groups(args):
+    from . import groups
+    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0:
+        sys.exit('ao3.py groups: error: --min-words and --min-works must be at least 1, '
+                 '--max-gap at least 0')
+    try:
+        groups.check_by(args.by)
+        return groups.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py groups: error: %s' % e)
 
 
 def main(argv=None):

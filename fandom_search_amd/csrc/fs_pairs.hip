@@ -30,6 +30,7 @@
 // pairs, same a and adjacent b, from adjacent addresses.  Rows past the last active work are
 // zero and share nothing.
 #include "fs_internal.h"
+#include "fs_cover.h"
 
 namespace {
 
@@ -146,13 +147,7 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_cover(Src src, PairsArgs a,
   if (k.x >= a.n_works || !flag[k.x] || o1 >= a.n_script || o0 > o1) return;
   const uint32_t ai = a.act[k.x];
   unsigned long long* row = a.cov + (size_t)(ai / kTile) * a.nk * kTile + ai % kTile;
-  const uint32_t k0 = o0 >> 6, k1 = o1 >> 6;
-  for (uint32_t w = k0; w <= k1; ++w) {
-    unsigned long long m = ~0ull;
-    if (w == k0) m &= ~0ull << (o0 & 63);
-    if (w == k1) m &= ~0ull >> (63 - (o1 & 63));
-    atomicOr(&row[(size_t)w * kTile], m);
-  }
+  fs_cover_span(row, kTile, o0, o1);
 }
 
 // a workgroup of 64 lanes per tile: lane r sums row r (adjacent lanes, adjacent addresses)

@@ -563,6 +563,59 @@ class ScriptIndex(object):
                     .view(abi.PAIR_WORK_DTYPE),
                     pairs[:n.value * abi.PAIR_DTYPE.itemsize].cpu().numpy().view(abi.PAIR_DTYPE))
 
+    def groups_device(self, rows_ptr, n_rows, n_works, mem_off, mem_grp, n_groups, label_of=None,
+                      n_labels=0, min_words=6, max_gap=0, min_works=1, out_ptrs=None, caps=None):
+        """`groups` over device-resident fs_row records sorted by (work, fan_ix) (after a search
+        or a gather; fs_groups_rows); membership (mem_off, mem_grp) and label_of are host
+        arrays.  Without `out_ptrs`: (abi.GROUP_DTYPE[n_groups], abi.GROUP_CELL_DTYPE cells,
+        abi.GROUP_WORD_DTYPE rows) on the host.  With `out_ptrs` = device addresses (groups;
+        cells, a buffer of caps[0]; word rows, a buffer of caps[1]): (cells, word rows) written;
+        FsError(FS_E_CAPACITY) with .required = both counts when a buffer is too small (the
+        groups are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+        nc, nw = C.c_uint64(0), C.c_uint64(0)
+        mem_off, mem_grp = abi.as_u64(mem_off), abi.as_u32(mem_grp)
+        lab = abi.as_u32(label_of) if n_labels else None
+
+        def call(groups, cells, cap_c, words, cap_w):
+            return L.fs_groups_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    abi.ptr(mem_off, C.c_uint64), abi.ptr(mem_grp, C.c_uint32),
+                                    int(n_groups), abi.ptr(lab, C.c_uint32), int(n_labels),
+                                    int(min_words), int(max_gap), int(min_works),
+                                    C.c_void_p(groups), C.c_void_p(cells), int(cap_c),
+                                    C.byref(nc), C.c_void_p(words), int(cap_w), C.byref(nw))
+        if out_ptrs is not None:
+            cap_c, cap_w = caps or (0, 0)
+            rc = call(out_ptrs[0], out_ptrs[1], cap_c, out_ptrs[2], cap_w)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_groups_rows", "cell or word buffer too small")
+                err.required = (int(nc.value), int(nw.value))
+                raise err
+            _lib.check(rc, "fs_groups_rows")
+            return int(nc.value), int(nw.value)
+        import torch
+        groups = torch.empty(max(1, int(n_groups)) * abi.GROUP_DTYPE.itemsize, dtype=torch.uint8,
+                             device="cuda")
+        cap_c, cap_w = caps or (4096, 1 << 16)
+        while True:
+            cells = torch.empty(max(1, cap_c) * abi.GROUP_CELL_DTYPE.itemsize, dtype=torch.uint8,
+                                device="cuda")
+            words = torch.empty(max(1, cap_w) * abi.GROUP_WORD_DTYPE.itemsize, dtype=torch.uint8,
+                                device="cuda")
+            torch_ready()
+            rc = call(groups.data_ptr(), cells.data_ptr(), cap_c, words.data_ptr(), cap_w)
+            if rc == abi.FS_E_CAPACITY:                  # (the count pass says how many)
+                cap_c, cap_w = max(cap_c, int(nc.value)), max(cap_w, int(nw.value))
+                continue
+            _lib.check(rc, "fs_groups_rows")
+            return (groups[:int(n_groups) * abi.GROUP_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.GROUP_DTYPE),
+                    cells[:nc.value * abi.GROUP_CELL_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.GROUP_CELL_DTYPE),
+                    words[:nw.value * abi.GROUP_WORD_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.GROUP_WORD_DTYPE))
+
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""
         ms = C.c_double(0)

@@ -441,6 +441,90 @@ int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t 
  * tools/pairs_bench.py. */
 int fs_pairs_times(double* ms);
 
+/* `ao3.py groups`: the same records reduced by groups of works (a year, an author, a tag).
+ * Records, passages and coverage as for fs_pairs.  Membership is many-to-many: work w is in the
+ * groups mem_grp[mem_off[w] .. mem_off[w + 1]), strictly ascending (a work may be in none, a
+ * group may have no work).  The depth of script word o in group g is the number of different
+ * member works of g whose coverage holds o.  A label (a scene) is label_of[orig_ix] of a
+ * record.  Every output is an integer. */
+typedef struct fs_group {
+  uint32_t n_works;          /* member works with at least one record                   */
+  uint32_t n_passage_works;  /* member works with at least one passage                  */
+  uint32_t n_words;          /* records of member works                                 */
+  uint32_t n_exact;          /* ... with exact != 0 (fs_groups_rows: comb <= 0)         */
+  uint32_t n_passages;       /* passages of member works                                */
+  uint32_t passage_words;    /* records inside them                                     */
+  uint32_t longest;          /* records in the longest                                  */
+  uint32_t covered;          /* script words of depth >= 1                              */
+  uint32_t peak;             /* the largest depth                                       */
+  uint32_t peak_first;       /* smallest word index at the peak; 0xFFFFFFFF at depth 0  */
+  uint32_t top_label;        /* label with the most records, the smallest id on a tie;
+                                0xFFFFFFFF without records or with n_labels == 0        */
+  uint32_t top_label_words;  /* its records                                             */
+  uint32_t n_cells;          /* the group's cells                                       */
+  uint32_t n_word_rows;      /* the group's fs_group_word rows (depth >= min_works)     */
+  uint32_t reserved, reserved2;   /* 0                                                  */
+} fs_group;                  /* 64 bytes                                                */
+
+/* one (group, label) pair that has a record of a member work; sorted by (group, label) */
+typedef struct fs_group_cell {
+  uint32_t group, label;
+  uint32_t n_words;          /* records of the pair                                     */
+  uint32_t n_exact;          /* ... exact ones                                          */
+  uint32_t n_works;          /* member works with a record at the label                 */
+  uint32_t reserved;         /* 0                                                       */
+} fs_group_cell;             /* 24 bytes                                                */
+
+/* one (group, script word) pair of depth >= min_works; sorted by (group, word) */
+typedef struct fs_group_word {
+  uint32_t group, orig_ix;
+  uint32_t n_works;          /* the depth                                               */
+  uint32_t reserved;         /* 0                                                       */
+} fs_group_word;             /* 16 bytes                                                */
+
+/* Counted against this, from the arguments alone and before anything is allocated, with
+ * nk = ceil(n_script / 64) and E = mem_off[n_works], the memberships:
+ *   the coverage rows            n_works * nk * 8
+ *   the depth rows               S * nk * 64 * 4, S = the groups of more than 255 works
+ *   records per (work, label)    n_works * n_labels * 8
+ *   the (group, label) counters  n_groups * n_labels * 12
+ *   rows and cells per block     n_groups * (ceil(nk / 64) + ceil(n_labels / 64)) * 4
+ *   the group-major membership   E * 4 + (groups + E / 255 slabs) * 16
+ * The records, the run heads and the outputs are not counted. */
+#define FS_GROUPS_MAX_BYTES (1u << 30)
+
+/* Host columns and host membership in; groups[n_groups], `cap_cells` cells and `cap_words` word
+ * rows out, on HIP device `device`.  label_of[n_script] gives every script word's label <
+ * n_labels (NULL with n_labels == 0: no cells, top_label = 0xFFFFFFFF).  Both entry points:
+ * FS_E_INVALID for min_words == 0, min_works == 0, records out of (work, fan_ix) order, a work
+ * >= n_works, an orig_ix >= n_script, a group >= n_groups, a label >= n_labels, a work's groups
+ * not strictly ascending, mem_off not non-decreasing or mem_off[0] != 0; FS_E_UNSUPPORTED for
+ * n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or tables above FS_GROUPS_MAX_BYTES (before
+ * anything is allocated); FS_E_CAPACITY with *n_cells and *n_words = the counts required when
+ * either buffer is too small (groups is complete then, cells and words untouched).
+ * n_rows == 0 or n_groups == 0: groups without counts (peak_first = top_label = 0xFFFFFFFF),
+ * *n_cells = *n_words = 0 (fs_groups: without device work). */
+int fs_groups(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              const uint8_t* exact, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+              const uint64_t* mem_off, const uint32_t* mem_grp, uint32_t n_groups,
+              const uint32_t* label_of, uint32_t n_labels, uint32_t min_words, uint32_t max_gap,
+              uint32_t min_works, fs_group* groups, fs_group_cell* cells, uint64_t cap_cells,
+              uint64_t* n_cells, fs_group_word* words, uint64_t cap_words, uint64_t* n_words);
+/* The same over device-resident fs_row records (16-byte aligned; exact: comb <= 0) into device
+ * buffers (d_groups and d_words 16-byte, d_cells 8-byte aligned); membership and label_of stay
+ * host arrays; n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_groups_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   const uint64_t* mem_off, const uint32_t* mem_grp, uint32_t n_groups,
+                   const uint32_t* label_of, uint32_t n_labels, uint32_t min_words,
+                   uint32_t max_gap, uint32_t min_works, fs_group* d_groups,
+                   fs_group_cell* d_cells, uint64_t cap_cells, uint64_t* n_cells,
+                   fs_group_word* d_words, uint64_t cap_words, uint64_t* n_words);
+/* HIP-event milliseconds of the last fs_groups / fs_groups_rows call on this thread: per-work
+ * tables (records, passages, coverage), reduction by group (scalars, labels, depth, counts),
+ * offsets, place pass; 0 for a pass that did not run.  tools/groups_bench.py. */
+int fs_groups_times(double* ms);
+
 /* `ao3.py variants`: what fans wrote at every script word. A record is (work, orig_ix, spell),
  * spell the id of its fan word's spelling (fs_matches_intern, or any dense numbering); records
  * come in any order, every output is a count or a distinct count.  A cell is a (script word,
