@@ -888,9 +888,12 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
   for (uint32_t e = threadIdx.x; e < disp_lds / 16; e += blockDim.x)     // (a multiple of 16 bytes)
     reinterpret_cast<uint4*>(s_dyn + (1u << lw))[e] = reinterpret_cast<const uint4*>(g.disp8)[e];
   copy_filter_to_lds(K ? g.sfilter : g.filter, s_filter, lw);
-  for (uint32_t e = threadIdx.x; e < kCoopSlots + kCoopWaves; e += blockDim.x) C.ring[e] = 0;
+  // (a launch that leaves the hand-off to k_compact holds no CoopLds: launch_scan_rows)
+  if (!sy.rinfo) {
+    for (uint32_t e = threadIdx.x; e < kCoopSlots + kCoopWaves; e += blockDim.x) C.ring[e] = 0;
+    if (threadIdx.x == 0) { C.head = 0; C.tail = 0; C.posted = 0; C.pool = 0; }
+  }
   if (threadIdx.x < n_waves) s_cnt[threadIdx.x] = 0;        // records per wave: LDS atomics add to them
-  if (threadIdx.x == 0) { C.head = 0; C.tail = 0; C.posted = 0; C.pool = 0; }
   // Instruction priority: a wave that scans goes in front of the waves that work their queues
   // off (the ids come from HBM, the rounds wait on L2 and LDS: with the scanners served first
   // the last of them is through 4 us earlier, 19 against 23 us, and the kernel 1.3-1.7 us
