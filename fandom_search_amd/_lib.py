@@ -23,6 +23,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
+           "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_debug_stamps",
@@ -187,6 +188,16 @@ def load():
                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_pairs_times.restype = C.c_int
     L.fs_pairs_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_clusters.restype = C.c_int
+    L.fs_clusters.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_clusters_rows.restype = C.c_int
+    L.fs_clusters_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_clusters_times.restype = C.c_int
+    L.fs_clusters_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_groups.restype = C.c_int
     L.fs_groups.argtypes = [C.c_int, u32p, u32p, u32p, C.POINTER(C.c_uint8), C.c_uint64,
                             C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, C.c_uint32,

@@ -125,6 +125,19 @@ PAIR_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("shared", np.uint32)
 assert PAIR_DTYPE.itemsize == 32
 FS_PAIRS_MAX_BYTES = 1 << 30
 
+# fs_cluster_work: 32 bytes; fs_cluster: 48 bytes
+CLUSTER_WORK_DTYPE = np.dtype([("covered", np.uint32), ("root", np.uint32), ("size", np.uint32),
+                               ("cluster", np.uint32), ("links", np.uint32), ("best", np.uint32),
+                               ("best_shared", np.uint32), ("reserved", np.uint32)])
+assert CLUSTER_WORK_DTYPE.itemsize == 32
+CLUSTER_DTYPE = np.dtype([("root", np.uint32), ("n_works", np.uint32), ("n_links", np.uint32),
+                          ("hub", np.uint32), ("hub_links", np.uint32), ("covered", np.uint32),
+                          ("common", np.uint32), ("peak", np.uint32), ("peak_first", np.uint32),
+                          ("run_first", np.uint32), ("run_words", np.uint32),
+                          ("reserved", np.uint32)])
+assert CLUSTER_DTYPE.itemsize == 48
+FS_CLUSTERS_MAX_BYTES = 1 << 30
+
 # fs_group: 64 bytes; fs_group_cell: 24 bytes; fs_group_word: 16 bytes
 GROUP_DTYPE = np.dtype([("n_works", np.uint32), ("n_passage_works", np.uint32),
                         ("n_words", np.uint32), ("n_exact", np.uint32),

@@ -7,7 +7,9 @@ and _deprecated.py:83-89), same positionals, flags and output files, and
 that reuse them (fandom_search_amd/quotes.py), and `variants`, which ranks the fan spellings
 under each script word (fandom_search_amd/variants.py), and `pairs`, which ranks the pairs of fan
 works by the script words both quote (fandom_search_amd/pairs.py), and `groups`, which reduces
-the reuse by year, author, language or tag of the works (fandom_search_amd/groups.py).  The
+the reuse by year, author, language or tag of the works (fandom_search_amd/groups.py), and
+`clusters`, which gathers the works quoting the same lines into families
+(fandom_search_amd/clusters.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -28,7 +30,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -232,6 +234,41 @@ def build_parser():
                                help='who reads the match csv: the GPU (default) or csv.reader; '
                                     'also FANDOM_SEARCH_READER')
     groups_parser.set_defaults(func=_groups)
+
+    clusters_parser = subparsers.add_parser(
+        'clusters', help='gathers the fan works quoting the same lines into families (connected '
+                         'components of the works linked by shared script words): per family '
+                         'its size, its hub and the words its members have in common, per work '
+                         'its family')
+    clusters_parser.add_argument('matches', action='store',
+                                 help='filename for search output (dated or batch file)')
+    clusters_parser.add_argument('-o', '--output', action='store', default=None,
+                                 help='prefix of the two csv files, PREFIX-clusters.csv and '
+                                      'PREFIX-clusters-works.csv (default: the input name '
+                                      'without .csv)')
+    clusters_parser.add_argument('--min-words', default=6, type=int,
+                                 help='fewest matched words a passage has, default 6')
+    clusters_parser.add_argument('--max-gap', default=0, type=int,
+                                 help='words without a record a passage may step over on each '
+                                      'side at once, default 0')
+    clusters_parser.add_argument('--min-shared', default=6, type=int,
+                                 help='fewest script words the passages of two linked works '
+                                      'both cover, default 6')
+    clusters_parser.add_argument('--min-jaccard', default=50, type=int,
+                                 help='fewest shared words of two linked works as a whole '
+                                      'percentage of the words either covers, 0 to 100, '
+                                      'default 50')
+    clusters_parser.add_argument('--min-size', default=2, type=int,
+                                 help='fewest works of a listed family, default 2')
+    clusters_parser.add_argument('--common', default=50, type=int,
+                                 help='a script word is common to a family when at least this '
+                                      'whole percentage of its works cover it, 1 to 100, '
+                                      'default 50')
+    clusters_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    clusters_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                 help='who reads the match csv: the GPU (default) or '
+                                      'csv.reader; also FANDOM_SEARCH_READER')
+    clusters_parser.set_defaults(func=_clusters)
     return parser
 
 
@@ -327,6 +364,20 @@ def _groups(args):
         return groups.process(args)
     except ValueError as e:
         sys.exit('ao3.py groups: error: %s' % e)
+
+
+def _clusters(args):
+    from . import clusters
+    if args.min_words < 1 or args.min_shared < 1 or args.min_size < 1 or args.max_gap < 0:
+        sys.exit('ao3.py clusters: error: --min-words, --min-shared and --min-size must be at '
+                 'least 1, --max-gap at least 0')
+    if not 0 <= args.min_jaccard <= 100 or not 1 <= args.common <= 100:
+        sys.exit('ao3.py clusters: error: --min-jaccard must be from 0 to 100, --common from 1 '
+                 'to 100')
+    try:
+        return clusters.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py clusters: error: %s' % e)
 
 
 def main(argv=None):

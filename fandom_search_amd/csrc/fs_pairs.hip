@@ -22,187 +22,23 @@
 //                    order, each row's kept pairs placed behind its cursor in ascending b
 //   k_pairs_detail   one lane per kept pair: first, last and the longest run of the AND
 //
-// The matrix is stored by tiles of 64 active works, k-major: word k of row r of tile t is at
-// cov[(t * nk + k) * 64 + r].  A K-slice of a tile is one contiguous piece, staged by a straight
-// coalesced copy; in LDS the four adjacent rows a thread takes are 32 contiguous bytes, two
-// 128-bit reads, and the lanes of a wave read 16 different such pieces (column side) or 4
-// (row side, the others broadcast): no bank is asked twice.  The detail pass reads neighbouring
-// pairs, same a and adjacent b, from adjacent addresses.  Rows past the last active work are
-// zero and share nothing.
-#include "fs_internal.h"
-#include "fs_cover.h"
+// The passes up to the row popcounts and the tile product (tile_counts) live in fs_tiles.h,
+// with the layout of the matrix, and are shared with fs_clusters.hip.  The detail pass reads
+// neighbouring pairs, same a and adjacent b, from adjacent addresses.
+#include "fs_tiles.h"
 
 namespace {
 
-constexpr uint32_t kTile = 64;              // active works per tile (tests: TILE)
-constexpr uint32_t kChunk = 8;              // column tiles a workgroup takes (tests: CHUNK)
-constexpr uint32_t kSlice = 32;             // 64-bit words per K-slice (tests: K_SLICE)
-constexpr uint32_t kBlock = 256;            // 16 x 16 threads, 4 x 4 pairs each
-constexpr uint32_t kRunBlock = 256;
-constexpr uint32_t kScanBlock = 1024;
-constexpr uint32_t kShStride = kTile + 1;   // of the tile of counts in LDS
-
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-};
-
-struct PairsArgs {
-  uint32_t n, n_works, n_script, nk, n_runs, min_words, min_shared;
-  uint32_t n_active, n_tiles, n_chunks;
-  const uint32_t* heads;        // [n_runs + 1] first record of a run
-  uint32_t* act;                // [n_works] active flag, then the active number (scanned)
-  uint32_t* work_of;            // [n_tiles * 64] work of an active number (FS_NONE: padding)
-  unsigned long long* cov;      // [n_tiles][nk][64] the coverage matrix
-  uint32_t* covered;            // [n_tiles * 64]
+struct PairsArgs : CoverArgs {
   uint32_t* partners;           // [n_tiles * 64]
   unsigned long long* best;     // [n_tiles * 64] shared << 32 | (0xFFFFFFFF - partner)
   uint32_t* cnt;                // [n_tiles * 64][n_chunks] kept pairs of a row in a chunk
   unsigned long long* off;      // the same, scanned
   uint32_t* any;                // [n_tiles][n_chunks] bit t: column tile t of the chunk keeps a pair
-  uint32_t* status;             // [0] invalid input, [1] active works
   unsigned long long* total;    // kept pairs
   fs_pair_work* works;
   fs_pair* pairs;
 };
-
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_check(Src src, PairsArgs a) {
-  const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  bool bad = false;
-  if (i < a.n) {
-    const uint4 k = src.key(i);
-    bad = k.x >= a.n_works || k.z >= a.n_script;
-  }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.status[0], 1u);
-}
-
-// one lane per run (after k_pairs_check found nothing: every work and word is inside)
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_flag(Src src, PairsArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  if (r >= a.n_runs) return;
-  const uint32_t h = a.heads[r], e = a.heads[r + 1];
-  if (e - h < a.min_words) return;
-  const uint32_t w = src.key(h).x;
-  if (w < a.n_works) a.act[w] = 1u;
-}
-
-// exclusive scan of in[0..nb) into out, *total = sum (one workgroup, chunks of 1024 in turn)
-template <class Out>
-__global__ __launch_bounds__(kScanBlock) void k_pairs_scan(const uint32_t* in, uint64_t nb,
-                                                           Out* out, Out* __restrict__ total) {
-  __shared__ Out s_w[kScanBlock / 64];
-  __shared__ Out s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const Out x = j < nb ? (Out)in[j] : (Out)0;
-    Out inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const Out y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    Out pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const Out t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const Out carry = s_carry;
-    if (j < nb) out[j] = carry + pre + inc - x;
-    __syncthreads();                       // s_w and s_carry read by every wave
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
-}
-
-// one lane per work, before the scan's numbers replace the flags: flag[w] is kept in `flag`
-__global__ __launch_bounds__(kRunBlock) void k_pairs_list(PairsArgs a, const uint32_t* flag) {
-  const uint64_t w = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  if (w < a.n_works && flag[w]) a.work_of[a.act[w]] = (uint32_t)w;
-}
-
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_cover(Src src, PairsArgs a,
-                                                           const uint32_t* flag) {
-  const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  if (r >= a.n_runs) return;
-  const uint32_t h = a.heads[r], e = a.heads[r + 1];
-  if (e - h < a.min_words) return;
-  const uint4 k = src.key(h);
-  const uint32_t o0 = k.z, o1 = src.key((uint64_t)e - 1).z;     // o0 <= o1: a run steps forward
-  if (k.x >= a.n_works || !flag[k.x] || o1 >= a.n_script || o0 > o1) return;
-  const uint32_t ai = a.act[k.x];
-  unsigned long long* row = a.cov + (size_t)(ai / kTile) * a.nk * kTile + ai % kTile;
-  fs_cover_span(row, kTile, o0, o1);
-}
-
-// a workgroup of 64 lanes per tile: lane r sums row r (adjacent lanes, adjacent addresses)
-__global__ __launch_bounds__(kTile) void k_pairs_covered(PairsArgs a) {
-  const unsigned long long* t = a.cov + (size_t)blockIdx.x * a.nk * kTile + threadIdx.x;
-  uint32_t c = 0;
-  for (uint32_t k = 0; k < a.nk; ++k) c += (uint32_t)__popcll(t[(size_t)k * kTile]);
-  a.covered[(size_t)blockIdx.x * kTile + threadIdx.x] = c;
-}
-
-__device__ inline unsigned long long wave_max(unsigned long long v) {
-  for (uint32_t d = 32; d; d >>= 1) {
-    const unsigned long long o = __shfl_xor(v, d);
-    if (o > v) v = o;
-  }
-  return v;
-}
-
-// The 64 x 64 counts of row tile ti against column tile tj into s_sh (stride kShStride); the
-// workgroup is synchronised on return.
-__device__ inline void tile_counts(const PairsArgs& a, uint32_t ti, uint32_t tj,
-                                   unsigned long long* s_a, unsigned long long* s_b,
-                                   uint32_t* s_sh) {
-  const uint32_t ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-  uint32_t acc[4][4] = {};
-  const unsigned long long* ga = a.cov + (size_t)ti * a.nk * kTile;
-  const unsigned long long* gb = a.cov + (size_t)tj * a.nk * kTile;
-  for (uint32_t k0 = 0; k0 < a.nk; k0 += kSlice) {
-    const uint32_t kc = a.nk - k0 < kSlice ? a.nk - k0 : kSlice;
-    const ulonglong2* va = reinterpret_cast<const ulonglong2*>(ga + (size_t)k0 * kTile);
-    const ulonglong2* vb = reinterpret_cast<const ulonglong2*>(gb + (size_t)k0 * kTile);
-    for (uint32_t v = threadIdx.x; v < kc * (kTile / 2); v += kBlock) {
-      reinterpret_cast<ulonglong2*>(s_a)[v] = va[v];
-      reinterpret_cast<ulonglong2*>(s_b)[v] = vb[v];
-    }
-    __syncthreads();
-    for (uint32_t k = 0; k < kc; ++k) {
-      const ulonglong2* pa = reinterpret_cast<const ulonglong2*>(s_a + k * kTile + ty * 4);
-      const ulonglong2* pb = reinterpret_cast<const ulonglong2*>(s_b + k * kTile + tx * 4);
-      const ulonglong2 a01 = pa[0], a23 = pa[1], b01 = pb[0], b23 = pb[1];
-      const unsigned long long ra[4] = {a01.x, a01.y, a23.x, a23.y};
-      const unsigned long long rb[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) acc[i][j] += (uint32_t)__popcll(ra[i] & rb[j]);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) s_sh[(ty * 4 + i) * kShStride + tx * 4 + j] = acc[i][j];
-  __syncthreads();
-}
 
 // blockIdx.x = row tile * n_chunks + chunk.  kPlace 0: counts, partners, best; 1: the pairs.
 template <int kPlace>
@@ -358,27 +194,12 @@ thread_local double t_ms[4];    // coverage, count, place, detail of the last ca
 
 // one call: count() through the per-work results and the number of pairs, then write()
 struct PairsJob {
-  DBuf<uint32_t> flag, act, work_of, covered, partners, cnt, any, status;
-  DBuf<unsigned long long> cov, best, off, total;
-  fs_runs* runs = nullptr;
-  hipEvent_t ev[6] = {};
+  CoverJob cj;
+  DBuf<uint32_t> partners, cnt, any;
+  DBuf<unsigned long long> best, off, total;
+  PassClock clk;
   PairsArgs a{};
   uint64_t n_pairs = 0;
-  ~PairsJob() {
-    if (runs) fs_runs_free(runs);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-
-  int mark(int k, hipStream_t s) {
-    if (!ev[k]) FS_HIP(hipEventCreate(&ev[k]));
-    FS_HIP(hipEventRecord(ev[k], s));
-    return FS_OK;
-  }
-  void elapsed(int k, int from, int to) {
-    float ms = 0.f;
-    t_ms[k] = hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess ? (double)ms : 0.0;
-  }
 
   // d_works written, n_pairs set (all on `s`, finished on return)
   template <class Src>
@@ -394,36 +215,9 @@ struct PairsJob {
     a.min_shared = min_shared;
     a.works = d_works;
     const dim3 work_grid((n_works + kRunBlock - 1) / kRunBlock), blk(kRunBlock);
-    if (!n) {
-      if (n_works) hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
-      FS_HIP(hipGetLastError());
-      FS_HIP(hipStreamSynchronize(s));
-      return FS_OK;
-    }
-    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &runs,
-                        &a.heads, &a.n_runs));
-    if (!n_works || !n_script) return invalid();
-    FS_TRY(flag.reserve(n_works));
-    FS_TRY(act.reserve(n_works));
-    FS_TRY(status.reserve(4));
-    FS_HIP(hipMemsetAsync(flag.p, 0, (size_t)n_works * sizeof(uint32_t), s));
-    FS_HIP(hipMemsetAsync(status.p, 0, 4 * sizeof(uint32_t), s));
-    a.act = flag.p;                                  // k_pairs_flag writes the flags
-    a.status = status.p;
-    const dim3 run_grid((a.n_runs + kRunBlock - 1) / kRunBlock);
-    hipLaunchKernelGGL(k_pairs_check<Src>, dim3((n + kRunBlock - 1) / kRunBlock), blk, 0, s, src, a);
-    hipLaunchKernelGGL(k_pairs_flag<Src>, run_grid, blk, 0, s, src, a);
-    hipLaunchKernelGGL(k_pairs_scan<uint32_t>, dim3(1), dim3(kScanBlock), 0, s, flag.p,
-                       (uint64_t)n_works, act.p, status.p + 1);
-    FS_HIP(hipGetLastError());
-    uint32_t st[2];
-    FS_HIP(hipMemcpyAsync(st, status.p, sizeof st, hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    if (st[0]) return invalid();
-    a.act = act.p;
-    a.n_active = st[1];
+    if (n) FS_TRY(cj.number(src, d_rows, cols, a, max_gap, s));
     if (!a.n_active) {
-      hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
+      if (n_works) hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
       FS_HIP(hipGetLastError());
       FS_HIP(hipStreamSynchronize(s));
       return FS_OK;
@@ -433,8 +227,6 @@ struct PairsJob {
                    "than %u bytes", a.n_active, n_script, FS_PAIRS_MAX_BYTES);
       return FS_E_UNSUPPORTED;
     }
-    a.n_tiles = (a.n_active + kTile - 1) / kTile;
-    a.n_chunks = (a.n_tiles + kChunk - 1) / kChunk;
     const size_t rows = (size_t)a.n_tiles * kTile, cells = rows * a.n_chunks;
     const uint64_t blocks = (uint64_t)a.n_tiles * a.n_chunks;
     if (blocks > 0x7FFFFFFFull) {
@@ -442,47 +234,38 @@ struct PairsJob {
                    a.n_active);
       return FS_E_UNSUPPORTED;
     }
-    FS_TRY(work_of.reserve(rows));
-    FS_TRY(covered.reserve(rows));
+    FS_TRY(cj.reserve(a, s));
     FS_TRY(partners.reserve(rows));
     FS_TRY(best.reserve(rows));
-    FS_TRY(cov.reserve(rows * a.nk));
     FS_TRY(cnt.reserve(cells));
     FS_TRY(off.reserve(cells));
     FS_TRY(any.reserve((size_t)blocks));
     FS_TRY(total.reserve(1));
-    FS_HIP(hipMemsetAsync(work_of.p, 0xFF, rows * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(partners.p, 0, rows * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(best.p, 0, rows * sizeof(unsigned long long), s));
-    FS_HIP(hipMemsetAsync(cov.p, 0, rows * a.nk * sizeof(unsigned long long), s));
     FS_HIP(hipMemsetAsync(cnt.p, 0, cells * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(any.p, 0, (size_t)blocks * sizeof(uint32_t), s));
-    a.work_of = work_of.p;
-    a.covered = covered.p;
     a.partners = partners.p;
     a.best = best.p;
-    a.cov = cov.p;
     a.cnt = cnt.p;
     a.off = off.p;
     a.any = any.p;
     a.total = total.p;
-    FS_TRY(mark(0, s));
-    hipLaunchKernelGGL(k_pairs_list, work_grid, blk, 0, s, a, flag.p);
-    hipLaunchKernelGGL(k_pairs_cover<Src>, run_grid, blk, 0, s, src, a, flag.p);
-    hipLaunchKernelGGL(k_pairs_covered, dim3(a.n_tiles), dim3(kTile), 0, s, a);
-    FS_TRY(mark(1, s));
+    FS_TRY(clk.mark(0, s));
+    cj.cover(src, a, s);
+    FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_pairs_tiles<0>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_pairs_scan<unsigned long long>, dim3(1), dim3(kScanBlock), 0, s, cnt.p,
                        (uint64_t)cells, off.p, total.p);
-    hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, flag.p);
-    FS_TRY(mark(2, s));
+    hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, cj.flag.p);
+    FS_TRY(clk.mark(2, s));
     FS_HIP(hipGetLastError());
     unsigned long long tot = 0;
     FS_HIP(hipMemcpyAsync(&tot, total.p, sizeof tot, hipMemcpyDeviceToHost, s));
     FS_HIP(hipStreamSynchronize(s));
     n_pairs = tot;
-    elapsed(0, 0, 1);
-    elapsed(1, 1, 2);
+    t_ms[0] = clk.elapsed(0, 1);
+    t_ms[1] = clk.elapsed(1, 2);
     return FS_OK;
   }
 
@@ -490,22 +273,17 @@ struct PairsJob {
   int write(fs_pair* d_pairs, hipStream_t s) {
     if (!n_pairs) return FS_OK;
     a.pairs = d_pairs;
-    FS_TRY(mark(3, s));
+    FS_TRY(clk.mark(3, s));
     hipLaunchKernelGGL(k_pairs_tiles<1>, dim3(a.n_tiles * a.n_chunks), dim3(kBlock), 0, s, a);
-    FS_TRY(mark(4, s));
+    FS_TRY(clk.mark(4, s));
     hipLaunchKernelGGL(k_pairs_detail, dim3((uint32_t)((n_pairs + kRunBlock - 1) / kRunBlock)),
                        dim3(kRunBlock), 0, s, a, (uint64_t)n_pairs);
-    FS_TRY(mark(5, s));
+    FS_TRY(clk.mark(5, s));
     FS_HIP(hipGetLastError());
     FS_HIP(hipStreamSynchronize(s));
-    elapsed(2, 3, 4);
-    elapsed(3, 4, 5);
+    t_ms[2] = clk.elapsed(3, 4);
+    t_ms[3] = clk.elapsed(4, 5);
     return FS_OK;
-  }
-
-  static int invalid() {
-    fs_set_error("a work >= n_works or an orig_ix >= n_script");
-    return FS_E_INVALID;
   }
 };
 

@@ -563,6 +563,50 @@ class ScriptIndex(object):
                     .view(abi.PAIR_WORK_DTYPE),
                     pairs[:n.value * abi.PAIR_DTYPE.itemsize].cpu().numpy().view(abi.PAIR_DTYPE))
 
+    def clusters_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_shared=6,
+                        min_jaccard=50, min_size=2, common_pct=50, out_ptrs=None, cap=None):
+        """`clusters` over device-resident fs_row records sorted by (work, fan_ix) (after a
+        search or a gather; fs_clusters_rows): per work its family, links and best partner, and
+        the families of >= min_size works in ascending order of root.  Without `out_ptrs`:
+        (abi.CLUSTER_WORK_DTYPE[n_works], abi.CLUSTER_DTYPE[n_clusters]) on the host.  With
+        `out_ptrs` = device addresses (works; clusters, a buffer of `cap` of them): the number
+        of families; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the
+        works are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+
+        def call(works, found, cap):
+            return L.fs_clusters_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                      int(min_words), int(max_gap), int(min_shared),
+                                      int(min_jaccard), int(min_size), int(common_pct),
+                                      C.c_void_p(works), C.c_void_p(found), int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_clusters_rows", "cluster buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_clusters_rows")
+            return int(n.value)
+        import torch
+        works = torch.empty(max(1, int(n_works)) * abi.CLUSTER_WORK_DTYPE.itemsize,
+                            dtype=torch.uint8, device="cuda")
+        cap = 4096 if cap is None else int(cap)
+        while True:
+            found = torch.empty(max(1, cap) * abi.CLUSTER_DTYPE.itemsize, dtype=torch.uint8,
+                                device="cuda")
+            torch_ready()
+            rc = call(works.data_ptr(), found.data_ptr(), cap)
+            if rc == abi.FS_E_CAPACITY:                  # (the numbering says how many)
+                cap = int(n.value)
+                continue
+            _lib.check(rc, "fs_clusters_rows")
+            return (works[:int(n_works) * abi.CLUSTER_WORK_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.CLUSTER_WORK_DTYPE),
+                    found[:n.value * abi.CLUSTER_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.CLUSTER_DTYPE))
+
     def groups_device(self, rows_ptr, n_rows, n_works, mem_off, mem_grp, n_groups, label_of=None,
                       n_labels=0, min_words=6, max_gap=0, min_works=1, out_ptrs=None, caps=None):
         """`groups` over device-resident fs_row records sorted by (work, fan_ix) (after a search

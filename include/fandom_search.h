@@ -441,6 +441,82 @@ int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t 
  * tools/pairs_bench.py. */
 int fs_pairs_times(double* ms);
 
+/* `ao3.py clusters`: families of fan works quoting the same lines.  Records, passages and
+ * coverage as for fs_pairs; a work with a passage is active.  Active works a < b are linked when
+ * shared = |C_a & C_b| >= min_shared and 100 * shared >= min_jaccard * (|C_a| + |C_b| - shared)
+ * (min_jaccard: a whole percentage, 0..100; equality links; at 0 the rule is that of fs_pairs).
+ * A family is a connected component of the links over the active works, so two works that
+ * share nothing may be in one family through a third; a single active work is a family of one.
+ * A family of at least min_size works is listed.  The depth of script word o in a family is the
+ * number of its members whose coverage holds o.  Every output is an integer. */
+typedef struct fs_cluster_work {
+  uint32_t covered;          /* |C_w|; 0 for a work without a passage                   */
+  uint32_t root;             /* smallest work number of its family; 0xFFFFFFFF for a
+                                work without a passage                                  */
+  uint32_t size;             /* works in its family; 0 for a work without a passage     */
+  uint32_t cluster;          /* index of its family among the listed ones; 0xFFFFFFFF
+                                when the family is not listed                           */
+  uint32_t links;            /* links the work is in                                    */
+  uint32_t best;             /* the linked partner with the largest shared, the smaller
+                                work number on a tie; 0xFFFFFFFF without links          */
+  uint32_t best_shared;      /* its shared; 0 without links                             */
+  uint32_t reserved;         /* 0                                                       */
+} fs_cluster_work;           /* 32 bytes                                                */
+
+typedef struct fs_cluster {
+  uint32_t root;             /* smallest work number of the family                      */
+  uint32_t n_works;          /* its works                                               */
+  uint32_t n_links;          /* links inside it (0xFFFFFFFF: that many or more)         */
+  uint32_t hub;              /* the member with the most links, the smaller work number
+                                on a tie                                                */
+  uint32_t hub_links;        /* its links                                               */
+  uint32_t covered;          /* script words of depth >= 1                              */
+  uint32_t common;           /* script words of depth >= t,
+                                t = (common_pct * n_works + 99) / 100                   */
+  uint32_t peak;             /* the largest depth                                       */
+  uint32_t peak_first;       /* smallest word index at the peak                         */
+  uint32_t run_first;        /* start of the longest run of consecutive script words of
+                                depth >= t, the first one among equals; 0xFFFFFFFF when
+                                common == 0                                             */
+  uint32_t run_words;        /* its length; 0 when common == 0                          */
+  uint32_t reserved;         /* 0                                                       */
+} fs_cluster;                /* 48 bytes                                                */
+
+/* Counted against this, with A = the active works, nk = ceil(n_script / 64) and before the
+ * work x work product runs:
+ *   the coverage rows              A * nk * 8
+ *   the rows of common-word masks  (A / min_size) * nk * 8, one per listed family at the
+ *                                  most families of min_size works there can be
+ * The per-work and per-family tables of a few words each, the records, the run heads and the
+ * outputs are not counted. */
+#define FS_CLUSTERS_MAX_BYTES (1u << 30)
+
+/* Host columns in; works[n_works] and `cap` listed families out, on HIP device `device`.  The
+ * families come in ascending order of root.  Both entry points: FS_E_INVALID for min_words,
+ * min_shared, min_size or common_pct == 0, min_jaccard > 100, common_pct > 100, records out of
+ * (work, fan_ix) order, a work >= n_works or an orig_ix >= n_script; FS_E_UNSUPPORTED for
+ * n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or tables above FS_CLUSTERS_MAX_BYTES;
+ * FS_E_CAPACITY with *n_clusters = families required when cap is smaller (works is complete
+ * then, clusters untouched).  n_rows == 0: works without coverage, *n_clusters = 0
+ * (fs_clusters: without device work). */
+int fs_clusters(int device, const uint32_t* work, const uint32_t* fan_ix,
+                const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                uint32_t min_words, uint32_t max_gap, uint32_t min_shared, uint32_t min_jaccard,
+                uint32_t min_size, uint32_t common_pct, fs_cluster_work* works,
+                fs_cluster* clusters, uint64_t cap, uint64_t* n_clusters);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_clusters_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                     uint32_t min_words, uint32_t max_gap, uint32_t min_shared,
+                     uint32_t min_jaccard, uint32_t min_size, uint32_t common_pct,
+                     fs_cluster_work* d_works, fs_cluster* d_clusters, uint64_t cap,
+                     uint64_t* n_clusters);
+/* HIP-event milliseconds of the last fs_clusters / fs_clusters_rows call on this thread:
+ * coverage matrix, link pass, families (roots, sizes, numbering, member lists, the works),
+ * depth pass, merge pass; 0 for a pass that did not run.  tools/clusters_bench.py. */
+int fs_clusters_times(double* ms);
+
 /* `ao3.py groups`: the same records reduced by groups of works (a year, an author, a tag).
  * Records, passages and coverage as for fs_pairs.  Membership is many-to-many: work w is in the
  * groups mem_grp[mem_off[w] .. mem_off[w + 1]), strictly ascending (a work may be in none, a
