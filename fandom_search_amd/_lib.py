@@ -22,6 +22,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_host_alloc", "fs_host_free", "fs_rows_unpack", "fs_rows_unpack8",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
+           "fs_readings", "fs_readings_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
@@ -222,6 +223,12 @@ def load():
     L.fs_variants.restype = C.c_int
     L.fs_variants.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_readings.restype = C.c_int
+    L.fs_readings.argtypes = [C.c_int, u32p, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                              C.c_void_p, C.c_uint64, u64p, u64p, u64p]
+    L.fs_readings_times.restype = C.c_int
+    L.fs_readings_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_intern.restype = C.c_int
     L.fs_matches_intern.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint64, u64p]
     L.fs_matches_intern_times.restype = C.c_int

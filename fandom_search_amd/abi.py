@@ -165,6 +165,20 @@ VARIANT_WORD_DTYPE = np.dtype([("n_records", np.uint32), ("n_spellings", np.uint
                                ("n_works", np.uint32), ("first_cell", np.uint32)])
 assert VARIANT_WORD_DTYPE.itemsize == 16
 
+# fs_reading 40 bytes, fs_reading_span 24
+READING_DTYPE = np.dtype([("first", np.uint64), ("orig_first", np.uint32),
+                          ("orig_last", np.uint32), ("n_words", np.uint32),
+                          ("n_passages", np.uint32), ("n_works", np.uint32), ("span", np.uint32),
+                          ("rank", np.uint32), ("reserved", np.uint32)])
+assert READING_DTYPE.itemsize == 40
+READING_SPAN_DTYPE = np.dtype([("orig_first", np.uint32), ("orig_last", np.uint32),
+                               ("n_passages", np.uint32), ("n_works", np.uint32),
+                               ("n_readings", np.uint32), ("first_reading", np.uint32)])
+assert READING_SPAN_DTYPE.itemsize == 24
+FS_READINGS_MAX_BYTES = 1 << 30
+FS_READINGS_SLOT_BYTES = 64
+READINGS_MS_NAMES = ("passages", "tables", "spans", "readings", "copy_out", "total")
+
 # the match CSV reader (fs_matches_*): fs_match_ix 64 bytes, fs_match_defer 8, fs_matches_info 96
 FS_MATCH_FIELDS = 12
 FS_MATCHES_PARSED = 0

@@ -9,7 +9,8 @@ under each script word (fandom_search_amd/variants.py), and `pairs`, which ranks
 works by the script words both quote (fandom_search_amd/pairs.py), and `groups`, which reduces
 the reuse by year, author, language or tag of the works (fandom_search_amd/groups.py), and
 `clusters`, which gathers the works quoting the same lines into families
-(fandom_search_amd/clusters.py).  The
+(fandom_search_amd/clusters.py), and `readings`, which collates the wordings fans give each
+quoted stretch (fandom_search_amd/readings.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -30,7 +31,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -269,6 +270,34 @@ def build_parser():
                                  help='who reads the match csv: the GPU (default) or '
                                       'csv.reader; also FANDOM_SEARCH_READER')
     clusters_parser.set_defaults(func=_clusters)
+
+    readings_parser = subparsers.add_parser(
+        'readings', help='collates the wordings fans give each quoted stretch of the script: '
+                         'per span and reading (the fan words of a passage), how many passages '
+                         'and works')
+    readings_parser.add_argument('matches', action='store',
+                                 help='filename for search output (dated or batch file)')
+    readings_parser.add_argument('-o', '--output', action='store', default=None,
+                                 help='prefix of the two csv files, PREFIX-readings.csv and '
+                                      'PREFIX-readings-spans.csv (default: the input name '
+                                      'without .csv)')
+    readings_parser.add_argument('--min-words', default=6, type=int,
+                                 help='fewest matched words a passage has, default 6')
+    readings_parser.add_argument('--max-gap', default=0, type=int,
+                                 help='words without a record a passage may step over on each '
+                                      'side at once, default 0')
+    readings_parser.add_argument('--top', default=10, type=int,
+                                 help='readings listed per span, those of the most works '
+                                      'first; 0: all; default 10')
+    readings_parser.add_argument('--min-works', default=1, type=int,
+                                 help='fewest works a listed reading has, default 1')
+    readings_parser.add_argument('--fold-case', action='store_true',
+                                 help='fan words equal when lower-cased are one spelling')
+    readings_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    readings_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                 help='who reads the match csv: the GPU (default) or '
+                                      'csv.reader; also FANDOM_SEARCH_READER')
+    readings_parser.set_defaults(func=_readings)
     return parser
 
 
@@ -378,6 +407,17 @@ def _clusters(args):
         return clusters.process(args)
     except ValueError as e:
         sys.exit('ao3.py clusters: error: %s' % e)
+
+
+def _readings(args):
+    from . import readings
+    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0 or args.top < 0:
+        sys.exit('ao3.py readings: error: --min-words and --min-works must be at least 1, '
+                 '--max-gap and --top at least 0')
+    try:
+        return readings.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py readings: error: %s' % e)
 
 
 def main(argv=None):

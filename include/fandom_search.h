@@ -631,6 +631,67 @@ int fs_variants(int device, const uint32_t* work, const uint32_t* orig_ix, const
                 uint64_t n, uint32_t n_works, uint32_t n_script, uint32_t n_spell,
                 fs_variant_word* words, fs_variant_cell* cells, uint64_t cap, uint64_t* n_cells);
 
+/* `ao3.py readings`: the wordings fans give each quoted stretch.  Records are sorted by (work,
+ * fan_ix), as for fs_passages; each carries spell, a dense id < n_spell for its fan word
+ * (fs_matches_intern, or any dense numbering).  Passages are those of fs_passages under
+ * min_words and max_gap; a passage is a run of consecutive records.
+ *  - The reading of a passage with records r0..r(k-1) is the sequence (orig_ix[ri] -
+ *    orig_ix[r0], spell[ri]) for i = 0..k-1, together with orig_ix[r0].
+ *  - Two passages have the same reading exactly when these are equal.  Sequences are compared,
+ *    never hashes alone.
+ *  - Passages with the same reading therefore have the same span (orig_first, orig_last) and
+ *    the same length.
+ *  - With max_gap > 0, two passages over one span that bridge different words are different
+ *    readings.
+ * A work that repeats a reading ten times counts once in n_works and ten times in n_passages. */
+typedef struct fs_reading {
+  uint64_t first;            /* first record of its first passage (record order)        */
+  uint32_t orig_first, orig_last;
+  uint32_t n_words;          /* records in each of its passages                         */
+  uint32_t n_passages;       /* passages with this reading                              */
+  uint32_t n_works;          /* distinct works among them                               */
+  uint32_t span;             /* index into the spans output                             */
+  uint32_t rank;             /* 1.. within its span                                     */
+  uint32_t reserved;         /* 0                                                       */
+} fs_reading;                /* 40 bytes                                                */
+
+typedef struct fs_reading_span {
+  uint32_t orig_first, orig_last;
+  uint32_t n_passages, n_works;        /* over all its readings; works distinct         */
+  uint32_t n_readings, first_reading;  /* its readings are first_reading .. +n_readings */
+} fs_reading_span;           /* 24 bytes                                                */
+
+/* The device tables are open-addressing tables of S slots each, S the power of two that is at
+ * least twice the number of passages (and at least 64), FS_READINGS_SLOT_BYTES bytes per slot
+ * over all of them: S * FS_READINGS_SLOT_BYTES may be up to FS_READINGS_MAX_BYTES, which
+ * admits 2^23 passages. */
+#define FS_READINGS_SLOT_BYTES 64u
+#define FS_READINGS_MAX_BYTES (1u << 30)
+
+/* Host columns in; `cap_readings` readings and `cap_spans` spans out, on HIP device `device`.
+ * Spans are sorted by orig_first ascending, then orig_last ascending.  Readings are in span
+ * order; within a span they are sorted by n_works descending, then n_passages descending, then
+ * first ascending: a total order, which gives rank.  FS_E_INVALID for min_words == 0, records
+ * out of (work, fan_ix) order, a work >= n_works, an orig_ix >= n_script or a spell >= n_spell;
+ * FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or tables above
+ * FS_READINGS_MAX_BYTES; FS_E_CAPACITY when either cap is too small (all three counts are
+ * filled in then, the buffers untouched).  n_rows == 0: zeros, without device work.  The
+ * environment's FS_READINGS_HASH_BITS=k (a diagnostic, read once per call) keeps k bits of the
+ * sequence hash, so that at 0 every passage collides; the output is the same.  There is no
+ * _rows twin: fs_row carries no fan word, so records a search left on the device cannot feed
+ * this. */
+int fs_readings(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+                const uint32_t* spell, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                uint32_t n_spell, uint32_t min_words, uint32_t max_gap,
+                fs_reading* readings, uint64_t cap_readings,
+                fs_reading_span* spans, uint64_t cap_spans,
+                uint64_t* n_readings, uint64_t* n_spans, uint64_t* n_passages);
+/* HIP-event milliseconds of the last fs_readings call on this thread: passages (checks, run
+ * heads, kept runs), tables (hashes, inserts and counts), spans (their order and records),
+ * readings (their places and ranks), copy out, and the total of the five; 0 for a pass that
+ * did not run.  tools/readings_bench.py. */
+int fs_readings_times(double* ms);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
