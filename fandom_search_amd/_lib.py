@@ -23,6 +23,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_readings", "fs_readings_times",
+           "fs_retellings", "fs_retellings_rows", "fs_retellings_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
@@ -229,6 +230,14 @@ def load():
                               C.c_void_p, C.c_uint64, u64p, u64p, u64p]
     L.fs_readings_times.restype = C.c_int
     L.fs_readings_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_retellings.restype = C.c_int
+    L.fs_retellings.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_retellings_rows.restype = C.c_int
+    L.fs_retellings_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_retellings_times.restype = C.c_int
+    L.fs_retellings_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_intern.restype = C.c_int
     L.fs_matches_intern.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint64, u64p]
     L.fs_matches_intern_times.restype = C.c_int

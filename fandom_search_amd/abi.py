@@ -179,6 +179,22 @@ FS_READINGS_MAX_BYTES = 1 << 30
 FS_READINGS_SLOT_BYTES = 64
 READINGS_MS_NAMES = ("passages", "tables", "spans", "readings", "copy_out", "total")
 
+# fs_retelling 40 bytes, fs_retelling_passage 48
+RETELLING_DTYPE = np.dtype([("n_passages", np.uint32), ("passage_words", np.uint32),
+                            ("chain_passages", np.uint32), ("chain_words", np.uint32),
+                            ("chain_first", np.uint32), ("chain_last", np.uint32),
+                            ("orig_first", np.uint32), ("orig_last", np.uint32),
+                            ("chain_script_words", np.uint32), ("n_descents", np.uint32)])
+assert RETELLING_DTYPE.itemsize == 40
+RETELLING_PASSAGE_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32),
+                                    ("work", np.uint32), ("fan_first", np.uint32),
+                                    ("fan_last", np.uint32), ("orig_first", np.uint32),
+                                    ("orig_last", np.uint32), ("best", np.uint32),
+                                    ("prev", np.uint32), ("depth", np.uint32),
+                                    ("chain_pos", np.uint32)])
+assert RETELLING_PASSAGE_DTYPE.itemsize == 48
+RETELLINGS_MS_NAMES = ("passages", "bins", "chains", "trace", "write", "total")
+
 # the match CSV reader (fs_matches_*): fs_match_ix 64 bytes, fs_match_defer 8, fs_matches_info 96
 FS_MATCH_FIELDS = 12
 FS_MATCHES_PARSED = 0

@@ -10,7 +10,8 @@ works by the script words both quote (fandom_search_amd/pairs.py), and `groups`,
 the reuse by year, author, language or tag of the works (fandom_search_amd/groups.py), and
 `clusters`, which gathers the works quoting the same lines into families
 (fandom_search_amd/clusters.py), and `readings`, which collates the wordings fans give each
-quoted stretch (fandom_search_amd/readings.py).  The
+quoted stretch (fandom_search_amd/readings.py), and `retellings`, which lists the works that
+quote the script in the script's own order (fandom_search_amd/retellings.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -31,7 +32,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -298,6 +299,34 @@ def build_parser():
                                  help='who reads the match csv: the GPU (default) or '
                                       'csv.reader; also FANDOM_SEARCH_READER')
     readings_parser.set_defaults(func=_readings)
+
+    retellings_parser = subparsers.add_parser(
+        'retellings', help='lists the fan works that quote the script in its order: per work '
+                           'the heaviest chain of passages that advance through the script as '
+                           'they advance through the work, and every passage with its place '
+                           'in the chain')
+    retellings_parser.add_argument('matches', action='store',
+                                   help='filename for search output (dated or batch file)')
+    retellings_parser.add_argument('-o', '--output', action='store', default=None,
+                                   help='prefix of the two csv files, PREFIX-retellings.csv and '
+                                        'PREFIX-retellings-passages.csv (default: the input name '
+                                        'without .csv)')
+    retellings_parser.add_argument('--min-words', default=6, type=int,
+                                   help='fewest matched words a passage has, default 6')
+    retellings_parser.add_argument('--max-gap', default=0, type=int,
+                                   help='words without a record a passage may step over on each '
+                                        'side at once, default 0')
+    retellings_parser.add_argument('--min-passages', default=2, type=int,
+                                   help='fewest passages in the chain of a listed work, '
+                                        'default 2')
+    retellings_parser.add_argument('--min-share', default=0, type=int,
+                                   help='fewest passage words of a listed work that lie in its '
+                                        'chain, as a whole percentage, 0 to 100, default 0')
+    retellings_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    retellings_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                   help='who reads the match csv: the GPU (default) or '
+                                        'csv.reader; also FANDOM_SEARCH_READER')
+    retellings_parser.set_defaults(func=_retellings)
     return parser
 
 
@@ -418,6 +447,19 @@ def _readings(args):
         return readings.process(args)
     except ValueError as e:
         sys.exit('ao3.py readings: error: %s' % e)
+
+
+def _retellings(args):
+    from . import retellings
+    if args.min_words < 1 or args.min_passages < 1 or args.max_gap < 0:
+        sys.exit('ao3.py retellings: error: --min-words and --min-passages must be at least 1, '
+                 '--max-gap at least 0')
+    if not 0 <= args.min_share <= 100:
+        sys.exit('ao3.py retellings: error: --min-share must be from 0 to 100')
+    try:
+        return retellings.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py retellings: error: %s' % e)
 
 
 def main(argv=None):

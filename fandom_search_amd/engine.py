@@ -607,6 +607,49 @@ class ScriptIndex(object):
                     found[:n.value * abi.CLUSTER_DTYPE.itemsize].cpu().numpy()
                     .view(abi.CLUSTER_DTYPE))
 
+    def retellings_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, out_ptrs=None,
+                          cap=None):
+        """`retellings` over device-resident fs_row records sorted by (work, fan_ix) (after a
+        search or a gather; fs_retellings_rows): per work its chain, and every passage with its
+        best, prev, depth and place in the chain.  Without `out_ptrs`:
+        (abi.RETELLING_DTYPE[n_works], abi.RETELLING_PASSAGE_DTYPE[n_passages]) on the host.
+        With `out_ptrs` = device addresses (works; passages, a buffer of `cap` of them): the
+        number of passages; FsError(FS_E_CAPACITY) with .required when that buffer is too small
+        (the works are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+
+        def call(works, found, cap):
+            return L.fs_retellings_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                        int(min_words), int(max_gap), C.c_void_p(works),
+                                        C.c_void_p(found), int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_retellings_rows", "passage buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_retellings_rows")
+            return int(n.value)
+        import torch
+        works = torch.empty(max(1, int(n_works)) * abi.RETELLING_DTYPE.itemsize,
+                            dtype=torch.uint8, device="cuda")
+        cap = int(n_rows) // max(1, int(min_words)) if cap is None else int(cap)
+        while True:
+            found = torch.empty(max(1, cap) * abi.RETELLING_PASSAGE_DTYPE.itemsize,
+                                dtype=torch.uint8, device="cuda")
+            torch_ready()
+            rc = call(works.data_ptr(), found.data_ptr(), cap)
+            if rc == abi.FS_E_CAPACITY:
+                cap = int(n.value)
+                continue
+            _lib.check(rc, "fs_retellings_rows")
+            return (works[:int(n_works) * abi.RETELLING_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.RETELLING_DTYPE),
+                    found[:n.value * abi.RETELLING_PASSAGE_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.RETELLING_PASSAGE_DTYPE))
+
     def groups_device(self, rows_ptr, n_rows, n_works, mem_off, mem_grp, n_groups, label_of=None,
                       n_labels=0, min_words=6, max_gap=0, min_works=1, out_ptrs=None, caps=None):
         """`groups` over device-resident fs_row records sorted by (work, fan_ix) (after a search

@@ -692,6 +692,69 @@ int fs_readings(int device, const uint32_t* work, const uint32_t* fan_ix, const 
  * did not run.  tools/readings_bench.py. */
 int fs_readings_times(double* ms);
 
+/* `ao3.py retellings`: works that quote the script in its order.  Records and passages as for
+ * fs_passages; inside a work the passages are numbered in record order, and passage k has
+ * n_words (its records), fan_first / fan_last and orig_first / orig_last (the fan and the
+ * script index of its first and last record).
+ *  - Passage i may follow passage j of the same work when j comes before i in record order and
+ *    orig_first(i) > orig_last(j): touching at one script word is not following,
+ *    orig_last(j) + 1 is.  A chain is a sequence of passages each following the one before; its
+ *    weight is the sum of its passages' n_words.
+ *  - best(i) = n_words(i) + max(0, max over the j that i may follow of best(j)).
+ *  - prev(i) is the j at that maximum, the smallest j on a tie; none when no j qualifies.
+ *  - depth(i) = 1 + depth(prev(i)), or 1 without a prev.
+ *  - The work's chain ends at the passage with the largest best, the smallest i on a tie, and
+ *    is read back through prev.
+ *  - A work's descents are the pairs of consecutive passages (k, k + 1) with
+ *    orig_first(k + 1) <= orig_last(k); for a work with a passage, n_descents == 0 exactly when
+ *    the chain holds all its passages.
+ * Every output is an integer below 2^32 (best never exceeds the number of records), and the
+ * candidates j are compared as (best(j), ~j), a total order: no schedule changes the result. */
+typedef struct fs_retelling {          /* one per work; zeros and 0xFFFFFFFF for a work without a passage */
+  uint32_t n_passages, passage_words;  /* as fs_work                                              */
+  uint32_t chain_passages, chain_words;
+  uint32_t chain_first, chain_last;    /* numbers (in the passage list) of the chain's ends; 0xFFFFFFFF: none */
+  uint32_t orig_first, orig_last;      /* orig_first of the chain's first passage, orig_last of its last; 0 without a chain */
+  uint32_t chain_script_words;         /* sum of (orig_last - orig_first + 1) over the chain's passages */
+  uint32_t n_descents;
+} fs_retelling;                        /* 40 bytes                                                */
+
+typedef struct fs_retelling_passage {  /* one per passage of the whole input, in record order     */
+  uint64_t first;                      /* index of its first record                               */
+  uint32_t n_words, work;
+  uint32_t fan_first, fan_last, orig_first, orig_last;
+  uint32_t best, prev;                 /* prev: a number in this list, 0xFFFFFFFF: none           */
+  uint32_t depth;
+  uint32_t chain_pos;                  /* 1-based place in its work's chain, 0 when not in it     */
+} fs_retelling_passage;                /* 48 bytes                                                */
+
+/* Host columns in; out[n_works] and `cap` passages out, on HIP device `device`.  Both entry
+ * points: FS_E_INVALID for null arguments, min_words == 0, records out of (work, fan_ix) order
+ * or a work >= n_works; FS_E_UNSUPPORTED for n_rows >= 2^32; FS_E_CAPACITY with *n_passages =
+ * passages required when cap is smaller (out is complete then, passages untouched).
+ * n_rows == 0: summaries without a passage, *n_passages = 0 (fs_retellings: without device
+ * work).  Any number of passages per work is taken; device memory is a few words per record.
+ * The works are handled by passage count: up to FS_RETELLINGS_SMALL (default 8) a lane each,
+ * up to FS_RETELLINGS_LDS (default and most 4096) a wave each with its arrays in LDS, beyond
+ * that a wave each over global memory.  Both are diagnostics of the environment, read on each
+ * call (0: no work takes the class); the output is the same wherever they stand. */
+int fs_retellings(int device, const uint32_t* work, const uint32_t* fan_ix,
+                  const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t min_words,
+                  uint32_t max_gap, fs_retelling* out, fs_retelling_passage* passages,
+                  uint64_t cap, uint64_t* n_passages);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (d_out
+ * 4-byte, d_passages 8-byte aligned), on the index's device and stream; returns when they are
+ * written. */
+int fs_retellings_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                       uint32_t min_words, uint32_t max_gap, fs_retelling* d_out,
+                       fs_retelling_passage* d_passages, uint64_t cap, uint64_t* n_passages);
+/* HIP-event milliseconds of the last fs_retellings / fs_retellings_rows call on this thread:
+ * passages (checks, run heads, kept runs, per-work offsets), bins (the works by class), chains
+ * (the recurrence, all classes), trace (the walk back and the per-work records), write (the
+ * passage records), and the total of the five; 0 for a pass that did not run.
+ * tools/retellings_bench.py. */
+int fs_retellings_times(double* ms);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
