@@ -25,6 +25,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_readings", "fs_readings_times",
            "fs_retellings", "fs_retellings_rows", "fs_retellings_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
+           "fs_companions", "fs_companions_rows", "fs_companions_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
@@ -190,6 +191,16 @@ def load():
                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_pairs_times.restype = C.c_int
     L.fs_pairs_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_companions.restype = C.c_int
+    L.fs_companions.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_companions_rows.restype = C.c_int
+    L.fs_companions_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_companions_times.restype = C.c_int
+    L.fs_companions_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_clusters.restype = C.c_int
     L.fs_clusters.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -125,6 +125,18 @@ PAIR_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("shared", np.uint32)
 assert PAIR_DTYPE.itemsize == 32
 FS_PAIRS_MAX_BYTES = 1 << 30
 
+# fs_companion_unit: 16 bytes; fs_companion: 32 bytes
+COMPANION_UNIT_DTYPE = np.dtype([("works", np.uint32), ("partners", np.uint32),
+                                 ("best", np.uint32), ("best_both", np.uint32)])
+assert COMPANION_UNIT_DTYPE.itemsize == 16
+COMPANION_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("both", np.uint32),
+                            ("works_a", np.uint32), ("works_b", np.uint32),
+                            ("first_work", np.uint32), ("last_work", np.uint32),
+                            ("reserved", np.uint32)])
+assert COMPANION_DTYPE.itemsize == 32
+FS_COMPANIONS_MAX_BYTES = 1 << 30
+COMPANIONS_MS_NAMES = ("incidence", "count", "place", "detail")
+
 # fs_cluster_work: 32 bytes; fs_cluster: 48 bytes
 CLUSTER_WORK_DTYPE = np.dtype([("covered", np.uint32), ("root", np.uint32), ("size", np.uint32),
                                ("cluster", np.uint32), ("links", np.uint32), ("best", np.uint32),

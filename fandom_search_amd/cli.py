@@ -11,7 +11,9 @@ the reuse by year, author, language or tag of the works (fandom_search_amd/group
 `clusters`, which gathers the works quoting the same lines into families
 (fandom_search_amd/clusters.py), and `readings`, which collates the wordings fans give each
 quoted stretch (fandom_search_amd/readings.py), and `retellings`, which lists the works that
-quote the script in the script's own order (fandom_search_amd/retellings.py).  The
+quote the script in the script's own order (fandom_search_amd/retellings.py), and `companions`,
+which relates the quoted stretches of the script by the works quoting both
+(fandom_search_amd/companions.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -32,7 +34,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings, companions or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -327,6 +329,40 @@ def build_parser():
                                    help='who reads the match csv: the GPU (default) or '
                                         'csv.reader; also FANDOM_SEARCH_READER')
     retellings_parser.set_defaults(func=_retellings)
+
+    companions_parser = subparsers.add_parser(
+        'companions', help='relates the quoted stretches of the script to each other: per pair '
+                           'of quoted regions, scenes or characters the fan works that quote '
+                           'both, per unit its closest companion')
+    companions_parser.add_argument('matches', action='store',
+                                   help='filename for search output (dated or batch file)')
+    companions_parser.add_argument('-o', '--output', action='store', default=None,
+                                   help='prefix of the two csv files, PREFIX-companions.csv and '
+                                        'PREFIX-companions-units.csv (default: the input name '
+                                        'without .csv)')
+    companions_parser.add_argument('--by', default='region',
+                                   choices=('region', 'scene', 'character'),
+                                   help='the units: the quoted regions of `quotes` (default), '
+                                        'the scenes or the characters of the script')
+    companions_parser.add_argument('--min-words', default=6, type=int,
+                                   help='fewest matched words a passage has, default 6')
+    companions_parser.add_argument('--max-gap', default=0, type=int,
+                                   help='words without a record a passage may step over on each '
+                                        'side at once, default 0')
+    companions_parser.add_argument('--min-works', default=1, type=int,
+                                   help='with --by region: fewest different works whose passages '
+                                        'cover every word of a region, default 1')
+    companions_parser.add_argument('--min-both', default=2, type=int,
+                                   help='fewest works quoting both units of a listed pair, '
+                                        'default 2')
+    companions_parser.add_argument('--min-share', default=0, type=int,
+                                   help='fewest works quoting both units as a whole percentage '
+                                        'of the works of the less quoted one, 0 to 100, default 0')
+    companions_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    companions_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                   help='who reads the match csv: the GPU (default) or '
+                                        'csv.reader; also FANDOM_SEARCH_READER')
+    companions_parser.set_defaults(func=_companions)
     return parser
 
 
@@ -460,6 +496,19 @@ def _retellings(args):
         return retellings.process(args)
     except ValueError as e:
         sys.exit('ao3.py retellings: error: %s' % e)
+
+
+def _companions(args):
+    from . import companions
+    if args.min_words < 1 or args.min_works < 1 or args.min_both < 1 or args.max_gap < 0:
+        sys.exit('ao3.py companions: error: --min-words, --min-works and --min-both must be at '
+                 'least 1, --max-gap at least 0')
+    if not 0 <= args.min_share <= 100:
+        sys.exit('ao3.py companions: error: --min-share must be from 0 to 100')
+    try:
+        return companions.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py companions: error: %s' % e)
 
 
 def main(argv=None):

@@ -755,6 +755,64 @@ int fs_retellings_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint
  * tools/retellings_bench.py. */
 int fs_retellings_times(double* ms);
 
+/* `ao3.py companions`: stretches of the script related by the fan works that quote both, the
+ * transpose of fs_pairs.  Records, passages, active works (works with a passage; N of them) and
+ * the coverage C_w as for fs_pairs.  unit_of[n_script] gives every script word a unit number
+ * below n_units, or 0xFFFFFFFF for none; a unit may hold any set of script words.  Work w quotes
+ * unit u when C_w holds a word o with unit_of[o] == u (a bridged word counts); M_u is the set of
+ * active works quoting u and works(u) = |M_u|.  For units a < b, both = |M_a & M_b|; the pair is
+ * kept when both >= min_both and both * 100 >= min_share * min(works(a), works(b)) (the product
+ * in 64 bits; min_share a whole percentage, 0..100; exactly at the bound is kept).  Every output
+ * is an integer. */
+typedef struct fs_companion_unit {
+  uint32_t works;            /* |M_u|; 0 for a unit nobody quotes                        */
+  uint32_t partners;         /* kept pairs the unit is in                               */
+  uint32_t best;             /* the partner with the largest both, the smaller unit
+                                number on a tie; 0xFFFFFFFF without partners            */
+  uint32_t best_both;        /* its both; 0 without partners                            */
+} fs_companion_unit;         /* 16 bytes                                                */
+
+typedef struct fs_companion {
+  uint32_t a, b;             /* unit numbers, a < b                                     */
+  uint32_t both;             /* active works quoting both                               */
+  uint32_t works_a, works_b; /* works(a), works(b)                                      */
+  uint32_t first_work;       /* smallest and largest work number (not active number)    */
+  uint32_t last_work;        /* among them                                              */
+  uint32_t reserved;         /* 0                                                       */
+} fs_companion;              /* 32 bytes                                                */
+
+/* The incidence matrix is a row of ceil(N / 64) 64-bit words per unit, the units padded to a
+ * multiple of 64: ceil(n_units / 64) * 64 * ceil(N / 64) * 8 bytes may be up to this.  The
+ * coverage matrix of fs_pairs is not built. */
+#define FS_COMPANIONS_MAX_BYTES (1u << 30)
+
+/* Host columns and the host unit map in; units[n_units] and `cap` pairs out, on HIP device
+ * `device`.  The pairs come in (a, b) ascending order.  Both entry points: FS_E_INVALID for
+ * min_words == 0, min_both == 0, min_share > 100, records out of (work, fan_ix) order, a work >=
+ * n_works, an orig_ix >= n_script or a unit_of entry that is neither below n_units nor
+ * 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or an
+ * incidence matrix above FS_COMPANIONS_MAX_BYTES; FS_E_CAPACITY with *n_pairs = pairs required
+ * when cap is smaller (units is complete then, pairs untouched).  n_rows == 0 or n_units == 0:
+ * units of no works with best 0xFFFFFFFF, *n_pairs = 0 (fs_companions: without device work, the
+ * unit map unread). */
+int fs_companions(int device, const uint32_t* work, const uint32_t* fan_ix,
+                  const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                  const uint32_t* unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+                  uint32_t min_both, uint32_t min_share, fs_companion_unit* units,
+                  fs_companion* pairs, uint64_t cap, uint64_t* n_pairs);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (16-byte aligned), on the index's device
+ * and stream; returns when they are written. */
+int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                       const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                       uint32_t max_gap, uint32_t min_both, uint32_t min_share,
+                       fs_companion_unit* d_units, fs_companion* d_pairs, uint64_t cap,
+                       uint64_t* n_pairs);
+/* HIP-event milliseconds of the last fs_companions / fs_companions_rows call on this thread:
+ * incidence matrix (with the row popcounts), count pass (with its scan and the per-unit
+ * results), place pass, detail pass; 0 for a pass that did not run.  tools/companions_bench.py. */
+int fs_companions_times(double* ms);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
