@@ -338,7 +338,7 @@ struct ClustersJob {
   DBuf<uint32_t> links, parent, root, size, listed, num, members, fam_root, fam_size, fam_off,
       fam_cur, fam_cnt;
   DBuf<unsigned long long> best, linksum, hub, fam_peak, mask;
-  PassClock clk;
+  Clock<8> clk;
   ClusterArgs a{};
 
   // d_works written, a.n_listed set (all on `s`, finished on return)

@@ -241,7 +241,7 @@ struct CompJob {
   CoverJob cj;
   DBuf<uint32_t> work_of, uworks, partners, cnt, any, bad;
   DBuf<unsigned long long> mat, best, off, total;
-  PassClock clk;
+  Clock<8> clk;
   CompArgs a{};
   uint64_t n_pairs = 0;
   uint32_t bad_units = 0;

@@ -32,32 +32,25 @@
 // it are shuffles.
 #include "fs_internal.h"
 #include "fs_cover.h"
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kPlanes = 8;
 constexpr uint32_t kSplit = 255;            // works per unit: what kPlanes bits count (tests: SPLIT)
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kGroupWords = sizeof(fs_group) / 4;
 enum { G_WORKS, G_PWORKS, G_WORDS, G_EXACT, G_PASSAGES, G_PASSAGE_WORDS, G_LONGEST, G_COVERED,
        G_PEAK, G_PEAK_FIRST, G_TOP, G_TOP_WORDS, G_CELLS, G_ROWS };
 constexpr uint32_t kWorkStats = 5;          // records, exact, passages, records in them, longest
 
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-  __device__ bool exact(uint64_t i) const { return rows[i].comb <= 0.0; }
+// the exact flag of a record: from its distance, or the column the caller passed with the others
+struct ExactCols : ColsSrc {
+  const uint8_t* ex;
 };
 
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  const uint8_t* ex;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-  __device__ bool exact(uint64_t i) const { return ex[i] != 0; }
-};
+__device__ inline bool exact_of(const RowsSrc& src, uint64_t i) { return src.comb(i) <= 0.0; }
+__device__ inline bool exact_of(const ExactCols& src, uint64_t i) { return src.ex[i] != 0; }
 
 struct GroupsArgs {
   uint32_t n, n_works, n_script, nk, n_groups, n_labels, n_runs, min_words, min_works;
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_groups_records(Src src, GroupsArgs a
     if (k.x >= a.n_works || k.z >= a.n_script) valid = false;
   }
   if (__ballot(i < a.n && !valid) && lane == 0) atomicOr(&a.status[0], 1u);
-  if (valid) ex = src.exact(i);
+  if (valid) ex = exact_of(src, i);
   int first;
   unsigned long long kf;
   for (uint64_t todo = __ballot(valid); todo;) {
@@ -191,12 +184,7 @@ __global__ __launch_bounds__(kBlock) void k_groups_runs(Src src, GroupsArgs a) {
   for (uint64_t todo = __ballot(keep); todo;) {
     const uint64_t m = same_key(todo, keep, w, &first, &kf);
     const bool mine = (m >> lane) & 1;
-    uint32_t sum = mine ? len : 0u, top = sum;
-    for (uint32_t d = 32; d; d >>= 1) {
-      sum += __shfl_xor(sum, d);
-      const uint32_t y = __shfl_xor(top, d);
-      top = y > top ? y : top;
-    }
+    const uint32_t sum = wave_sum(mine ? len : 0u), top = wave_max(mine ? len : 0u);
     if ((int)lane == first) {
       uint32_t* s = a.wstat + (size_t)kf * kWorkStats;
       atomicAdd(&s[2], (uint32_t)__popcll(m));
@@ -452,34 +440,7 @@ __global__ __launch_bounds__(kBlock) void k_groups_finish(GroupsArgs a) {
 __global__ __launch_bounds__(kScanBlock) void k_groups_scan(const uint32_t* groups, uint32_t field,
                                                             uint32_t nb, unsigned long long* out,
                                                             unsigned long long* total) {
-  __shared__ unsigned long long s_w[kScanBlock / 64];
-  __shared__ unsigned long long s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const unsigned long long x = j < nb ? groups[j * kGroupWords + field] : 0ull;
-    unsigned long long inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const unsigned long long y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const unsigned long long t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const unsigned long long carry = s_carry;
-    if (j < nb) out[j] = carry + pre + inc - x;
-    __syncthreads();                       // s_w and s_carry read by every wave
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
+  scan_array<unsigned long long, unsigned long long, kGroupWords>(groups + field, nb, out, total);
 }
 
 thread_local double t_ms[4];    // per-work tables, reduction by group, offsets, place pass
@@ -823,7 +784,7 @@ extern "C" int fs_groups(int device, const uint32_t* work, const uint32_t* fan_i
   FS_TRY(d_orig.upload(orig_ix, n, nullptr));
   FS_TRY(d_exact.upload(exact, n, nullptr));
   FS_TRY(d_groups.reserve(n_groups));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, d_exact.p};
+  const ExactCols src{{d_work.p, d_fan.p, d_orig.p}, d_exact.p};
   GroupsJob job;
   FS_TRY(job.count(src, nullptr, src, plan, n, n_works, n_script, n_groups, label_of, n_labels,
                    min_words, max_gap, min_works, d_groups.p, nullptr));

@@ -27,15 +27,13 @@
 #include "fs_internal.h"
 #include "fs_dec.h"
 #include "fs_probe.h"
-
-#include <stdlib.h>
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kChunk = 64;                 // bytes per lane: one word of the row-start mask
 constexpr uint32_t kTile = kBlock * kChunk;     // bytes per workgroup
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kFields = FS_MATCH_FIELDS;
 constexpr uint32_t kPad = 128;                  // zero bytes behind the file on the device
 constexpr uint32_t kStage = 8192;               // LDS bytes a wave stages its 64 rows in
@@ -237,36 +235,10 @@ __global__ __launch_bounds__(kBlock) void k_mt_parity(const uint8_t* __restrict_
 }
 
 // exclusive scan of v[0..nb) in place, *total = sum (one workgroup, chunks of 1024 in turn)
-__global__ __launch_bounds__(kScanBlock) void k_mt_scan(uint32_t* __restrict__ v, uint32_t nb,
+// (the 32-bit prefixes are used only when the total fits)
+__global__ __launch_bounds__(kScanBlock) void k_mt_scan(uint32_t* v, uint32_t nb,
                                                         uint64_t* __restrict__ total) {
-  __shared__ uint32_t s_w[kScanBlock / 64];
-  __shared__ uint64_t s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const uint32_t x = j < nb ? v[j] : 0u;
-    uint32_t inc = x;
-    for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-      const uint32_t y = __shfl_up(inc, dd);
-      if (lane >= dd) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const uint64_t carry = s_carry;
-    if (j < nb) v[j] = (uint32_t)carry + pre + inc - x;   // (used only when the total fits)
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
+  scan_array<uint32_t, uint64_t>(v, nb, v, total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mt_classify(const uint8_t* __restrict__ d, uint64_t n,
@@ -343,11 +315,7 @@ __global__ __launch_bounds__(kBlock) void k_mt_place(const uint64_t* __restrict_
   const uint64_t word = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   uint64_t m = word < n_words ? mask[word] : 0;
   const uint32_t c = (uint32_t)__popcll(m);
-  uint32_t inc = c;
-  for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-    const uint32_t y = __shfl_up(inc, dd);
-    if (lane >= dd) inc += y;
-  }
+  const uint32_t inc = wave_scan(c);
   if (lane == 63) s_w[wave] = inc;
   __syncthreads();
   uint64_t pos = (uint64_t)off[blockIdx.x] + inc - c;
@@ -523,19 +491,9 @@ __global__ __launch_bounds__(kBlock) void k_in_insert(InternArgs a) {
 // their number in *total
 __device__ inline bool intern_head(const InternArgs& a, uint32_t* rank, uint32_t* total) {
   __shared__ uint32_t s_w[kBlock / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   const bool head = r < a.n && a.first[a.slot_of[r]] == r;
-  const uint64_t b = __ballot(head);
-  if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t pre = (uint32_t)__popcll(b & ((1ull << lane) - 1)), tot = 0;
-  for (uint32_t w = 0; w < kBlock / 64; ++w) {
-    if (w < wave) pre += s_w[w];
-    tot += s_w[w];
-  }
-  *rank = pre;
-  *total = tot;
+  block_rank<kBlock>(head, s_w, rank, total);
   return head;
 }
 
@@ -604,12 +562,7 @@ namespace {
 
 int matches_run(fs_matches* m, const uint8_t* bytes, uint64_t n) {
   fs_matches_info& info = m->info;
-  hipEvent_t ev[7];
-  for (auto& e : ev) FS_HIP(hipEventCreate(&e));
-  struct Drop {
-    hipEvent_t* ev;
-    ~Drop() { for (int k = 0; k < 7; ++k) (void)hipEventDestroy(ev[k]); }
-  } drop{ev};
+  Clock<7> clk;
   const uint32_t nb = tiles(n);
   const uint64_t n_words = (n + kChunk - 1) / kChunk;
   FS_TRY(m->bytes.reserve(n + kPad));
@@ -618,17 +571,17 @@ int matches_run(fs_matches* m, const uint8_t* bytes, uint64_t n) {
   FS_TRY(m->mask.reserve(n_words));
   FS_TRY(m->status.reserve(kStWords));
   FS_TRY(m->total.reserve(2));
-  FS_HIP(hipEventRecord(ev[0], nullptr));
+  FS_TRY(clk.mark(0, nullptr));
   FS_HIP(hipMemcpyAsync(m->bytes.p, bytes, n, hipMemcpyHostToDevice, nullptr));
   FS_HIP(hipMemsetAsync(m->bytes.p + n, 0, kPad, nullptr));
   FS_HIP(hipMemsetAsync(m->status.p, 0, kStWords * sizeof(uint32_t), nullptr));
-  FS_HIP(hipEventRecord(ev[1], nullptr));
+  FS_TRY(clk.mark(1, nullptr));
   hipLaunchKernelGGL(k_mt_parity, dim3(nb), dim3(kBlock), 0, nullptr, m->bytes.p, n, m->par.p);
   hipLaunchKernelGGL(k_mt_scan, dim3(1), dim3(kScanBlock), 0, nullptr, m->par.p, nb, m->total.p);
-  FS_HIP(hipEventRecord(ev[2], nullptr));
+  FS_TRY(clk.mark(2, nullptr));
   hipLaunchKernelGGL(k_mt_classify, dim3(nb), dim3(kBlock), 0, nullptr, m->bytes.p, n, m->par.p,
                      m->mask.p, m->cnt.p, m->status.p);
-  FS_HIP(hipEventRecord(ev[3], nullptr));
+  FS_TRY(clk.mark(3, nullptr));
   hipLaunchKernelGGL(k_mt_scan, dim3(1), dim3(kScanBlock), 0, nullptr, m->cnt.p, nb,
                      m->total.p + 1);
   FS_HIP(hipGetLastError());
@@ -638,11 +591,8 @@ int matches_run(fs_matches* m, const uint8_t* bytes, uint64_t n) {
   FS_HIP(hipMemcpyAsync(total, m->total.p, sizeof total, hipMemcpyDeviceToHost, nullptr));
   FS_HIP(hipStreamSynchronize(nullptr));
   const auto timings = [&](int last) {
-    float t;
-    double* ms = info.ms;
-    for (int k = 0; k < last; ++k)
-      if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess) ms[k] = t;
-    if (hipEventElapsedTime(&t, ev[0], ev[last]) == hipSuccess) ms[6] = t;
+    for (int k = 0; k < last; ++k) info.ms[k] = clk.elapsed(k, k + 1);
+    info.ms[6] = clk.elapsed(0, last);
   };
   if (st[kStBad]) {
     info.status = FS_MATCHES_OUTSIDE;
@@ -658,7 +608,7 @@ int matches_run(fs_matches* m, const uint8_t* bytes, uint64_t n) {
   FS_TRY(m->row_start.reserve(n_all));
   hipLaunchKernelGGL(k_mt_place, dim3(nb), dim3(kBlock), 0, nullptr, m->mask.p, n_words, m->cnt.p,
                      m->row_start.p);
-  FS_HIP(hipEventRecord(ev[4], nullptr));
+  FS_TRY(clk.mark(4, nullptr));
   uint64_t start0 = 0;
   FS_HIP(hipMemcpy(&start0, m->row_start.p, sizeof start0, hipMemcpyDeviceToHost));
   info.has_header = is_header(bytes, n, start0) ? 1u : 0u;
@@ -683,12 +633,12 @@ int matches_run(fs_matches* m, const uint8_t* bytes, uint64_t n) {
                    m->fan.p, m->orig.p, m->lev.p, m->dist.p, m->comb.p, m->ix.p, m->defer.p,
                    m->defer_cap, m->status.p};
   const dim3 grid((uint32_t)((n_rows + kBlock - 1) / kBlock));
-  FS_HIP(hipEventRecord(ev[5], nullptr));
+  FS_TRY(clk.mark(5, nullptr));
   if (staged_default())
     hipLaunchKernelGGL(k_mt_rows<true>, grid, dim3(kBlock), 0, nullptr, a);
   else
     hipLaunchKernelGGL(k_mt_rows<false>, grid, dim3(kBlock), 0, nullptr, a);
-  FS_HIP(hipEventRecord(ev[6], nullptr));
+  FS_TRY(clk.mark(6, nullptr));
   FS_HIP(hipGetLastError());
   FS_HIP(hipMemcpy(st, m->status.p, sizeof st, hipMemcpyDeviceToHost));
   timings(6);
@@ -838,15 +788,10 @@ extern "C" int fs_matches_intern(fs_matches* m, uint32_t column, uint32_t* id, u
     return FS_E_INVALID;
   }
   FS_ENTER(m->device);
-  hipEvent_t ev[5];
-  for (auto& e : ev) FS_HIP(hipEventCreate(&e));
-  struct Drop {
-    hipEvent_t* ev;
-    ~Drop() { for (int k = 0; k < 5; ++k) (void)hipEventDestroy(ev[k]); }
-  } drop{ev};
+  Clock<5> clk;
   uint64_t slots = fs_probe_slots(n);
   if (slots > (1ull << 32)) slots = 1ull << 32;              // (slot numbers are 32 bits)
-  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  const uint32_t blocks = blocks_of(n, kBlock);
   FS_TRY(m->in_slots.reserve(slots));
   FS_TRY(m->in_first.reserve(slots));
   FS_TRY(m->in_slot_id.reserve(slots));
@@ -866,12 +811,12 @@ extern "C" int fs_matches_intern(fs_matches* m, uint32_t column, uint32_t* id, u
   a.slot_id = m->in_slot_id.p;
   a.cnt = m->in_cnt.p;
   a.id = m->in_id.p;
-  FS_HIP(hipEventRecord(ev[0], nullptr));
+  FS_TRY(clk.mark(0, nullptr));
   FS_HIP(hipMemsetAsync(a.slots, 0xFF, slots * sizeof(unsigned long long), nullptr));
   FS_HIP(hipMemsetAsync(a.first, 0xFF, slots * sizeof(uint32_t), nullptr));
-  FS_HIP(hipEventRecord(ev[1], nullptr));
+  FS_TRY(clk.mark(1, nullptr));
   hipLaunchKernelGGL(k_in_insert, dim3(blocks), dim3(kBlock), 0, nullptr, a);
-  FS_HIP(hipEventRecord(ev[2], nullptr));
+  FS_TRY(clk.mark(2, nullptr));
   hipLaunchKernelGGL(k_in_count, dim3(blocks), dim3(kBlock), 0, nullptr, a);
   hipLaunchKernelGGL(k_mt_scan, dim3(1), dim3(kScanBlock), 0, nullptr, a.cnt, blocks, m->total.p);
   FS_HIP(hipGetLastError());
@@ -881,17 +826,15 @@ extern "C" int fs_matches_intern(fs_matches* m, uint32_t column, uint32_t* id, u
   a.list = m->in_list.p;
   hipLaunchKernelGGL(k_in_number, dim3(blocks), dim3(kBlock), 0, nullptr, a);
   hipLaunchKernelGGL(k_in_ids, dim3(blocks), dim3(kBlock), 0, nullptr, a);
-  FS_HIP(hipEventRecord(ev[3], nullptr));
+  FS_TRY(clk.mark(3, nullptr));
   FS_HIP(hipGetLastError());
   FS_HIP(hipMemcpyAsync(id, a.id, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
   if (total <= cap)
     FS_HIP(hipMemcpyAsync(first, a.list, total * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
-  FS_HIP(hipEventRecord(ev[4], nullptr));
+  FS_TRY(clk.mark(4, nullptr));
   FS_HIP(hipStreamSynchronize(nullptr));
-  float t;
-  for (int k = 0; k < 4; ++k)
-    if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess) m->in_ms[k] = t;
-  if (hipEventElapsedTime(&t, ev[0], ev[4]) == hipSuccess) m->in_ms[4] = t;
+  for (int k = 0; k < 4; ++k) m->in_ms[k] = clk.elapsed(k, k + 1);
+  m->in_ms[4] = clk.elapsed(0, 4);
   *n_distinct = total;
   if (total > cap) {
     fs_set_error("%llu spellings need room", (unsigned long long)total);

@@ -197,7 +197,7 @@ struct PairsJob {
   CoverJob cj;
   DBuf<uint32_t> partners, cnt, any;
   DBuf<unsigned long long> best, off, total;
-  PassClock clk;
+  Clock<8> clk;
   PairsArgs a{};
   uint64_t n_pairs = 0;
 

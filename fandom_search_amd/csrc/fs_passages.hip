@@ -13,32 +13,14 @@
 // Sums are walked in record order by one lane (or, for a long run, by the whole wave in
 // lock-step, every lane adding the same values in the same order).
 #include "fs_internal.h"
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kItems = 16;
 constexpr uint32_t kTile = kBlock * kItems;     // records (runs) per workgroup: 64 ballot words
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kLong = 256;                 // runs of this many records are walked by a wave
-
-// fs_row records: the key half {work, fan_ix, orig_ix, lev} and the value half {dist, comb},
-// one 16-byte load each (rows are 16-byte aligned, 32 bytes apart)
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-  __device__ double2 val(uint64_t i) const { return reinterpret_cast<const double2*>(rows + i)[1]; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  const double* dist;
-  const double* comb;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-  __device__ double2 val(uint64_t i) const { return make_double2(dist[i], comb[i]); }
-};
 
 // s continues r: same work, 1 <= fan step <= 1 + G, 1 <= script step <= 1 + G (signed)
 __device__ inline bool joins(uint4 r, uint4 s, int64_t g1) {
@@ -67,12 +49,7 @@ __device__ inline void tile_prefix(const uint64_t* __restrict__ mask, uint64_t n
     const uint32_t lane = threadIdx.x;
     const uint64_t w = (uint64_t)blockIdx.x * (kTile / 64) + lane;
     const uint32_t c = w < n_words ? (uint32_t)__popcll(mask[w]) : 0u;
-    uint32_t inc = c;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    s_pre[lane] = inc - c;
+    s_pre[lane] = wave_scan(c) - c;
   }
   __syncthreads();
 }
@@ -107,36 +84,9 @@ __global__ __launch_bounds__(kBlock) void k_pass_heads(Src src, uint32_t n, int6
 }
 
 // exclusive scan of v[0..nb) in place, *total = sum (one workgroup, chunks of 1024 in turn)
-__global__ __launch_bounds__(kScanBlock) void k_pass_scan(uint32_t* __restrict__ v, uint32_t nb,
+__global__ __launch_bounds__(kScanBlock) void k_pass_scan(uint32_t* v, uint32_t nb,
                                                           uint32_t* __restrict__ total) {
-  __shared__ uint32_t s_w[kScanBlock / 64];
-  __shared__ uint32_t s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const uint32_t x = j < nb ? v[j] : 0u;
-    uint32_t inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const uint32_t carry = s_carry;
-    if (j < nb) v[j] = carry + pre + inc - x;
-    __syncthreads();                       // s_w and s_carry read by every wave
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
+  scan_array<uint32_t, uint32_t>(v, nb, v, total);
 }
 
 // heads[k] = index of the first record of run k; heads[n_runs] = n
@@ -381,8 +331,8 @@ int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d
                  hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
   fs_runs* r = new fs_runs;
   const int rc = d_rows ? pass_count(RowsSrc{d_rows}, n, min_words, max_gap, r->w, s)
-                        : pass_count(ColsSrc{d_work, d_fan, d_orig, nullptr, nullptr}, n,
-                                     min_words, max_gap, r->w, s);
+                        : pass_count(ColsSrc{d_work, d_fan, d_orig}, n, min_words, max_gap, r->w,
+                                     s);
   if (rc != FS_OK) {
     delete r;
     return rc;

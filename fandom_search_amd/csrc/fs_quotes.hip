@@ -26,6 +26,7 @@
 // A workgroup is one wave with its own LDS, sized from n_script (two bits per script word at
 // most: 128 KB at FS_WORKS_MAX_SCRIPT, of the CU's 160 KB) or from the number of regions.
 #include "fs_internal.h"
+#include "fs_prims.h"
 
 namespace {
 
@@ -33,26 +34,10 @@ constexpr uint32_t kWave = 64;
 constexpr uint32_t kSlice = 8192;          // records per slice of a large work, at least (quotes_run)
 constexpr uint32_t kWorksPerWave = 8;       // works a wave takes when there are many (quotes_run)
 constexpr uint32_t kDepth = 4;              // chunks of 64 records whose loads are in flight together
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kScanItems = 4;          // script words per thread of the one-workgroup scan
 constexpr uint32_t kRunBlock = 256;
 constexpr uint32_t kLong = 256;             // regions of this many words are reduced by a wave
 constexpr size_t kLdsMax = 160 * 1024;      // LDS of a CU
-
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-  __device__ double comb(uint64_t i) const { return rows[i].comb; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  const double* cmb;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-  __device__ double comb(uint64_t i) const { return cmb[i]; }
-};
 
 constexpr uint32_t kWordU32 = sizeof(fs_quote_word) / 4;       // counters of a word, as uint32
 constexpr uint32_t kRegionU32 = sizeof(fs_quote_region) / 4;
@@ -80,11 +65,6 @@ struct QuotesArgs {
   fs_quote_word* words;
   fs_quote_region* regions;
 };
-
-__device__ inline uint32_t wave_sum(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // one lane per run
 template <class Src>
@@ -297,27 +277,6 @@ __global__ __launch_bounds__(kWave) void k_quotes_each(Src src, QuotesArgs a) {
   if (__ballot(bad) && lane == 0) atomicOr(&a.status[0], 1u);
 }
 
-// inclusive scan of x over the workgroup; returns this thread's prefix and *total
-__device__ inline uint32_t block_scan(uint32_t x, uint32_t* s_w, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = x;
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(inc, d);
-    if (lane >= d) inc += y;
-  }
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-    const uint32_t t = s_w[w];
-    if (w < wave) pre += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + inc;
-}
-
 // One workgroup over the script, chunks of 4096 words in turn: per word the passages covering
 // it (scan of diff), the spans starting at or before it, the region heads at or before it and
 // its region; status[1] = regions.
@@ -347,9 +306,9 @@ __global__ __launch_bounds__(kScanBlock) void k_quotes_scan(QuotesArgs a) {
       mh += h[t];
     }
     uint32_t tp, ts, th;
-    uint32_t ap = carry_p + block_scan(mp, s_w[0], &tp) - mp;
-    uint32_t as = carry_s + block_scan(ms, s_w[1], &ts) - ms;
-    uint32_t ah = carry_h + block_scan(mh, s_w[2], &th) - mh;
+    uint32_t ap = carry_p + block_scan<kScanBlock>(mp, s_w[0], &tp);
+    uint32_t as = carry_s + block_scan<kScanBlock>(ms, s_w[1], &ts);
+    uint32_t ah = carry_h + block_scan<kScanBlock>(mh, s_w[2], &th);
 #pragma unroll
     for (uint32_t t = 0; t < kScanItems; ++t) {
       const uint64_t j = j0 + t;
@@ -659,7 +618,7 @@ extern "C" int fs_quotes(int device, const uint32_t* work, const uint32_t* fan_i
   FS_TRY(d_comb.upload(comb, n, nullptr));
   FS_TRY(d_words.reserve(n_script));
   FS_TRY(d_regions.reserve(cap < most ? cap : most));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, d_comb.p};
+  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, nullptr, d_comb.p};
   const int rc = quotes_run(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_works,
                             d_words.p, d_regions.p, cap, n_regions, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;

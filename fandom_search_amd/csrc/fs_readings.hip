@@ -24,13 +24,11 @@
 //                     kLong readings, or a bucket of more than kLong spans, by the whole wave)
 #include "fs_internal.h"
 #include "fs_probe.h"
-
-#include <stdlib.h>
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kLong = 64;
 
 static_assert(sizeof(fs_reading) == 40 && sizeof(fs_reading_span) == 24, "fs_readings");
@@ -73,22 +71,6 @@ struct RdArgs {
   fs_reading_span* spans;
 };
 
-// rank of a flagged thread among the flagged threads of its workgroup, and their number
-__device__ inline void block_rank(bool flag, uint32_t* rank, uint32_t* total) {
-  __shared__ uint32_t s_w[kBlock / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t b = __ballot(flag);
-  if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t pre = (uint32_t)__popcll(b & ((1ull << lane) - 1)), tot = 0;
-  for (uint32_t w = 0; w < kBlock / 64; ++w) {
-    if (w < wave) pre += s_w[w];
-    tot += s_w[w];
-  }
-  *rank = pre;
-  *total = tot;
-}
-
 __global__ __launch_bounds__(kBlock) void k_rd_check(RdArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const bool bad = i < a.n && (a.work[i] >= a.n_works || a.orig[i] >= a.n_script ||
@@ -100,36 +82,14 @@ __global__ __launch_bounds__(kBlock) void k_rd_check(RdArgs a) {
 // of 1024 in turn)
 __global__ __launch_bounds__(kScanBlock) void k_rd_scan(const uint32_t* in, uint32_t* out,
                                                         uint32_t nb, uint32_t* total) {
-  __shared__ uint32_t s_w[kScanBlock / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const uint32_t x = j < nb ? in[j] : 0u;
-    uint32_t inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    if (j < nb) out[j] = carry + pre + inc - x;
-    carry += tot;
-    __syncthreads();                       // s_w read by every wave
-  }
-  if (threadIdx.x == 0) *total = carry;
+  scan_array<uint32_t, uint32_t>(in, nb, out, total);
 }
 
 // kPlace false: kept runs of this workgroup's 256 runs into cnt; true: the kept runs to their
 // places, cnt holding the scan
 template <bool kPlace>
 __global__ __launch_bounds__(kBlock) void k_rd_kept(RdArgs a) {
+  __shared__ uint32_t s_w[kBlock / 64];
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   uint32_t b = 0, e = 0;
   if (r < a.n_runs) {
@@ -138,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_kept(RdArgs a) {
   }
   const bool keep = r < a.n_runs && e - b >= a.min_words;
   uint32_t rank, total;
-  block_rank(keep, &rank, &total);
+  block_rank<kBlock>(keep, s_w, &rank, &total);
   if (!kPlace) {
     if (threadIdx.x == 0) a.cnt[blockIdx.x] = total;
   } else if (keep) {
@@ -156,21 +116,6 @@ __device__ inline bool set_insert(unsigned long long* tab, uint64_t mask, unsign
                                     [key](unsigned long long cur) { return cur == key; },
                                     &inserted);
   return inserted;
-}
-
-__device__ inline uint64_t wave_sum64(uint64_t v) {
-  for (uint32_t d = 32; d; d >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-    v += (uint64_t)hi << 32 | lo;
-  }
-  return v;
-}
-
-// lane 0's value in every lane
-__device__ inline uint64_t wave_first64(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return (uint64_t)hi << 32 | lo;
 }
 
 // the readings of passages x and y (wave-uniform) are equal; the whole wave compares
@@ -198,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_insert(RdArgs a) {
     const uint64_t rec = (uint64_t)(a.orig[me.x + i] - me.z) << 32 | a.spell[me.x + i];
     acc += fs_mix64(rec + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull);
   }
-  acc = wave_sum64(acc);
+  acc = wave_sum(acc);
   uint64_t h = acc ^ fs_mix64((uint64_t)me.z << 32 | me.y);
   h = fs_mix64(fs_mix64(h) & a.hash_mask);       // the kept bits decide slot and tag
   const uint32_t tag = (uint32_t)(h >> 32);
@@ -226,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_insert(RdArgs a) {
         if (cur == kProbeEmpty) cur = mine;
       }
     }
-    cur = wave_first64(cur);
+    cur = wave_first(cur);
     if (cur == mine) {
       inserted = true;
       break;
@@ -286,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_span_rank(RdArgs a) {
     const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)c.y, j);
     uint32_t before = 0;
     for (uint32_t k = lane; k < lj; k += 64) before += a.sp_tmp[fj + k].y < yj ? 1u : 0u;
-    for (uint32_t d = 32; d; d >>= 1) before += __shfl_xor(before, d);
+    before = wave_sum(before);
     if ((int)lane == j) rank = before;
   }
   if (live && !is_long)
@@ -347,7 +292,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_rank(RdArgs a) {
     cj.w = 0;                                                    // (not compared)
     uint32_t before = 0;
     for (uint32_t k = lane; k < lj; k += 64) before += precedes(a.rd_tmp[fj + k], cj) ? 1u : 0u;
-    for (uint32_t d = 32; d; d >>= 1) before += __shfl_xor(before, d);
+    before = wave_sum(before);
     if ((int)lane == j) rank = before;
   }
   if (live && !is_long)
@@ -374,26 +319,6 @@ uint64_t readings_hash_mask() {
   const long k = strtol(e, nullptr, 10);
   return k <= 0 ? 0ull : k >= 64 ? ~0ull : (1ull << k) - 1;
 }
-
-uint32_t blocks_of(uint64_t count) { return (uint32_t)((count + kBlock - 1) / kBlock); }
-
-struct Clock {
-  static constexpr int kMarks = 6;
-  hipEvent_t ev[kMarks] = {};
-  ~Clock() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int mark(int k) {
-    if (!ev[k]) FS_HIP(hipEventCreate(&ev[k]));
-    FS_HIP(hipEventRecord(ev[k], nullptr));
-    return FS_OK;
-  }
-  double elapsed(int from, int to) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess ? (double)ms : 0.0;
-  }
-};
 
 struct RunsGuard {
   fs_runs* r = nullptr;
@@ -460,9 +385,9 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   a.min_words = min_words;
   a.hash_mask = readings_hash_mask();
   a.status = d_status.p;
-  Clock clk;
-  FS_TRY(clk.mark(0));
-  hipLaunchKernelGGL(k_rd_check, dim3(blocks_of(n)), dim3(kBlock), 0, nullptr, a);
+  Clock<6> clk;
+  FS_TRY(clk.mark(0, nullptr));
+  hipLaunchKernelGGL(k_rd_check, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, nullptr, a);
   FS_HIP(hipGetLastError());
   RunsGuard runs;
   FS_TRY(fs_runs_find(nullptr, d_work.p, d_fan.p, d_orig.p, n, min_words, max_gap, nullptr, &runs.r,
@@ -472,7 +397,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   if (st[0]) return invalid();
 
   // the kept runs, in record order
-  const uint32_t run_blocks = blocks_of(a.n_runs);
+  const uint32_t run_blocks = blocks_of(a.n_runs, kBlock);
   DBuf<uint32_t> d_cnt, d_pwork;
   DBuf<uint4> d_pinfo;
   FS_TRY(d_cnt.reserve(run_blocks));
@@ -496,7 +421,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   a.pwork = d_pwork.p;
   hipLaunchKernelGGL(k_rd_kept<true>, dim3(run_blocks), dim3(kBlock), 0, nullptr, a);
   FS_HIP(hipGetLastError());
-  FS_TRY(clk.mark(1));
+  FS_TRY(clk.mark(1, nullptr));
 
   // readings and spans: tables and counts
   DBuf<unsigned long long> d_keys;               // the four key tables
@@ -526,11 +451,11 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   a.of_cnt = d_of.p;
   a.of_first = d_of.p + n_script;
   a.of_cur = d_of.p + 2 * (size_t)n_script;
-  const uint32_t slot_blocks = blocks_of(slots);
+  const uint32_t slot_blocks = blocks_of(slots, kBlock);
   hipLaunchKernelGGL(k_rd_insert, dim3((a.n_pass + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock),
                      0, nullptr, a);
   FS_HIP(hipGetLastError());
-  FS_TRY(clk.mark(2));
+  FS_TRY(clk.mark(2, nullptr));
 
   // spans in (orig_first, orig_last) order
   hipLaunchKernelGGL(k_rd_span_count, dim3(slot_blocks), dim3(kBlock), 0, nullptr, a);
@@ -554,7 +479,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   a.sp_firstr = d_sp.p + 2 * (size_t)a.n_spans;
   a.sp_cur = d_sp.p + 3 * (size_t)a.n_spans;
   a.spans = d_spans.p;
-  const uint32_t span_blocks = blocks_of(a.n_spans);
+  const uint32_t span_blocks = blocks_of(a.n_spans, kBlock);
   hipLaunchKernelGGL(k_rd_span_scatter, dim3(slot_blocks), dim3(kBlock), 0, nullptr, a);
   hipLaunchKernelGGL(k_rd_span_rank, dim3(span_blocks), dim3(kBlock), 0, nullptr, a);
   hipLaunchKernelGGL(k_rd_scan, dim3(1), dim3(kScanBlock), 0, nullptr, a.sp_nrs, a.sp_firstr,
@@ -564,7 +489,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   FS_HIP(hipMemcpy(st, d_status.p, sizeof st, hipMemcpyDeviceToHost));
   a.n_readings = st[1];
   *n_readings = a.n_readings;
-  FS_TRY(clk.mark(3));
+  FS_TRY(clk.mark(3, nullptr));
   if (a.n_readings > cap_readings || a.n_spans > cap_spans) {
     fs_set_error("%u readings and %u spans need room", a.n_readings, a.n_spans);
     return FS_E_CAPACITY;
@@ -578,14 +503,14 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   a.rd_tmp = d_rd_tmp.p;
   a.readings = d_readings.p;
   hipLaunchKernelGGL(k_rd_scatter, dim3(slot_blocks), dim3(kBlock), 0, nullptr, a);
-  hipLaunchKernelGGL(k_rd_rank, dim3(blocks_of(a.n_readings)), dim3(kBlock), 0, nullptr, a);
+  hipLaunchKernelGGL(k_rd_rank, dim3(blocks_of(a.n_readings, kBlock)), dim3(kBlock), 0, nullptr, a);
   FS_HIP(hipGetLastError());
-  FS_TRY(clk.mark(4));
+  FS_TRY(clk.mark(4, nullptr));
   FS_HIP(hipMemcpyAsync(readings, d_readings.p, (size_t)a.n_readings * sizeof(fs_reading),
                         hipMemcpyDeviceToHost, nullptr));
   FS_HIP(hipMemcpyAsync(spans, d_spans.p, (size_t)a.n_spans * sizeof(fs_reading_span),
                         hipMemcpyDeviceToHost, nullptr));
-  FS_TRY(clk.mark(5));
+  FS_TRY(clk.mark(5, nullptr));
   FS_HIP(hipDeviceSynchronize());
   for (int k = 0; k < 5; ++k) t_ms[k] = clk.elapsed(k, k + 1);
   t_ms[5] = clk.elapsed(0, 5);

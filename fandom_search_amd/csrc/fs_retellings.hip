@@ -27,31 +27,16 @@
 //                   per-work record
 //   k_rt_write      one lane per passage: the passage records
 #include "fs_internal.h"
-
-#include <stdlib.h>
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kSmallDefault = 8;
 constexpr uint32_t kLdsDefault = 4096;
 constexpr uint32_t kLdsMax = 4096;             // 12 bytes a passage: 48 KiB of LDS a wave
 
 static_assert(sizeof(fs_retelling) == 40 && sizeof(fs_retelling_passage) == 48, "fs_retellings");
-
-// fs_row records: the key half {work, fan_ix, orig_ix, lev}, one 16-byte load
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-};
 
 // status words
 enum { kStBad = 0, kStTotal = 1, kStMedium = 2, kStLarge = 3, kStMaxMedium = 4, kStWords = 8 };
@@ -84,22 +69,6 @@ struct RtArgs {
   fs_retelling_passage* passages;
 };
 
-// rank of a flagged thread among the flagged threads of its workgroup, and their number
-__device__ inline void block_rank(bool flag, uint32_t* s_w, uint32_t* rank, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t b = __ballot(flag);
-  if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t pre = (uint32_t)__popcll(b & ((1ull << lane) - 1)), tot = 0;
-  for (uint32_t w = 0; w < kBlock / 64; ++w) {
-    if (w < wave) pre += s_w[w];
-    tot += s_w[w];
-  }
-  *rank = pre;
-  *total = tot;
-  __syncthreads();                         // s_w may be used again
-}
-
 template <class Src>
 __global__ __launch_bounds__(kBlock) void k_rt_check(Src src, RtArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -111,30 +80,7 @@ __global__ __launch_bounds__(kBlock) void k_rt_check(Src src, RtArgs a) {
 // of 1024 in turn)
 __global__ __launch_bounds__(kScanBlock) void k_rt_scan(const uint32_t* in, uint32_t* out,
                                                         uint32_t nb, uint32_t* total) {
-  __shared__ uint32_t s_w[kScanBlock / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const uint32_t x = j < nb ? in[j] : 0u;
-    uint32_t inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    if (j < nb) out[j] = carry + pre + inc - x;
-    carry += tot;
-    __syncthreads();                       // s_w read by every wave
-  }
-  if (threadIdx.x == 0) *total = carry;
+  scan_array<uint32_t, uint32_t>(in, nb, out, total);
 }
 
 // kPlace false: kept runs of this workgroup's 256 runs into cnt; true: the kept runs to their
@@ -150,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_rt_kept(Src src, RtArgs a) {
   }
   const bool keep = r < a.n_runs && e - b >= a.min_words;
   uint32_t rank, total;
-  block_rank(keep, s_w, &rank, &total);
+  block_rank<kBlock>(keep, s_w, &rank, &total);
   if (!kPlace) {
     if (threadIdx.x == 0) a.cnt[blockIdx.x] = total;
   } else if (keep) {
@@ -187,8 +133,8 @@ __global__ __launch_bounds__(kBlock) void k_rt_bin(RtArgs a) {
   const uint32_t c = w < a.n_works ? a.woff[w + 1] - a.woff[w] : 0u;
   const bool medium = c > a.small && c <= a.lds, large = c > a.small && c > a.lds;
   uint32_t rm, tm, rl, tl;
-  block_rank(medium, s_w, &rm, &tm);
-  block_rank(large, s_w, &rl, &tl);
+  block_rank<kBlock>(medium, s_w, &rm, &tm);
+  block_rank<kBlock>(large, s_w, &rl, &tl);
   if (!kPlace) {
     if (threadIdx.x == 0) {
       a.bcnt[blockIdx.x] = tm;
@@ -199,16 +145,6 @@ __global__ __launch_bounds__(kBlock) void k_rt_bin(RtArgs a) {
     if (medium) a.list[a.bcnt[blockIdx.x] + rm] = w;
     if (large) a.list[a.status[kStMedium] + a.bcnt[a.work_blocks + blockIdx.x] + rl] = w;
   }
-}
-
-// best and depth are written and read back inside one kernel, by other lanes of the wave too:
-// past the CU's vector cache
-__device__ inline uint32_t ld_agent(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline void st_agent(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __device__ inline uint64_t key_of(uint32_t best, uint32_t j) {
@@ -242,19 +178,6 @@ __global__ __launch_bounds__(kBlock) void k_rt_chain_small(RtArgs a) {
   a.wend[w] = b + ~(uint32_t)end;
   a.wdesc[w] = desc;
   a.wwords[w] = words;
-}
-
-__device__ inline uint32_t lane_u32(uint32_t v, uint32_t s) {      // s wave-uniform
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)s);
-}
-
-__device__ inline uint64_t wave_max64(uint64_t v) {
-  for (uint32_t d = 32; d; d >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-    const uint64_t o = (uint64_t)hi << 32 | lo;
-    if (o > v) v = o;
-  }
-  return v;
 }
 
 // a wave (= a workgroup) per listed work.  kLds: {orig_last, best, depth} of the work's
@@ -324,11 +247,9 @@ __global__ __launch_bounds__(64) void k_rt_chain_wave(RtArgs a, uint32_t list_fi
     }
     if (kLds) __syncthreads(); else __threadfence();  // the tile's values before the next reads them
   }
-  end = wave_max64(end);
-  for (uint32_t d = 32; d; d >>= 1) {
-    words += __shfl_xor(words, d);
-    desc += __shfl_xor(desc, d);
-  }
+  end = wave_max(end);
+  words = wave_sum(words);
+  desc = wave_sum(desc);
   if (lane == 0) {
     a.wend[w] = b + ~(uint32_t)end;
     a.wdesc[w] = desc;
@@ -371,37 +292,6 @@ __global__ __launch_bounds__(kBlock) void k_rt_write(RtArgs a) {
                                        a.ol[p], a.best[p], a.prev[p], a.depth[p], a.cpos[p]};
 }
 
-// FS_RETELLINGS_SMALL, FS_RETELLINGS_LDS: diagnostics, read on each call
-uint32_t bound_of(const char* name, uint32_t dflt, uint32_t most) {
-  const char* e = getenv(name);
-  if (!e || !*e) return dflt;
-  const unsigned long long v = strtoull(e, nullptr, 10);
-  return v > most ? most : (uint32_t)v;
-}
-
-uint32_t blocks_of(uint64_t count) { return (uint32_t)((count + kBlock - 1) / kBlock); }
-
-struct Clock {
-  static constexpr int kMarks = 6;
-  hipEvent_t ev[kMarks] = {};
-  bool set[kMarks] = {};
-  ~Clock() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int mark(int k, hipStream_t s) {
-    if (!ev[k]) FS_HIP(hipEventCreate(&ev[k]));
-    FS_HIP(hipEventRecord(ev[k], s));
-    set[k] = true;
-    return FS_OK;
-  }
-  double elapsed(int from, int to) {
-    float ms = 0.f;
-    if (!set[from] || !set[to]) return 0.0;
-    return hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess ? (double)ms : 0.0;
-  }
-};
-
 // passages, bins, chains, trace, write, total of the last call
 thread_local double t_ms[6];
 
@@ -443,7 +333,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
            fs_retelling_passage* d_passages, uint64_t cap, uint64_t* n_passages, hipStream_t s) {
   for (double& t : t_ms) t = 0.0;
   if (n && !n_works) return rt_invalid();
-  const dim3 blk(kBlock), work_grid(blocks_of(n_works));
+  const dim3 blk(kBlock), work_grid(blocks_of(n_works, kBlock));
   const auto none = [&]() -> int {
     if (n_works) hipLaunchKernelGGL(k_rt_none, work_grid, blk, 0, s, d_out, n_works);
     FS_HIP(hipGetLastError());
@@ -454,12 +344,13 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
 
   RtScratch k;
   RtArgs a{};
-  Clock clk;
+  Clock<6> clk;
   a.n = n;
   a.n_works = n_works;
   a.min_words = min_words;
-  a.small = bound_of("FS_RETELLINGS_SMALL", kSmallDefault, 0xFFFFFFFFu);
-  a.lds = bound_of("FS_RETELLINGS_LDS", kLdsDefault, kLdsMax);
+  // FS_RETELLINGS_SMALL, FS_RETELLINGS_LDS: diagnostics, read on each call
+  a.small = env_u32("FS_RETELLINGS_SMALL", kSmallDefault, 0xFFFFFFFFu);
+  a.lds = env_u32("FS_RETELLINGS_LDS", kLdsDefault, kLdsMax);
   a.work_blocks = work_grid.x;
   a.out = d_out;
   a.passages = d_passages;
@@ -467,7 +358,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   FS_HIP(hipMemsetAsync(k.status.p, 0, kStWords * sizeof(uint32_t), s));
   a.status = k.status.p;
   FS_TRY(clk.mark(0, s));
-  hipLaunchKernelGGL((k_rt_check<Src>), dim3(blocks_of(n)), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_rt_check<Src>), dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
   FS_HIP(hipGetLastError());
   FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &k.runs,
                       &a.heads, &a.n_runs));
@@ -477,7 +368,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   if (st[kStBad]) return rt_invalid();
 
   // the kept runs, in record order
-  const uint32_t run_blocks = blocks_of(a.n_runs);
+  const uint32_t run_blocks = blocks_of(a.n_runs, kBlock);
   FS_TRY(k.cnt.reserve(run_blocks));
   a.cnt = k.cnt.p;
   hipLaunchKernelGGL((k_rt_kept<Src, false>), dim3(run_blocks), blk, 0, s, src, a);
@@ -514,7 +405,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   a.list = k.list.p;
   FS_HIP(hipMemsetAsync(a.cpos, 0, np * sizeof(uint32_t), s));
   hipLaunchKernelGGL((k_rt_kept<Src, true>), dim3(run_blocks), blk, 0, s, src, a);
-  hipLaunchKernelGGL(k_rt_offsets, dim3(blocks_of((uint64_t)n_works + 1)), blk, 0, s, a);
+  hipLaunchKernelGGL(k_rt_offsets, dim3(blocks_of((uint64_t)n_works + 1, kBlock)), blk, 0, s, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(1, s));
 
@@ -544,7 +435,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(4, s));
   const bool fits = a.n_pass <= cap;
-  if (fits) hipLaunchKernelGGL(k_rt_write, dim3(blocks_of(np)), blk, 0, s, a);
+  if (fits) hipLaunchKernelGGL(k_rt_write, dim3(blocks_of(np, kBlock)), blk, 0, s, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(5, s));
   FS_HIP(hipStreamSynchronize(s));

@@ -11,6 +11,7 @@
 #pragma once
 #include "fs_internal.h"
 #include "fs_cover.h"
+#include "fs_prims.h"
 
 namespace {
 
@@ -19,20 +20,7 @@ constexpr uint32_t kChunk = 8;              // column tiles a workgroup takes (t
 constexpr uint32_t kSlice = 32;             // 64-bit words per K-slice (tests: K_SLICE)
 constexpr uint32_t kBlock = 256;            // 16 x 16 threads, 4 x 4 pairs each
 constexpr uint32_t kRunBlock = 256;
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kShStride = kTile + 1;   // of the tile of counts in LDS
-
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-};
 
 // what the shared passes read and write; a command's own arguments derive from it
 struct CoverArgs {
@@ -72,34 +60,7 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_flag(Src src, CoverArgs a) 
 template <class Out>
 __global__ __launch_bounds__(kScanBlock) void k_pairs_scan(const uint32_t* in, uint64_t nb,
                                                            Out* out, Out* __restrict__ total) {
-  __shared__ Out s_w[kScanBlock / 64];
-  __shared__ Out s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < nb; c += kScanBlock) {
-    const uint64_t j = c + threadIdx.x;
-    const Out x = j < nb ? (Out)in[j] : (Out)0;
-    Out inc = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const Out y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    Out pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const Out t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const Out carry = s_carry;
-    if (j < nb) out[j] = carry + pre + inc - x;
-    __syncthreads();                       // s_w and s_carry read by every wave
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
+  scan_array<Out, Out>(in, nb, out, total);
 }
 
 // one lane per work, before the scan's numbers replace the flags: flag[w] is kept in `flag`
@@ -129,14 +90,6 @@ __global__ __launch_bounds__(kTile) void k_pairs_covered(CoverArgs a) {
   uint32_t c = 0;
   for (uint32_t k = 0; k < a.nk; ++k) c += (uint32_t)__popcll(t[(size_t)k * kTile]);
   a.covered[(size_t)blockIdx.x * kTile + threadIdx.x] = c;
-}
-
-__device__ inline unsigned long long wave_max(unsigned long long v) {
-  for (uint32_t d = 32; d; d >>= 1) {
-    const unsigned long long o = __shfl_xor(v, d);
-    if (o > v) v = o;
-  }
-  return v;
 }
 
 // The 64 x 64 counts of row tile ti against column tile tj into s_sh (stride kShStride), by a
@@ -252,25 +205,6 @@ struct CoverJob {
   static int invalid() {
     fs_set_error("a work >= n_works or an orig_ix >= n_script");
     return FS_E_INVALID;
-  }
-};
-
-// HIP events around the passes of one call
-struct PassClock {
-  static constexpr int kMarks = 8;
-  hipEvent_t ev[kMarks] = {};
-  ~PassClock() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int mark(int k, hipStream_t s) {
-    if (!ev[k]) FS_HIP(hipEventCreate(&ev[k]));
-    FS_HIP(hipEventRecord(ev[k], s));
-    return FS_OK;
-  }
-  double elapsed(int from, int to) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess ? (double)ms : 0.0;
   }
 };
 

@@ -15,11 +15,11 @@
 //                  word of more than kLong cells is counted by the whole wave
 #include "fs_internal.h"
 #include "fs_probe.h"
+#include "fs_prims.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kScanItems = 4;          // script words per thread of the one-workgroup scan
 constexpr uint32_t kLong = 64;              // words of more cells than this are ranked by a wave
 
@@ -77,39 +77,10 @@ __global__ __launch_bounds__(kBlock) void k_var_insert(VarArgs a) {
 // words in front (0xFFFFFFFF for a word without any); status[1] = cells.
 __global__ __launch_bounds__(kScanBlock) void k_var_scan(VarArgs a) {
   __shared__ uint32_t s_w[kScanBlock / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c = 0; c < a.n_script; c += kScanBlock * kScanItems) {
-    const uint64_t j0 = c + (uint64_t)threadIdx.x * kScanItems;
-    uint32_t x[kScanItems], mine = 0;
-#pragma unroll
-    for (uint32_t t = 0; t < kScanItems; ++t) {
-      x[t] = j0 + t < a.n_script ? a.words[j0 + t].n_spellings : 0u;
-      mine += x[t];
-    }
-    uint32_t inc = mine;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    __syncthreads();
-    uint32_t at = carry + pre + inc - mine;
-#pragma unroll
-    for (uint32_t t = 0; t < kScanItems; ++t) {
-      if (j0 + t < a.n_script) a.words[j0 + t].first_cell = x[t] ? at : FS_NONE;
-      at += x[t];
-    }
-    carry += tot;
-  }
-  if (threadIdx.x == 0) a.status[1] = carry;
+  const uint32_t cells = scan_chunks<kScanItems, uint32_t, uint32_t>(
+      a.n_script, [&a](uint64_t j) { return a.words[j].n_spellings; },
+      [&a](uint64_t j, uint32_t at, uint32_t x) { a.words[j].first_cell = x ? at : FS_NONE; }, s_w);
+  if (threadIdx.x == 0) a.status[1] = cells;
 }
 
 __global__ __launch_bounds__(kBlock) void k_var_scatter(VarArgs a) {
@@ -153,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_var_rank(VarArgs a) {
     cj.n_works = (uint32_t)__builtin_amdgcn_readlane((int)c.n_works, j);
     uint32_t before = 0;
     for (uint32_t k = lane; k < lj; k += 64) before += precedes(a.tmp[fj + k], cj) ? 1u : 0u;
-    for (uint32_t d = 32; d; d >>= 1) before += __shfl_xor(before, d);
+    before = wave_sum(before);
     if ((int)lane == j) rank = before;
   }
   if (live && !is_long)

@@ -19,6 +19,7 @@
 // A workgroup is one wave with its own LDS: the bitmap and counters sized from n_script and
 // n_groups, so the usual 5 KB runs 32 waves per CU and only the limit case (96 KB) one.
 #include "fs_internal.h"
+#include "fs_prims.h"
 
 namespace {
 
@@ -26,24 +27,8 @@ constexpr uint32_t kWave = 64;
 constexpr uint32_t kSlice = 8192;          // records per slice of a large work, at least (works_run)
 constexpr uint32_t kWorksPerWave = 8;       // works a wave takes when there are many (works_run)
 constexpr uint32_t kDepth = 4;              // chunks of 64 records whose loads are in flight together
-constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kScanItems = 4;          // works per thread of the one-workgroup scan
 constexpr uint32_t kRunBlock = 256;
-
-struct RowsSrc {
-  const fs_row* rows;
-  __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
-  __device__ double comb(uint64_t i) const { return rows[i].comb; }
-};
-
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  const double* cmb;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-  __device__ double comb(uint64_t i) const { return cmb[i]; }
-};
 
 struct WorksArgs {
   uint32_t n, n_works, n_script, bw, n_groups, n_thr, slice, min_words, per_wave;
@@ -61,19 +46,6 @@ struct WorksArgs {
   fs_work_cell* staged;
   fs_work_cell* cells;
 };
-
-__device__ inline uint32_t wave_sum(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-__device__ inline uint32_t wave_max(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) {
-    const uint32_t y = __shfl_xor(v, d);
-    v = y > v ? y : v;
-  }
-  return v;
-}
 
 // one lane per run
 template <class Src>
@@ -125,53 +97,16 @@ __global__ __launch_bounds__(kRunBlock) void k_works_runs(Src src, WorksArgs a,
 template <int kKind>
 __global__ __launch_bounds__(kScanBlock) void k_works_scan(WorksArgs a) {
   __shared__ uint32_t s_w[kScanBlock / 64];
-  __shared__ uint32_t s_carry;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t* __restrict__ dst = kKind ? a.coff : a.toff;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (uint64_t c = 0; c < a.n_works; c += kScanBlock * kScanItems) {
-    const uint64_t j0 = c + (uint64_t)threadIdx.x * kScanItems;
-    uint32_t x[kScanItems], mine = 0;
-#pragma unroll
-    for (uint32_t t = 0; t < kScanItems; ++t) {
-      const uint64_t j = j0 + t;
-      x[t] = 0;
-      if (j < a.n_works) {
-        if (kKind) {
-          x[t] = a.out[j].n_groups_hit;
-        } else {
-          const uint32_t nw = a.wend[j] - a.wstart[j];
-          x[t] = nw < a.n_groups ? nw : a.n_groups;
-        }
-      }
-      mine += x[t];
-    }
-    uint32_t inc = mine;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
-      const uint32_t t = s_w[w];
-      if (w < wave) pre += t;
-      tot += t;
-    }
-    const uint32_t carry = s_carry;
-    uint32_t at = carry + pre + inc - mine;
-#pragma unroll
-    for (uint32_t t = 0; t < kScanItems; ++t) {
-      if (j0 + t < a.n_works) dst[j0 + t] = at;
-      at += x[t];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.status[kKind ? 2 : 1] = s_carry;
+  const uint32_t cells = scan_chunks<kScanItems, uint32_t, uint32_t>(
+      a.n_works,
+      [&a](uint64_t j) -> uint32_t {
+        if (kKind) return a.out[j].n_groups_hit;
+        const uint32_t nw = a.wend[j] - a.wstart[j];
+        return nw < a.n_groups ? nw : a.n_groups;
+      },
+      [dst](uint64_t j, uint32_t at, uint32_t) { dst[j] = at; }, s_w);
+  if (threadIdx.x == 0) a.status[kKind ? 2 : 1] = cells;
 }
 
 // A wave's LDS: bit per script word, then records and exact records per group.
@@ -593,7 +528,7 @@ extern "C" int fs_works(int device, const uint32_t* work, const uint32_t* fan_ix
   FS_TRY(d_out.reserve(n_works));
   FS_TRY(d_counts.reserve((size_t)n_works * (n_thr + 1)));
   FS_TRY(d_cells.reserve(cap < n_rows ? cap : n_rows));       // a record makes at most one cell
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, d_comb.p};
+  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, nullptr, d_comb.p};
   const int rc = works_run(src, nullptr, src, n, n_works, n_script, group_of, n_groups, min_words,
                            max_gap, thresholds, n_thr, d_out.p, d_counts.p, d_cells.p, cap, n_cells,
                            nullptr);

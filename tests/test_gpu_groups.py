@@ -153,6 +153,22 @@ def test_one_group_of_all_of_a_thousand_works_and_a_thousand_groups_of_one():
     check(cols, n_works, n_script, [[0]] * n_works, 1, m=3, k=300)      # above a slab's count
 
 
+@pytest.mark.parametrize("n_groups", [1023, 1025, 2049])
+def test_groups_around_the_scan_s_chunk(n_groups):
+    """k_groups_scan takes 1024 groups per chunk: every group has cells and word rows, so the
+    offsets of the groups past a chunk carry the sums of the chunks in front."""
+    n_script = 300
+    rng = np.random.default_rng(n_groups)
+    spans_of = [[(int(rng.integers(0, n_script - 12)), int(rng.integers(3, 13)))]
+                for _ in range(n_groups)]
+    cols = with_exact(from_spans(spans_of), n_groups)
+    # work w is in group w, and every third one in the group after it as well
+    mem = [sorted({w, (w + 1) % n_groups} if w % 3 == 0 else {w}) for w in range(n_groups)]
+    found = check(cols, n_groups, n_script, mem, n_groups, m=3)
+    assert (found[0]["n_passage_works"] >= 1).all() and (found[0]["covered"] >= 3).all()
+    assert len(set(found[1]["group"].tolist())) == n_groups == len(set(found[2]["group"].tolist()))
+
+
 @pytest.mark.parametrize("k", [1, 3])
 def test_twenty_groups_per_work_out_of_three_hundred(k):
     n_works, n_script, n_groups = 400, 200, 300

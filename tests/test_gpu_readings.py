@@ -199,6 +199,23 @@ def test_200000_records(monkeypatch, n_script, hash_bits):
     check(cols, 5000, n_script, 997, min_words=4, max_gap=2)
 
 
+# fs_readings.hip: k_rd_kept counts the kept runs of 256 runs, and the one-workgroup scan takes
+# 1024 such counts per chunk
+RUN_CHUNK = 1024 * 256
+
+
+@pytest.mark.parametrize("n", [RUN_CHUNK - 1, RUN_CHUNK + 1])
+def test_kept_runs_around_the_scan_s_chunk(monkeypatch, n):
+    """Every record its own kept run (the fan index steps by 2): one run short of a chunk of
+    the scan of the kept-run counts, and one run into its second chunk."""
+    set_bits(monkeypatch, None)
+    i = np.arange(n, dtype=np.int64)
+    cols = [np.asarray(c, dtype=np.uint32) for c in (i * 7 // n, 2 * i, i * 7 % 40, i // 3 % 5)]
+    found, spans, n_pass = check(cols, 7, 40, 5, min_words=1)
+    assert n_pass == n and len(spans) == 40 and len(found) == 120
+    assert int(found["n_passages"].sum()) == n
+
+
 # ---- capacity and refusals -------------------------------------------------------------------
 
 def call(cols, n_works, n_script, n_spell, min_words, max_gap, cap_r, cap_s, n_rows=None):

@@ -223,6 +223,27 @@ def test_works_of_every_class_in_one_input(path):
     assert [tuple(w) for w in works[empty].tolist()] == [(0, 0, 0, 0, NONE, NONE, 0, 0, 0, 0)] * 38
 
 
+# fs_retellings.hip: k_rt_kept counts the kept runs of 256 runs, and the one-workgroup scan
+# takes 1024 such counts per chunk
+RUN_CHUNK = 1024 * 256
+
+
+@pytest.mark.parametrize("n", [RUN_CHUNK - 1, RUN_CHUNK + 1])
+def test_kept_runs_around_the_scan_s_chunk(monkeypatch, n):
+    """Every record its own kept run (the fan index steps by 2), four to a work: one run short
+    of a chunk of the scan of the kept-run counts, and one run into its second chunk."""
+    for name in ("FS_RETELLINGS_SMALL", "FS_RETELLINGS_LDS"):
+        monkeypatch.delenv(name, raising=False)
+    i = np.arange(n, dtype=np.int64)
+    orig = np.random.default_rng(n).integers(0, 997, n)
+    cols = tuple(np.asarray(c, dtype=np.uint32) for c in (i // 4, 2 * (i % 4), orig))
+    n_works = (n + 3) // 4
+    works, found = check(cols, n_works, min_words=1)
+    assert len(found) == n and found["first"].tolist() == list(range(n))
+    assert works["n_passages"].tolist() == [4] * (n // 4) + [n % 4] * (n_works - n // 4)
+    assert 2 < works["chain_passages"].mean() < 3
+
+
 # ---- capacity and refusals -------------------------------------------------------------------
 
 def call(cols, n_works, min_words, max_gap, cap, n_rows=None, out=True):

@@ -95,7 +95,8 @@ def main():
                 cols = [np.empty(n, dtype=d) for d in (np.uint32,) * 3 + (np.float64,) * 2]
                 ix = np.empty(n, dtype=abi.MATCH_IX_DTYPE)
                 t2 = time.perf_counter()
-                _lib.check(L.fs_matches_read(h, *(c.ctypes.data_as(C.c_void_p) for c in cols),
+                types = L.fs_matches_read.argtypes[1:6]
+                _lib.check(L.fs_matches_read(h, *(c.ctypes.data_as(t) for c, t in zip(cols, types)),
                                              ix.ctypes.data_as(C.c_void_p), n, None, 0), "fs_matches_read")
                 t3 = time.perf_counter()
                 L.fs_matches_close(h)
