@@ -26,6 +26,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_retellings", "fs_retellings_rows", "fs_retellings_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_companions", "fs_companions_rows", "fs_companions_times",
+           "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
@@ -201,6 +202,17 @@ def load():
                                      C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_companions_times.restype = C.c_int
     L.fs_companions_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_transitions.restype = C.c_int
+    L.fs_transitions.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                 u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_transitions_rows.restype = C.c_int
+    L.fs_transitions_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      u64p]
+    L.fs_transitions_times.restype = C.c_int
+    L.fs_transitions_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_clusters.restype = C.c_int
     L.fs_clusters.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

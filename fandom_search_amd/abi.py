@@ -137,6 +137,21 @@ assert COMPANION_DTYPE.itemsize == 32
 FS_COMPANIONS_MAX_BYTES = 1 << 30
 COMPANIONS_MS_NAMES = ("incidence", "count", "place", "detail")
 
+# fs_transition_unit: 40 bytes; fs_transition: 32 bytes
+TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
+                                  ("starts", np.uint32), ("ends", np.uint32),
+                                  ("steps_out", np.uint32), ("steps_in", np.uint32),
+                                  ("successors", np.uint32), ("predecessors", np.uint32),
+                                  ("best_next", np.uint32), ("best_steps", np.uint32)])
+assert TRANSITION_UNIT_DTYPE.itemsize == 40
+TRANSITION_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("steps", np.uint32),
+                             ("advances", np.uint32), ("works", np.uint32),
+                             ("first_work", np.uint32), ("steps_out_a", np.uint32),
+                             ("steps_in_b", np.uint32)])
+assert TRANSITION_DTYPE.itemsize == 32
+FS_TRANSITIONS_DENSE = 64
+TRANSITIONS_MS_NAMES = ("sequence", "count", "keep", "place", "total")
+
 # fs_cluster_work: 32 bytes; fs_cluster: 48 bytes
 CLUSTER_WORK_DTYPE = np.dtype([("covered", np.uint32), ("root", np.uint32), ("size", np.uint32),
                                ("cluster", np.uint32), ("links", np.uint32), ("best", np.uint32),

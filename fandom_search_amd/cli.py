@@ -13,7 +13,8 @@ the reuse by year, author, language or tag of the works (fandom_search_amd/group
 quoted stretch (fandom_search_amd/readings.py), and `retellings`, which lists the works that
 quote the script in the script's own order (fandom_search_amd/retellings.py), and `companions`,
 which relates the quoted stretches of the script by the works quoting both
-(fandom_search_amd/companions.py).  The
+(fandom_search_amd/companions.py), and `transitions`, which counts which stretch the works
+quote next after each stretch (fandom_search_amd/transitions.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -34,7 +35,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings, companions or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings, companions, transitions or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -363,6 +364,45 @@ def build_parser():
                                    help='who reads the match csv: the GPU (default) or '
                                         'csv.reader; also FANDOM_SEARCH_READER')
     companions_parser.set_defaults(func=_companions)
+
+    transitions_parser = subparsers.add_parser(
+        'transitions', help='counts which stretch of the script the fan works quote next: per '
+                            'pair (from, to) of quoted regions, scenes or characters the steps '
+                            'from one to the other, per unit its most usual successor')
+    transitions_parser.add_argument('matches', action='store',
+                                    help='filename for search output (dated or batch file)')
+    transitions_parser.add_argument('-o', '--output', action='store', default=None,
+                                    help='prefix of the two csv files, PREFIX-transitions.csv and '
+                                         'PREFIX-transitions-units.csv (default: the input name '
+                                         'without .csv)')
+    transitions_parser.add_argument('--by', default='region',
+                                    choices=('region', 'scene', 'character'),
+                                    help='the units: the quoted regions of `quotes` (default), '
+                                         'the scenes or the characters of the script')
+    transitions_parser.add_argument('--min-words', default=6, type=int,
+                                    help='fewest matched words a passage has, default 6')
+    transitions_parser.add_argument('--max-gap', default=0, type=int,
+                                    help='words without a record a passage may step over on each '
+                                         'side at once, default 0')
+    transitions_parser.add_argument('--min-works', default=1, type=int,
+                                    help='with --by region: fewest different works whose passages '
+                                         'cover every word of a region, default 1')
+    transitions_parser.add_argument('--within', default=None, type=int,
+                                    help='most fan words between the two passages of a step, '
+                                         'default any distance')
+    transitions_parser.add_argument('--min-steps', default=1, type=int,
+                                    help='fewest steps of a listed cell, default 1')
+    transitions_parser.add_argument('--min-step-works', default=2, type=int,
+                                    help='fewest different works taking the step of a listed '
+                                         'cell, default 2')
+    transitions_parser.add_argument('--min-share', default=0, type=int,
+                                    help='fewest steps of a listed cell as a whole percentage of '
+                                         'the steps leaving its first unit, 0 to 100, default 0')
+    transitions_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    transitions_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                    help='who reads the match csv: the GPU (default) or '
+                                         'csv.reader; also FANDOM_SEARCH_READER')
+    transitions_parser.set_defaults(func=_transitions)
     return parser
 
 
@@ -509,6 +549,23 @@ def _companions(args):
         return companions.process(args)
     except ValueError as e:
         sys.exit('ao3.py companions: error: %s' % e)
+
+
+def _transitions(args):
+    from . import transitions
+    if (args.min_words < 1 or args.min_works < 1 or args.min_steps < 1 or args.min_step_works < 1
+            or args.max_gap < 0):
+        sys.exit('ao3.py transitions: error: --min-words, --min-works, --min-steps and '
+                 '--min-step-works must be at least 1, --max-gap at least 0')
+    if args.within is not None and not 0 <= args.within < 0xFFFFFFFF:
+        sys.exit('ao3.py transitions: error: --within must be from 0 to 4294967294 (leave it '
+                 'out for any distance)')
+    if not 0 <= args.min_share <= 100:
+        sys.exit('ao3.py transitions: error: --min-share must be from 0 to 100')
+    try:
+        return transitions.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py transitions: error: %s' % e)
 
 
 def main(argv=None):

@@ -608,6 +608,52 @@ class ScriptIndex(object):
                     pairs[:n.value * abi.COMPANION_DTYPE.itemsize].cpu().numpy()
                     .view(abi.COMPANION_DTYPE))
 
+    def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
+                           max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
+                           min_share=0, out_ptrs=None, cap=None):
+        """`transitions` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident unit map of the script's words (fs_transitions_rows): per unit its
+        passages, works, starts, ends, steps and best successor, and the kept cells (a, b) of
+        steps from unit a to unit b, in (a, b) order.  Without `out_ptrs`:
+        (abi.TRANSITION_UNIT_DTYPE[n_units], abi.TRANSITION_DTYPE[n_cells]) on the host.  With
+        `out_ptrs` = device addresses (units; cells, a buffer of `cap` of them): the number of
+        cells; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the units
+        are complete then).  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+        n = C.c_uint64(0)
+
+        def call(units, cells, cap):
+            return L.fs_transitions_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                         C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                         int(max_gap), int(within), int(min_steps),
+                                         int(min_step_works), int(min_share), C.c_void_p(units),
+                                         C.c_void_p(cells), int(cap), C.byref(n))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_transitions_rows", "cell buffer too small")
+                err.required = int(n.value)
+                raise err
+            _lib.check(rc, "fs_transitions_rows")
+            return int(n.value)
+        import torch
+        units = torch.empty(max(1, int(n_units)) * abi.TRANSITION_UNIT_DTYPE.itemsize,
+                            dtype=torch.uint8, device="cuda")
+        cap = 4096 if cap is None else int(cap)
+        while True:
+            cells = torch.empty(max(1, cap) * abi.TRANSITION_DTYPE.itemsize, dtype=torch.uint8,
+                                device="cuda")
+            torch_ready()
+            rc = call(units.data_ptr(), cells.data_ptr(), cap)
+            if rc == abi.FS_E_CAPACITY:                  # (the keep pass says how many)
+                cap = int(n.value)
+                continue
+            _lib.check(rc, "fs_transitions_rows")
+            return (units[:int(n_units) * abi.TRANSITION_UNIT_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.TRANSITION_UNIT_DTYPE),
+                    cells[:n.value * abi.TRANSITION_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.TRANSITION_DTYPE))
+
     def clusters_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_shared=6,
                         min_jaccard=50, min_size=2, common_pct=50, out_ptrs=None, cap=None):
         """`clusters` over device-resident fs_row records sorted by (work, fan_ix) (after a

@@ -813,6 +813,80 @@ int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint
  * results), place pass, detail pass; 0 for a pass that did not run.  tools/companions_bench.py. */
 int fs_companions_times(double* ms);
 
+/* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
+ * complement of fs_companions.  Records and passages as for fs_passages, in record order;
+ * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
+ * unit_of[n_script] as for fs_companions; the unit of a passage is unit_of[orig_first], and a
+ * passage without a unit is left out: it neither counts nor breaks anything.
+ *  - A work's sequence is its unit-bearing passages in record order, p_1 .. p_m.
+ *  - A step is a pair (p_k, p_k+1) of the sequence with within == 0xFFFFFFFF (any distance) or
+ *    fan_first(p_k+1) - fan_last(p_k) <= within + 1 (in 64 bits): at most `within` fan words
+ *    lie between the two.  It goes from a = unit(p_k) to b = unit(p_k+1); a == b is a loop.  It
+ *    advances when orig_first(p_k+1) > orig_last(p_k), the following rule of fs_retellings.
+ *  - Cell (a, b): its steps, those that advance, the distinct works with such a step and the
+ *    smallest of them.  steps_out(a) and steps_in(b) sum over all cells, kept or not.
+ *  - A cell is kept when steps >= min_steps, works >= min_step_works and steps * 100 >=
+ *    min_share * steps_out(a) (the product in 64 bits; min_share a whole percentage, 0..100;
+ *    exactly at the bound is kept).
+ * Every output is an integer: adds and minima commute, set membership does not depend on who
+ * inserted, ties are settled by single 64-bit keys and places come from scanned counts, so no
+ * schedule changes the result. */
+typedef struct fs_transition_unit {
+  uint32_t passages;         /* unit-bearing passages in the unit                       */
+  uint32_t works;            /* distinct works with one                                 */
+  uint32_t starts;           /* works whose sequence begins in the unit                 */
+  uint32_t ends;             /* works whose sequence ends in it (one passage: both)     */
+  uint32_t steps_out, steps_in;
+  uint32_t successors;       /* kept cells (u, .)                                       */
+  uint32_t predecessors;     /* kept cells (., u)                                       */
+  uint32_t best_next;        /* the b of the kept cell (u, b) with the most steps, the
+                                smaller b on a tie; 0xFFFFFFFF without a kept cell      */
+  uint32_t best_steps;       /* its steps; 0 without one                                */
+} fs_transition_unit;        /* 40 bytes                                                */
+
+typedef struct fs_transition {
+  uint32_t a, b;             /* from unit a to unit b                                   */
+  uint32_t steps, advances;
+  uint32_t works, first_work;
+  uint32_t steps_out_a, steps_in_b;
+} fs_transition;             /* 32 bytes                                                */
+
+/* Host columns and the host unit map in; units[n_units] and `cap` cells out, on HIP device
+ * `device`.  The kept cells come in (a, b) ascending order.  Both entry points: FS_E_INVALID for
+ * null arguments, min_words, min_steps or min_step_works == 0, min_share > 100, records out of
+ * (work, fan_ix) order, a work >= n_works, an orig_ix >= n_script or a unit_of entry that is
+ * neither below n_units nor 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32 or n_script >
+ * FS_WORKS_MAX_SCRIPT; FS_E_CAPACITY with *n_cells = cells required when cap is smaller (units
+ * is complete then, cells untouched).  n_rows == 0 or n_units == 0: units of zeros with
+ * best_next 0xFFFFFFFF, *n_cells = 0 (fs_transitions: without device work, the unit map unread).
+ * Device memory is a few words per record and per unit.  Up to FS_TRANSITIONS_DENSE units
+ * (default and most 64; 0: never) the cells are a plain n_units x n_units array that every
+ * workgroup accumulates in LDS; beyond it they are the slots of a hash table.
+ * FS_TRANSITIONS_HASH_BITS keeps that many bits of every hash (0: every key probes from slot
+ * 0).  Both are diagnostics of the environment, read on each call; the output is the same
+ * wherever they stand. */
+int fs_transitions(int device, const uint32_t* work, const uint32_t* fan_ix,
+                   const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                   const uint32_t* unit_of, uint32_t n_units, uint32_t min_words,
+                   uint32_t max_gap, uint32_t within, uint32_t min_steps,
+                   uint32_t min_step_works, uint32_t min_share, fs_transition_unit* units,
+                   fs_transition* cells, uint64_t cap, uint64_t* n_cells);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (4-byte aligned), on the index's device
+ * and stream; returns when they are written. */
+int fs_transitions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                        const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                        uint32_t max_gap, uint32_t within, uint32_t min_steps,
+                        uint32_t min_step_works, uint32_t min_share,
+                        fs_transition_unit* d_units, fs_transition* d_cells, uint64_t cap,
+                        uint64_t* n_cells);
+/* HIP-event milliseconds of the last fs_transitions / fs_transitions_rows call on this thread:
+ * sequence (checks, run heads, the unit-bearing passages listed), count (the steps and every
+ * figure behind them), keep (the keep rule, the scan, the per-unit results), place (scatter and
+ * rank), and the total of the four; 0 for a pass that did not run.
+ * tools/transitions_bench.py. */
+int fs_transitions_times(double* ms);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
