@@ -772,11 +772,13 @@ static int corpus_prepare(fs_index* ix, fs_corpus* c) {
     FS_TRY(fs_launch_levtab(ix, c, ix->stream));
     FS_HIP(hipMemcpyAsync(ix->h_status, ix->cur->d_status.p, sizeof(fs_status), hipMemcpyDeviceToHost, ix->stream));
     FS_HIP(hipStreamSynchronize(ix->stream));
-    if (ix->h_status->bad_string) { fs_set_error("script vector id without a string"); return FS_E_INVALID; }
-    if (ix->h_status->lev_overflow) {
-      fs_set_error("an n-gram text exceeds %d code points", FS_LEV_MAX);
-      return FS_E_UNSUPPORTED;
-    }
+    FS_HIP(hipMemsetAsync(ix->cur->d_status.p, 0, sizeof(fs_status), ix->stream));
+    if (ix->h_status->bad_string && !c->has_str) { fs_set_error("script vector id without a string"); return FS_E_INVALID; }
+    // (an n-gram text of more than FS_LEV_MAX code points leaves its entries unknown, and so
+    // does, for a batch with string ids of its own, a vector id without a string: such hits go
+    // to the per-hit kernels, and without string ids a hit on such an n-gram is refused by the
+    // search that finds it)
+    c->levtab_holes = ix->h_status->lev_overflow != 0 || ix->h_status->bad_string != 0;
     c->levtab_ready = true;
   }
   // (the LSH pipeline's k_lsh_lev reads them too, with or without string ids of the batch's own)

@@ -393,6 +393,7 @@ struct fs_corpus {
   bool strrec_ready = false;
   DBuf<uint32_t> d_ctab;               // batch table of k_scan_rows: ids + this batch's best records (k_ctab)
   bool levtab_ready = false;
+  bool levtab_holes = false;           // ... with entries FS_NONE: an n-gram text of more than FS_LEV_MAX code points, or (string ids of the batch's own when it was built) a vector id without a string
   bool ctab_ready = false;
   bool ctab_str = false;               // ... built for a batch with string ids of its own (entries mark unknown table distances)
   DBuf<unsigned long long> d_gramtab_best;   // LSH pipeline: per script n-gram, what a window with its ids and

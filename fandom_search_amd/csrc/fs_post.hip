@@ -314,11 +314,12 @@ __global__ __launch_bounds__(kThreads, 8) void k_verify_direct(CorpusDev c, Gram
 // against the strings whose ids are the gram's vector ids.  For corpora whose string id ==
 // vector id the fan text of a hit is a function of the gram alone; corpora with string ids
 // of their own use the table for the hits whose tokens all carry string id == vector id
-// (k_matchlev).  One wave per entry.  `tolerant` (string ids of their own): an id without
-// a string or an over-long text gives FS_NONE instead of an error.
+// (k_matchlev).  One wave per entry.  An over-long text or an id without a string gives FS_NONE
+// and is reported in st: the table has entries that a hit must not use (a search refuses such
+// a hit, the n-grams nothing quotes cost nothing; what a missing string means is the host's
+// to say: an error without string ids of the batch's own).
 __global__ __launch_bounds__(256) void k_levtab(GramIndexDev g, CorpusDev c,
-                                                uint32_t* __restrict__ levtab, fs_status* st,
-                                                bool tolerant) {
+                                                uint32_t* __restrict__ levtab, fs_status* st) {
   __shared__ uint32_t s_a[4][FS_LEV_MAX + 2], s_b[4][FS_LEV_MAX + 2];
   __shared__ fs_status s_st[4];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -328,16 +329,14 @@ __global__ __launch_bounds__(256) void k_levtab(GramIndexDev g, CorpusDev c,
     uint32_t v = 0;
     if (r < g.gcnt[gram]) {                              // wave-uniform
       const uint32_t first = g.gpos[(size_t)gram * g.nn];
-      if (tolerant) {
-        if (lane == 0) { s_st[wave].bad_string = 0; s_st[wave].lev_overflow = 0; }
-        __builtin_amdgcn_wave_barrier();
-        v = lev_wave(g, g.gpos[i], g.stok + first, c.chars, c.coff, c.n_str, &s_st[wave], s_a[wave],
-                     s_b[wave]);
-        __builtin_amdgcn_wave_barrier();
-        if (s_st[wave].bad_string | s_st[wave].lev_overflow) v = FS_NONE;
-      } else {
-        v = lev_wave(g, g.gpos[i], g.stok + first, c.chars, c.coff, c.n_str, st, s_a[wave], s_b[wave]);
-      }
+      if (lane == 0) { s_st[wave].bad_string = 0; s_st[wave].lev_overflow = 0; }
+      __builtin_amdgcn_wave_barrier();
+      v = lev_wave(g, g.gpos[i], g.stok + first, c.chars, c.coff, c.n_str, &s_st[wave], s_a[wave],
+                   s_b[wave]);
+      __builtin_amdgcn_wave_barrier();
+      if (s_st[wave].bad_string | s_st[wave].lev_overflow) v = FS_NONE;
+      if (lane == 0 && s_st[wave].lev_overflow) st->lev_overflow = 1;
+      if (lane == 0 && s_st[wave].bad_string) st->bad_string = 1;
     }
     if (lane == 0) levtab[i] = v;
     __builtin_amdgcn_wave_barrier();
@@ -499,8 +498,24 @@ __device__ __forceinline__ fs_best best_of_ranks(const GramIndexDev& g, uint32_t
 __global__ void k_gbest(GramIndexDev g, const uint32_t* __restrict__ levtab,
                         fs_best* __restrict__ gbest) {
   for (uint32_t gram = blockIdx.x * blockDim.x + threadIdx.x; gram < g.n_grams;
-       gram += gridDim.x * blockDim.x)
-    gbest[gram] = best_of_ranks(g, gram, levtab + (size_t)gram * g.nn);
+       gram += gridDim.x * blockDim.x) {
+    fs_best b = best_of_ranks(g, gram, levtab + (size_t)gram * g.nn);
+    // a rank whose distance is not known: so is the n-gram's record
+    for (uint32_t r = 0; r < g.gcnt[gram]; ++r)
+      if (levtab[(size_t)gram * g.nn + r] == FS_NONE) b.lev = FS_NONE;
+    gbest[gram] = b;
+  }
+}
+
+// String id == vector id and a table with unknown entries (fs_corpus::levtab_holes): a hit on
+// an n-gram whose record is not known is refused like an over-long operand of a per-hit kernel.
+__global__ void k_gbest_known(const uint32_t* __restrict__ cg, NSrc nc,
+                              const fs_best* __restrict__ gbest, fs_status* st) {
+  const uint32_t total = nc.get();
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const uint32_t gram = cg[i];
+    if (gram != FS_NONE && gbest[gram].lev == FS_NONE) st->lev_overflow = 1;
+  }
 }
 
 __global__ void k_cbest(GramIndexDev g, const uint32_t* __restrict__ cg,
@@ -829,7 +844,7 @@ int fs_launch_levtab(fs_index* ix, fs_corpus* c, hipStream_t s) {
   if (total) {
     const uint32_t blocks = (uint32_t)((total + 3) / 4);
     hipLaunchKernelGGL(k_levtab, dim3(blocks > 4096 ? 4096 : blocks), dim3(256), 0, s,
-                       ix->gram_dev(), c->dev(), c->d_levtab.p, ix->cur->d_status.p, c->has_str);
+                       ix->gram_dev(), c->dev(), c->d_levtab.p, ix->cur->d_status.p);
     const uint32_t gb = (ix->n_grams + 255) / 256;
     hipLaunchKernelGGL(k_gbest, dim3(gb > 1024 ? 1024 : gb), dim3(256), 0, s, ix->gram_dev(),
                        c->d_levtab.p, c->d_gbest.p);
@@ -932,6 +947,8 @@ int fs_launch_post(fs_index* ix, fs_corpus* c, uint32_t n_sub, int tpl, uint32_t
                        ix->cur->w_mlev.p, st);
     hipLaunchKernelGGL(k_cbest, dim3(kNB), dim3(kThreads), 0, s, g, ix->cur->w_cg.p, ix->cur->w_mlev.p, nc,
                        ix->cur->w_cbest.p);
+  } else if (!per_cand && c->levtab_holes) {
+    hipLaunchKernelGGL(k_gbest_known, dim3(kNB), dim3(kThreads), 0, s, ix->cur->w_cg.p, nc, c->d_gbest.p, st);
   }
   FS_HIP(hipGetLastError());
   return fs_launch_rows(ix, c, per_cand ? ix->cur->w_cbest.p : c->d_gbest.p, per_cand ? 1 : 0, ccap,

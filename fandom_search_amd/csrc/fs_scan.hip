@@ -1401,6 +1401,9 @@ uint32_t fs_scan_rows_shape(const fs_index* ix, const fs_corpus* c, uint32_t* bl
   // (string ids of their own: the per-hit Levenshtein form, when the character classes exist)
   if (c->has_str && !(c->ctab_str && c->strrec_ready && ix->strfast_ok && ix->sw.str_fused && ix->sw.str_fast)) return 0;
   if (!c->has_str && c->ctab_str) return 0;
+  // (string id == vector id and n-grams whose table distance is not known: the chained kernels
+  // refuse a hit on one of those, k_gbest_known)
+  if (!c->has_str && c->levtab_holes) return 0;
   // a switch that asks for one of the other scan kernels or paths
   const fs_switches& sw = ix->sw;
   if (sw.scan_simple || sw.scan_tpl == 4 || !sw.scan_direct || sw.scan_capw) return 0;
