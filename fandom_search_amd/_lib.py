@@ -27,6 +27,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_companions", "fs_companions_rows", "fs_companions_times",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
+           "fs_matrix", "fs_matrix_rows", "fs_matrix_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
@@ -261,6 +262,14 @@ def load():
                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_retellings_times.restype = C.c_int
     L.fs_retellings_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_matrix.restype = C.c_int
+    L.fs_matrix.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                            C.c_uint32, u32p, C.c_void_p, C.c_uint64, u64p, u64p]
+    L.fs_matrix_rows.restype = C.c_int
+    L.fs_matrix_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p]
+    L.fs_matrix_times.restype = C.c_int
+    L.fs_matrix_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_intern.restype = C.c_int
     L.fs_matches_intern.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint64, u64p]
     L.fs_matches_intern_times.restype = C.c_int

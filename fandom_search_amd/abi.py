@@ -222,6 +222,12 @@ RETELLING_PASSAGE_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32)
 assert RETELLING_PASSAGE_DTYPE.itemsize == 48
 RETELLINGS_MS_NAMES = ("passages", "bins", "chains", "trace", "write", "total")
 
+# fs_matrix_ngram 8 bytes
+FS_MATRIX_MAX_BYTES = 1 << 30
+MATRIX_NGRAM_DTYPE = np.dtype([("work", np.uint32), ("start", np.uint32)])
+assert MATRIX_NGRAM_DTYPE.itemsize == 8
+MATRIX_MS_NAMES = ("runs", "spans", "counter", "pick", "place", "total")
+
 # the match CSV reader (fs_matches_*): fs_match_ix 64 bytes, fs_match_defer 8, fs_matches_info 96
 FS_MATCH_FIELDS = 12
 FS_MATCHES_PARSED = 0

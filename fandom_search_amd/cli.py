@@ -101,6 +101,14 @@ def build_parser():
                                help='fandom/movie name for output file prefix')
     matrix_parser.add_argument('-n', action='store', default=6, type=int,
                                help='n-gram size, default is 6-grams')
+    matrix_parser.add_argument('--engine', default='python', choices=('python', 'device'),
+                               help='where the spans are joined, counted and chosen: python '
+                                    '(the default, no GPU needed) or device (the GPU; a file it '
+                                    'does not take goes to python)')
+    matrix_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    matrix_parser.add_argument('--cells', action='store_true',
+                               help='also write the matrix without its zeros, one row per '
+                                    'non-zero cell, to ...-gram-match-cells.csv')
     matrix_parser.set_defaults(func=_matrix)
 
     passages_parser = subparsers.add_parser(

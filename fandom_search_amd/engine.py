@@ -741,6 +741,46 @@ class ScriptIndex(object):
                     found[:n.value * abi.RETELLING_PASSAGE_DTYPE.itemsize].cpu().numpy()
                     .view(abi.RETELLING_PASSAGE_DTYPE))
 
+    def matrix_device(self, rows_ptr, n_rows, n_works, n_script, ngram=6, out_ptrs=None,
+                      cap=None):
+        """The n-grams of `matrix` over device-resident fs_row records sorted by
+        (work, fan_ix) (after a search or a gather; fs_matrix_rows).  Without `out_ptrs`:
+        (starts[n_script], n_spans, abi.MATRIX_NGRAM_DTYPE kept n-grams) on the host.  With
+        `out_ptrs` = device addresses (starts, or 0 for none; n-grams, a buffer of `cap` of
+        them): (n_spans, n_kept); FsError(FS_E_CAPACITY) with .required when that buffer is too
+        small (starts is complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+        spans, kept = C.c_uint64(0), C.c_uint64(0)
+
+        def call(starts, found, cap):
+            return L.fs_matrix_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    int(n_script), int(ngram), C.c_void_p(starts),
+                                    C.c_void_p(found), int(cap), C.byref(spans), C.byref(kept))
+        if out_ptrs is not None:
+            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
+            if rc == abi.FS_E_CAPACITY:
+                err = _lib.FsError(rc, "fs_matrix_rows", "n-gram buffer too small")
+                err.required = int(kept.value)
+                raise err
+            _lib.check(rc, "fs_matrix_rows")
+            return int(spans.value), int(kept.value)
+        import torch
+        starts = torch.empty(max(1, int(n_script)) * 4, dtype=torch.uint8, device="cuda")
+        cap = int(n_rows) // max(1, int(ngram)) + 1 if cap is None else int(cap)
+        while True:
+            found = torch.empty(max(1, cap) * abi.MATRIX_NGRAM_DTYPE.itemsize,
+                                dtype=torch.uint8, device="cuda")
+            torch_ready()
+            rc = call(starts.data_ptr(), found.data_ptr(), cap)
+            if rc == abi.FS_E_CAPACITY:
+                cap = int(kept.value)
+                continue
+            _lib.check(rc, "fs_matrix_rows")
+            return (starts[:int(n_script) * 4].cpu().numpy().view(np.uint32), int(spans.value),
+                    found[:kept.value * abi.MATRIX_NGRAM_DTYPE.itemsize].cpu().numpy()
+                    .view(abi.MATRIX_NGRAM_DTYPE))
+
     def groups_device(self, rows_ptr, n_rows, n_works, mem_off, mem_grp, n_groups, label_of=None,
                       n_labels=0, min_words=6, max_gap=0, min_works=1, out_ptrs=None, caps=None):
         """`groups` over device-resident fs_row records sorted by (work, fan_ix) (after a search

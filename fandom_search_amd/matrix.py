@@ -90,6 +90,10 @@ class StrictNgramDedupe(object):
         return ' '.join(m['ORIGINAL_SCRIPT_WORD'].lower() for m in match)
 
     def matrix_rows(self):
+        return self.tables()[0]
+
+    def tables(self):
+        """(the matrix's rows, the start each phrase's column ended up with)."""
         phrase_ix = {}
         works = set()
         cells = collections.defaultdict(int)
@@ -103,11 +107,116 @@ class StrictNgramDedupe(object):
         body = [[cells[(fn, ph)] for ph in phrases] for fn in works]
         totals = [sum(col) for col in zip(*body)] if body else []
         return ([['FILENAME'] + phrases, ['(total)'] + totals]
-                + [[fn] + r for fn, r in zip(works, body)])
+                + [[fn] + r for fn, r in zip(works, body)]), [phrase_ix[ph] for ph in phrases]
 
     def write_match_work_count_matrix(self, out_filename):
-        with open(out_filename, 'w', encoding='utf-8') as op:
-            csv.writer(op).writerows(self.matrix_rows())
+        write_rows(out_filename, self.matrix_rows())
+
+
+def write_rows(out_filename, rows):
+    with open(out_filename, 'w', encoding='utf-8') as op:
+        csv.writer(op).writerows(rows)
+
+
+CELL_FIELDS = ['FILENAME', 'PHRASE_INDEX', 'ORIGINAL_SCRIPT_WORD_INDEX', 'PHRASE', 'COUNT']
+
+
+def cell_rows(rows, starts):
+    """The non-zero cells of the matrix `rows` (its '(total)' row included, as the first rows:
+    the list of the phrases), in row order then column order; PHRASE_INDEX is the 1-based
+    column and starts[column - 1] the script index the column stands at."""
+    phrases = rows[0][1:]
+    out = [CELL_FIELDS]
+    for row in rows[1:]:
+        out.extend([row[0], k + 1, starts[k], phrases[k], c]
+                   for k, c in enumerate(row[1:]) if c)
+    return out
+
+
+def device_tables(data_path, ngram_size, device=0):
+    """StrictNgramDedupe(data_path, ngram_size).tables() with steps 1-5 on HIP device `device`,
+    or None for a file the Python engine has to take: one outside the device reader's grammar
+    or without the header row, a script word spelt in two ways, a '\r' in a text this command
+    shows (StrictNgramDedupe reads with universal newlines, which turn it into '\n'), or more
+    than fs_matrix supports."""
+    import numpy as np
+
+    from . import _lib, abi
+    from .matches import MatchFile
+    from .passages import _ORIG_WORD
+    n = int(ngram_size)
+    with MatchFile(data_path, device) as mf:
+        if mf.outside or not mf.has_header or any('\r' in name for name in mf.names):
+            return None
+        _, work, fan, orig, _, _ = mf.sorted()
+        n_script = int(orig.max()) + 1 if len(orig) else 0
+        try:
+            kept = find_ngrams(work, fan, orig, len(mf.names), n_script, n, device)[2]
+        except _lib.FsError as e:
+            if e.code == abi.FS_E_UNSUPPORTED:
+                return None
+            raise
+        if not len(kept):
+            return [['FILENAME'], ['(total)']], []
+        label = mf.labels(_ORIG_WORD, n_script)
+        if label is None or any('\r' in text for text in label.values()):
+            return None
+        names = mf.names
+    start = kept['start'].astype(np.int64)
+    # a phrase stands at the start of its last n-gram in span order
+    uniq, inv = np.unique(start, return_inverse=True)
+    last = np.zeros(len(uniq), dtype=np.int64)
+    last[inv] = np.arange(len(start))
+    phrase_ix, seen_at = {}, {}
+    text = [' '.join(label[s + k].lower() for k in range(n)) for s in uniq.tolist()]
+    for s, at, phrase in zip(uniq.tolist(), last.tolist(), text):
+        if seen_at.get(phrase, -1) < at:
+            seen_at[phrase], phrase_ix[phrase] = at, s
+    phrases = sorted(phrase_ix, key=phrase_ix.get)
+    column = {phrase: k for k, phrase in enumerate(phrases)}
+    col = np.array([column[phrase] for phrase in text], dtype=np.int64)[inv]
+    # the works by file name, their cells by column
+    works = np.array(sorted(np.unique(kept['work']).tolist(), key=names.__getitem__),
+                     dtype=np.int64)
+    row_of = np.zeros(len(names), dtype=np.int64)
+    row_of[works] = np.arange(len(works))
+    cell, count = np.unique(row_of[kept['work']] * len(phrases) + col, return_counts=True)
+    totals = np.bincount(col, minlength=len(phrases)).tolist()
+    body = [[0] * len(phrases) for _ in range(len(works))]
+    for at, c in zip(cell.tolist(), count.tolist()):
+        body[at // len(phrases)][at % len(phrases)] = c
+    rows = ([['FILENAME'] + phrases, ['(total)'] + totals]
+            + [[names[w]] + r for w, r in zip(works.tolist(), body)])
+    return rows, [phrase_ix[ph] for ph in phrases]
+
+
+def find_ngrams(work, fan_ix, orig_ix, n_works, n_script, ngram, device=0):
+    """(starts[n_script], n_spans, abi.MATRIX_NGRAM_DTYPE kept n-grams in span order) of records
+    sorted by (work, fan_ix): fs_matrix."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib, abi
+    work, fan, orig = (abi.as_u32(v) for v in (work, fan_ix, orig_ix))
+    n = len(work)
+    if not (len(fan) == len(orig) == n):
+        raise ValueError("columns of different lengths")
+    L = _lib.load()
+    starts = np.zeros(int(n_script), dtype=np.uint32)
+    cap = min(n // max(1, int(ngram)) + 1, 4096)
+    while True:
+        found = np.empty(cap, dtype=abi.MATRIX_NGRAM_DTYPE)
+        spans, got = C.c_uint64(0), C.c_uint64(0)
+        rc = L.fs_matrix(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+                         abi.ptr(orig, C.c_uint32), n, int(n_works), int(n_script), int(ngram),
+                         abi.ptr(starts, C.c_uint32), found.ctypes.data_as(C.c_void_p), cap,
+                         C.byref(spans), C.byref(got))
+        if rc == abi.FS_E_CAPACITY:
+            cap = int(got.value)
+            continue
+        _lib.check(rc, "fs_matrix")
+        return starts, int(spans.value), found[:got.value]
 
 
 def matrix_filename(prefix, ngram_size):
@@ -115,9 +224,20 @@ def matrix_filename(prefix, ngram_size):
             .format(prefix, ngram_size))
 
 
+def cells_filename(prefix, ngram_size):
+    return ('{}-most-common-perfect-matches-no-overlap-{}-gram-match-cells.csv'
+            .format(prefix, ngram_size))
+
+
 def process(args):
-    """`ao3.py matrix i m [-n N]`."""
-    dd = StrictNgramDedupe(args.i, ngram_size=args.n)
+    """`ao3.py matrix i m [-n N] [--engine {python,device}] [--device D] [--cells]`."""
+    tables = None
+    if getattr(args, 'engine', 'python') == 'device' and int(args.n) >= 1:
+        tables = device_tables(args.i, args.n, getattr(args, 'device', 0))
+    if tables is None:          # the python engine, or a file the device engine does not take
+        tables = StrictNgramDedupe(args.i, ngram_size=args.n).tables()
     out = matrix_filename(args.m, int(args.n))
-    dd.write_match_work_count_matrix(out)
+    write_rows(out, tables[0])
+    if getattr(args, 'cells', False):
+        write_rows(cells_filename(args.m, int(args.n)), cell_rows(*tables))
     return out

@@ -887,6 +887,60 @@ int fs_transitions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uin
  * tools/transitions_bench.py. */
 int fs_transitions_times(double* ms);
 
+/* `ao3.py matrix --engine device`: the n-grams behind the works x phrases matrix.  Records
+ * sorted by (work, fan_ix), in the order the command takes them (works by first appearance,
+ * stable by fan index).
+ *  - A fan run starts where the work changes or fan_ix is not the previous record's + 1
+ *    (compared without 32-bit wrap): a repeated fan index splits a run.
+ *  - Inside a fan run, c(v) is the number of records that name script word v.  The distinct v
+ *    are walked in ascending order with an open interval: v extends the interval when it ends
+ *    at v - 1, else the interval is closed and [v, v] opened; then, if c(v) >= 2, the interval
+ *    is closed at v, c(v) - 2 single-word spans [v, v] follow, and [v, v] is opened again.
+ *    The closed intervals of at least `ngram` words are the spans.
+ *  - starts[s] is the number of spans [a, b] with a <= s <= b - ngram + 1, over all works.
+ *  - A span's n-gram starts at the first s in a .. b - ngram + 1 with the largest starts[s].  It
+ *    is kept iff starts[s'] < starts[s] for every s' in [s - ngram + 1, s) and starts[s'] <=
+ *    starts[s] for every s' in (s, s + ngram); positions below 0 or from n_script on count 0.
+ *  - out is the kept n-grams in span order: works, then fan runs in record order, then spans
+ *    by ascending first word (equal spans give equal n-grams).
+ * Every value is an integer: no schedule changes a result. */
+typedef struct fs_matrix_ngram {
+  uint32_t work, start;
+} fs_matrix_ngram;                     /* 8 bytes                                                 */
+
+/* Device memory of a call, counted before anything runs: 20 bytes for every slot of the table
+ * of c(v) (the power of two that is at least twice n_rows, and at least 64), 40 bytes a record
+ * (the lists of runs and spans at their largest) and 8 bytes a script word. */
+#define FS_MATRIX_MAX_BYTES (1u << 30)
+
+/* Host columns in; starts[n_script] (or null) and `cap` n-grams out, on HIP device `device`.
+ * Both entry points: FS_E_INVALID for null arguments, ngram == 0, records out of (work, fan_ix)
+ * order, a work >= n_works or a script index >= n_script; FS_E_UNSUPPORTED for n_rows >= 2^32,
+ * n_script > FS_WORKS_MAX_SCRIPT or tables above FS_MATRIX_MAX_BYTES; FS_E_CAPACITY with
+ * *n_kept = n-grams required when cap is smaller (starts and *n_spans are complete then, out
+ * untouched); n_rows / ngram + 1 always suffices.  *n_spans: the spans of at least ngram words.
+ * n_rows == 0: zeros, without device work in fs_matrix.  A span of up to FS_MATRIX_SMALL
+ * (default 32) starts is handled by a lane, a longer one by a wave; FS_MATRIX_HASH_BITS keeps
+ * that many bits of the hash behind the table of c(v) (0: every key collides).  Both are
+ * diagnostics of the environment, read on each call; the output is the same wherever they
+ * stand. */
+int fs_matrix(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t ngram,
+              uint32_t* starts, fs_matrix_ngram* out, uint64_t cap, uint64_t* n_spans,
+              uint64_t* n_kept);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (4-byte
+ * aligned; d_starts may be null), on the index's device and stream; returns when they are
+ * written. */
+int fs_matrix_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   uint32_t n_script, uint32_t ngram, uint32_t* d_starts, fs_matrix_ngram* d_out,
+                   uint64_t cap, uint64_t* n_spans, uint64_t* n_kept);
+/* HIP-event milliseconds of the last fs_matrix / fs_matrix_rows call on this thread: runs
+ * (checks, run heads, the table of c(v)), spans (span ends, spans per run, the difference
+ * array), counter (its running sum), pick (the span list, places, n-grams and their
+ * neighbourhoods), place (the kept n-grams counted and written), and the total of the five; 0
+ * for a pass that did not run.  tools/matrix_bench.py. */
+int fs_matrix_times(double* ms);
+
 /* ---- `ao3.py passages / works / quotes`: the match CSV read on the device ----
  * The twelve-column file `search` writes (csv.writer's defaults, distances by repr), with its
  * header row or without: the bytes in, the non-empty rows out as a field index, the numeric
