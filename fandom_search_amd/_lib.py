@@ -32,7 +32,8 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_debug_stamps",
-           "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_stream_floor",
+           "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_index_lsh_counts",
+           "fs_stream_floor",
            "fs_textenc_create", "fs_textenc_destroy", "fs_textenc_add", "fs_textenc_encode_files",
            "fs_textenc_encode_files_vec",
            "fs_csvw_create", "fs_csvw_destroy", "fs_csvw_set_script", "fs_csvw_add_strings", "fs_csvw_strings",
@@ -298,6 +299,9 @@ def load():
     if hasattr(L, "fs_index_share_counts"):
         L.fs_index_share_counts.restype = C.c_int
         L.fs_index_share_counts.argtypes = [C.c_void_p, u64p]
+    if hasattr(L, "fs_index_lsh_counts"):
+        L.fs_index_lsh_counts.restype = C.c_int
+        L.fs_index_lsh_counts.argtypes = [C.c_void_p, u64p]
     if hasattr(L, "fs_index_share_info"):
         L.fs_index_share_info.restype = C.c_int
         L.fs_index_share_info.argtypes = [C.c_void_p, u32p, u32p, u32p, C.POINTER(C.c_double)]

@@ -100,6 +100,7 @@ WORK_CELL_DTYPE = np.dtype([("work", np.uint32), ("group", np.uint32), ("n_words
                             ("n_exact", np.uint32)])
 assert WORK_CELL_DTYPE.itemsize == 16
 FS_NONE = 0xFFFFFFFF
+FS_LSH_COUNTERS = 24            # fs_index_lsh_counts
 FS_WORKS_MAX_SCRIPT = 1 << 19
 FS_WORKS_MAX_GROUPS = 4096
 

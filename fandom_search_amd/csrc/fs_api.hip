@@ -579,6 +579,17 @@ extern "C" int fs_index_share_counts(fs_index* ix, uint64_t* out8) {
   return FS_OK;
 }
 
+extern "C" int fs_index_lsh_counts(fs_index* ix, uint64_t* out) {
+  if (!ix || !out) return FS_E_INVALID;
+  for (int i = 0; i < FS_LSH_COUNTERS; ++i) out[i] = 0;
+  if (ix->d_lsh_cnt.n < 2 * FS_LSH_COUNTERS) return FS_OK;
+  FS_ENTER(ix->device);
+  FS_HIP(hipDeviceSynchronize());
+  FS_HIP(hipMemcpy(out, ix->d_lsh_cnt.p, FS_LSH_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  FS_HIP(hipMemset(ix->d_lsh_cnt.p, 0, FS_LSH_COUNTERS * sizeof(uint64_t)));
+  return FS_OK;
+}
+
 extern "C" const char* fs_search_kernel_name(fs_index* ix, fs_corpus* c) {
   static thread_local char name[64];
   if (!ix || !c || c->ix != ix || (c->is_view && !c->base)) return "";

@@ -67,6 +67,8 @@ struct LshDev {
   uint32_t V, W;
   int n, H, B, D, C, Cp, nn, unique;
   double thr, cmax;
+  unsigned long long* lsh_cnt;     // diagnostics (FS_LSH_COUNT=1): which branch of the one-slot maps a window took
+                                   // (LshCount below; k_lsh_sift*, k_lsh_enum), or nullptr
 };
 
 // shared by the units, not exported from the library (fs_internal.h's functions are the ones
@@ -85,12 +87,31 @@ FS_LSH_LOCAL int lsh_launch_sift(fs_index* ix, fs_corpus* c, const LshDev& L, ui
 constexpr uint32_t FS_PENDING = 0xFFFFFFFEu;
 // component id of a fan token that counts as agreeing with anything (share_comp, fs_build_share)
 #define FS_WILD 0xFFFFFFFEu
+// The counters behind LshDev::lsh_cnt, in the order fs_index_lsh_counts returns them: windows by
+// the branch they took in sift_stage2 (each window in one of the first eight at most: the reasons
+// to stay pending in the order the code asks them -- a full bucket, more than two n-grams, a
+// distance) and in k_lsh_enum (listed windows by their number of n-grams within the threshold;
+// a window may give up for more than one reason and counts under each).
+enum LshCount {
+  kCntRecordNeighbours = 0, kCntRecordAlone, kCntWmapEnded0, kCntWmapEnded1, kCntWmapEnded2,
+  kCntWmapPendingDistance, kCntWmapPendingMany, kCntWmapPendingFull,
+  kCntEnumListed1, kCntEnumListed2, kCntEnumListed3, kCntEnumListed4, kCntEnumReordered, kCntEnumCut,
+  kCntEnumChainOnce, kCntEnumChainTwice, kCntEnumGiveUpFifth, kCntEnumGiveUpChain, kCntEnumGiveUpTie,
+  kCntLsh                                    // (their number; FS_LSH_COUNTERS of the header holds room for them)
+};
 
 // (an anonymous namespace in a header: every unit gets its own copy, inlined into its kernels,
 // and nothing is exported; a unit uses some of these, not all)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"
 namespace {
+
+// diagnostics: the lanes with `on` (of those that are active here) add to counter `which`, one
+// addition per wave
+__device__ __forceinline__ void lsh_count(unsigned long long* cnt, int which, bool on) {
+  const unsigned long long b = __ballot(on);
+  if (on && (int)(threadIdx.x & 63) == __ffsll(b) - 1) atomicAdd(cnt + which, (unsigned long long)__popcll(b));
+}
 
 // ---- canonical per-token quantities ------------------------------------------
 

@@ -956,7 +956,9 @@ __global__ __launch_bounds__(256) void k_lsh_pkeys(CorpusDev c, LshDev L, const 
   }
 }
 
-template <int N>
+// CNT: with the counters of fs_index_lsh_counts (a form of its own: the kernel without them keeps
+// its registers)
+template <int N, bool CNT>
 __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, GramIndexDev g,
                                                   const uint32_t* __restrict__ cpos, uint32_t cap,
                                                   uint32_t* __restrict__ cg, uint32_t* __restrict__ cw,
@@ -976,6 +978,8 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
     const uint32_t j = j0 + threadIdx.x;
     const bool live = j < n_pend;
     bool give_up = false;
+    bool gu_fifth = false, gu_chain = false, reordered = false, cut = false;   // (for the counters)
+    int deepest = 0;
     uint32_t work = FS_NONE, i = 0;
     uint64_t p = 0;
     if (live) { i = pend[j]; work = pwork[j]; p = cpos[i]; }
@@ -1013,7 +1017,7 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
 #pragma unroll
       for (int x = 0; x < kEnumG; ++x) seen = seen || gl[x] == gid;
       if (seen) return;
-      if (gn >= (uint32_t)kEnumG) { give_up = true; return; }
+      if (gn >= (uint32_t)kEnumG) { give_up = true; if (CNT) gu_fifth = true; return; }
 #pragma unroll
       for (int x = 0; x < kEnumG; ++x) gl[x] = gn == (uint32_t)x ? gid : gl[x];
       ++gn;
@@ -1039,8 +1043,9 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
 #pragma unroll
             for (int e = 0; e < 4; ++e)
               if (val[e] && key[e] == h && ok) add_gram(val[e] - 1);
+            if (CNT) deepest = max(deepest, probe);               // (the chain's buckets read behind the first)
             if (!val[3] || !ok) break;            // (not full: nothing has spilt past it)
-            if (probe == 2) { give_up = true; break; }
+            if (probe == 2) { give_up = true; if (CNT) gu_chain = true; break; }
             bkt = (bkt + 1) & ((1u << L.log2_emap) - 1u);
             const uint4* bp = reinterpret_cast<const uint4*>(L.emap + 4 * (size_t)bkt);
             a = bp[0]; b = bp[1];
@@ -1120,6 +1125,7 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
     // would interleave by arrival: left to the bucket walk.
     auto cswap = [&](int a, int b) {
       const bool sw2 = (gt[b] != 0 && (gt[a] == 0 || gd[b] < gd[a]));
+      if (CNT) reordered = reordered || (sw2 && gt[a] != 0);
       const double da = gd[a], db = gd[b];
       const uint32_t ta = gt[a], tb2 = gt[b], ga = gl[a], gb = gl[b];
       gd[a] = sw2 ? db : da; gd[b] = sw2 ? da : db;
@@ -1128,14 +1134,16 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
     };
     static_assert(kEnumG == 4, "a sorting network of four");
     cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
+    bool tie = false;
 #pragma unroll
     for (int x = 0; x + 1 < kEnumG; ++x)
-      if (gt[x] && gt[x + 1] && gd[x] == gd[x + 1]) give_up = true;
+      if (gt[x] && gt[x + 1] && gd[x] == gd[x + 1]) { give_up = true; if (CNT) tie = true; }
     uint32_t made = 0;
     if (ok && !give_up) {
       const size_t jj = (size_t)j * nn;
 #pragma unroll
       for (int x = 0; x < kEnumG; ++x) {
+        if (CNT && gt[x] && made >= nn) cut = true;
         if (!gt[x] || made >= nn) continue;
         const uint32_t gid = gl[x], occ = g.gcnt[gid];
         uint32_t o[kEnumNN];
@@ -1153,7 +1161,25 @@ __global__ __launch_bounds__(256, 4) void k_lsh_enum(CorpusDev c, LshDev L, Gram
             ++made;
             if (++r == occ) { r = 0; tb &= tb - 1; }
           }
+        if (CNT && tb) cut = true;                // (entries of this n-gram beyond the N kept)
       }
+    }
+    if (CNT) {                                    // diagnostics (fs_index_lsh_counts)
+      const bool listed = ok && !give_up;
+      uint32_t within = 0;
+#pragma unroll
+      for (int x = 0; x < kEnumG; ++x) within += gt[x] ? 1u : 0u;
+      lsh_count(L.lsh_cnt, kCntEnumListed1, listed && within == 1);
+      lsh_count(L.lsh_cnt, kCntEnumListed2, listed && within == 2);
+      lsh_count(L.lsh_cnt, kCntEnumListed3, listed && within == 3);
+      lsh_count(L.lsh_cnt, kCntEnumListed4, listed && within == 4);
+      lsh_count(L.lsh_cnt, kCntEnumReordered, listed && reordered);
+      lsh_count(L.lsh_cnt, kCntEnumCut, listed && cut);
+      lsh_count(L.lsh_cnt, kCntEnumChainOnce, ok && !gu_chain && deepest == 1);
+      lsh_count(L.lsh_cnt, kCntEnumChainTwice, ok && !gu_chain && deepest == 2);
+      lsh_count(L.lsh_cnt, kCntEnumGiveUpFifth, ok && gu_fifth);
+      lsh_count(L.lsh_cnt, kCntEnumGiveUpChain, ok && gu_chain);
+      lsh_count(L.lsh_cnt, kCntEnumGiveUpTie, ok && tie);
     }
     if (live && !give_up) {
       mcnt[j] = made;
@@ -1372,7 +1398,8 @@ static int lsh_launch_pending(fs_index* ix, fs_corpus* c, const LshDev& L, uint3
   EnumFn enumk = nullptr;
   if (defer && ix->sw.lsh_batch && L.H <= kBatchH && L.nn <= 48 && !L.serial_neighbours && !(L.diag & 0xFFFF))
     switch (L.n) {
-#define FS_B(N) case N: batch = k_lsh_batch<N>; pkeys = k_lsh_pkeys<N>; enumk = k_lsh_enum<N>; break
+#define FS_B(N) case N: batch = k_lsh_batch<N>; pkeys = k_lsh_pkeys<N>; \
+                        enumk = L.lsh_cnt ? k_lsh_enum<N, true> : k_lsh_enum<N, false>; break
       FS_B(6); FS_B(7); FS_B(8); FS_B(9); FS_B(10); FS_B(12);
 #undef FS_B
       default: break;

@@ -307,6 +307,7 @@ LshDev lsh_dev(const fs_index* ix) {
   L.ss = ix->d_ss.p; L.sw = ix->d_sw.p; L.q = ix->d_q.p; L.emb = ix->d_emb.p; L.stok = ix->d_stok.p;
   L.gtab = ix->d_gtab.n > 1 ? ix->d_gtab.p : nullptr; L.sidx = ix->d_sidx.p;
   L.spos = ix->d_spos.n > 1 ? ix->d_spos.p : nullptr;
+  L.lsh_cnt = ix->d_lsh_cnt.n > 1 ? reinterpret_cast<unsigned long long*>(ix->d_lsh_cnt.p) : nullptr;
   L.share_cnt = nullptr; L.oovmap = nullptr; L.log2_oovmap = 0; L.compa = nullptr; L.ssig = nullptr; L.sharef = nullptr; L.smap = nullptr; L.slists = nullptr; L.log2_smap = 0; L.log2_sharef = 0; L.share_flags = 0;
   L.share_lim = 0.0f; L.share_scale = 0.0; L.share_phi = 1.0; L.share_tau = 0.0; L.share_gamma = 1.0;
   if (ix->share_flags) {
@@ -945,6 +946,11 @@ int fs_lsh_build(fs_index* ix) {
                        ix->d_bids.p, d_big.p + 1, n_big, d_tmp.p);
     FS_HIP(hipGetLastError());
     FS_HIP(hipStreamSynchronize(s));           // the scratch buffers die with this scope
+  }
+  static_assert(kCntLsh <= FS_LSH_COUNTERS, "fs_index_lsh_counts returns every counter");
+  if (getenv("FS_LSH_COUNT")) {
+    FS_TRY(ix->d_lsh_cnt.reserve(2 * FS_LSH_COUNTERS));
+    FS_HIP(hipMemsetAsync(ix->d_lsh_cnt.p, 0, FS_LSH_COUNTERS * sizeof(uint64_t), s));
   }
   FS_HIP(hipStreamSynchronize(s));
   ix->lsh_ready = true;

@@ -105,7 +105,9 @@ struct SiftOut {
   uint32_t* pend; uint32_t* pend_cnt;
   uint32_t* s_pn; uint32_t* s_pbase;          // LDS words of the workgroup
 };
-template <int NW, bool WMAP>
+// CNT: with the counters of fs_index_lsh_counts (a form of its own: the kernels without them keep
+// their registers)
+template <int NW, bool WMAP, bool CNT>
 __device__ __forceinline__ void sift_stage2(const CorpusDev& c, const LshDev& L, const GramIndexDev& g,
                                             const SiftOut& o, uint32_t il, uint64_t p_in, uint32_t* matches_io) {
   const int lane = threadIdx.x & 63;
@@ -133,6 +135,10 @@ __device__ __forceinline__ void sift_stage2(const CorpusDev& c, const LshDev& L,
         cg[il] = 0;
         cw[il] = w;
         matches += have - 1;
+      }
+      if (CNT) {                                      // diagnostics (fs_index_lsh_counts)
+        lsh_count(L.lsh_cnt, kCntRecordNeighbours, have != 1);
+        lsh_count(L.lsh_cnt, kCntRecordAlone, have == 1);
       }
       live = false;
     }
@@ -167,11 +173,20 @@ __device__ __forceinline__ void sift_stage2(const CorpusDev& c, const LshDev& L,
           }
         possible = possible || val[3] != 0;       // (filled in order: the bucket is full)
       }
+    const bool full = possible;
     possible = possible || nh > 2;
     if (L.diag & 512) possible = possible || nh > 0;                 // diagnostics: no distances here
     if (!possible && nh > 0) possible = one_slot_within<NW>(L, s0, k0, f);
     if (!possible && nh > 1) possible = one_slot_within<NW>(L, s1, k1, f);
     if (!possible) { cg[il] = FS_NONE; live = false; }
+    if (CNT) {                                                       // diagnostics (fs_index_lsh_counts)
+      lsh_count(L.lsh_cnt, kCntWmapPendingFull, full);
+      lsh_count(L.lsh_cnt, kCntWmapPendingMany, !full && nh > 2);
+      lsh_count(L.lsh_cnt, kCntWmapPendingDistance, !full && nh <= 2 && possible);
+      lsh_count(L.lsh_cnt, kCntWmapEnded0, !possible && nh == 0);
+      lsh_count(L.lsh_cnt, kCntWmapEnded1, !possible && nh == 1);
+      lsh_count(L.lsh_cnt, kCntWmapEnded2, !possible && nh == 2);
+    }
   }
   // what is left: onto the list k_lsh_verify deals out window by window (pending windows
   // come in runs, the boundary windows of one quoted passage, so dealing out blocks of
@@ -195,7 +210,7 @@ __device__ __forceinline__ void sift_stage2(const CorpusDev& c, const LshDev& L,
   }
 }
 
-template <int NW, bool WMAP, int NN>
+template <int NW, bool WMAP, int NN, bool CNT>
 __global__ __launch_bounds__(256, 5) void k_lsh_sift(CorpusDev c, LshDev L, GramIndexDev g,
                                                   const uint32_t* __restrict__ cpos, NSrc nc,
                                                   uint32_t* __restrict__ cg, uint32_t* __restrict__ cw,
@@ -220,7 +235,7 @@ __global__ __launch_bounds__(256, 5) void k_lsh_sift(CorpusDev c, LshDev L, Gram
   // stage 2 for one queued candidate (FS_NONE: none); every thread of the workgroup calls it
   const SiftOut so{cg, cw, cbest, tab_best, tab_cnt, pend, pend_cnt, &s_pn, &s_pbase};
   auto stage2 = [&](uint32_t il) {
-    sift_stage2<NW, WMAP>(c, L, g, so, il, il != FS_NONE ? (uint64_t)cpos[il] : 0ull, &matches);
+    sift_stage2<NW, WMAP, CNT>(c, L, g, so, il, il != FS_NONE ? (uint64_t)cpos[il] : 0ull, &matches);
   };
   // U candidates per lane and pass, their loads level by level: positions, ids, filter blocks
   constexpr int U = NW <= 8 ? 3 : 2;
@@ -340,7 +355,7 @@ __global__ __launch_bounds__(256, 5) void k_lsh_sift(CorpusDev c, LshDev L, Gram
 // chunk sums' prefix, which each workgroup makes for itself in LDS): one pass of full waves.
 // (A workgroup per chunk measured 45 us at n = 8 and 67 at n = 10: a C2 batch leaves 70 to 100
 // survivors per chunk, so the deep steps ran at a third of the lanes, twice over.)
-template <int NW, bool WMAP>
+template <int NW, bool WMAP, bool CNT>
 __global__ __launch_bounds__(256, 5) void k_lsh_sift2(CorpusDev c, LshDev L, GramIndexDev g,
                                                    const uint32_t* __restrict__ slist, uint32_t caps,
                                                    const uint32_t* __restrict__ scount,
@@ -397,7 +412,7 @@ __global__ __launch_bounds__(256, 5) void k_lsh_sift2(CorpusDev c, LshDev L, Gra
       p = slist[(size_t)(4 * a + r) * caps + off];
       cpos[il] = p;
     }
-    sift_stage2<NW, WMAP>(c, L, g, so, live ? il : FS_NONE, p, &matches);
+    sift_stage2<NW, WMAP, CNT>(c, L, g, so, live ? il : FS_NONE, p, &matches);
   }
   if (blockIdx.x == 0) {                              // for the kernels behind and the host
     uint32_t over = 0;
@@ -411,6 +426,26 @@ __global__ __launch_bounds__(256, 5) void k_lsh_sift2(CorpusDev c, LshDev L, Gra
     bmatch[blockIdx.x] = tot;
     for (uint32_t b = blockIdx.x + gridDim.x; b < (uint32_t)kNB; b += gridDim.x) bmatch[b] = 0;
   }
+}
+
+// the kernels for this index: its window size, with or without the exact one-slot map, with the
+// counters where the index has them
+template <bool CNT>
+auto sift_kernel(const LshDev& L) -> decltype(&k_lsh_sift<8, true, 0, CNT>) {
+  auto sift = L.n <= 8 ? (L.wmap ? k_lsh_sift<8, true, 0, CNT> : k_lsh_sift<8, false, 0, CNT>)
+                       : (L.wmap ? k_lsh_sift<FS_MAX_WINDOW, true, 0, CNT> : k_lsh_sift<FS_MAX_WINDOW, false, 0, CNT>);
+  switch (L.n) {            // the common window sizes with their size at compile time
+    case 6: sift = L.wmap ? k_lsh_sift<8, true, 6, CNT> : k_lsh_sift<8, false, 6, CNT>; break;
+    case 8: sift = L.wmap ? k_lsh_sift<8, true, 8, CNT> : k_lsh_sift<8, false, 8, CNT>; break;
+    case 10: sift = L.wmap ? k_lsh_sift<FS_MAX_WINDOW, true, 10, CNT> : k_lsh_sift<FS_MAX_WINDOW, false, 10, CNT>; break;
+    default: break;
+  }
+  return sift;
+}
+template <bool CNT>
+auto sift2_kernel(const LshDev& L) -> decltype(&k_lsh_sift2<8, true, CNT>) {
+  return L.n <= 8 ? (L.wmap ? k_lsh_sift2<8, true, CNT> : k_lsh_sift2<8, false, CNT>)
+                  : (L.wmap ? k_lsh_sift2<FS_MAX_WINDOW, true, CNT> : k_lsh_sift2<FS_MAX_WINDOW, false, CNT>);
 }
 
 }  // namespace
@@ -428,17 +463,9 @@ int lsh_launch_sift(fs_index* ix, fs_corpus* c, const LshDev& L, uint32_t ccap, 
     tab_best = c->d_gramtab_best.p;
     tab_cnt = c->d_gramtab_cnt.p;
   }
-  auto sift = L.n <= 8 ? (L.wmap ? k_lsh_sift<8, true, 0> : k_lsh_sift<8, false, 0>)
-                       : (L.wmap ? k_lsh_sift<FS_MAX_WINDOW, true, 0> : k_lsh_sift<FS_MAX_WINDOW, false, 0>);
-  switch (L.n) {            // the common window sizes with their size at compile time
-    case 6: sift = L.wmap ? k_lsh_sift<8, true, 6> : k_lsh_sift<8, false, 6>; break;
-    case 8: sift = L.wmap ? k_lsh_sift<8, true, 8> : k_lsh_sift<8, false, 8>; break;
-    case 10: sift = L.wmap ? k_lsh_sift<FS_MAX_WINDOW, true, 10> : k_lsh_sift<FS_MAX_WINDOW, false, 10>; break;
-    default: break;
-  }
+  const auto sift = L.lsh_cnt ? sift_kernel<true>(L) : sift_kernel<false>(L);
   if (near) {
-    auto sift2 = L.n <= 8 ? (L.wmap ? k_lsh_sift2<8, true> : k_lsh_sift2<8, false>)
-                          : (L.wmap ? k_lsh_sift2<FS_MAX_WINDOW, true> : k_lsh_sift2<FS_MAX_WINDOW, false>);
+    const auto sift2 = L.lsh_cnt ? sift2_kernel<true>(L) : sift2_kernel<false>(L);
     const uint32_t blocks = lsh_resident_blocks(ix, reinterpret_cast<const void*>(sift2));
     hipLaunchKernelGGL(sift2, dim3(blocks), dim3(256), 0, s, c->dev(), L, ix->gram_dev(),
                        near->slist, near->caps, near->scount, ix->cur->w_bsum.p,

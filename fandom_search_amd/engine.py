@@ -342,6 +342,20 @@ class ScriptIndex(object):
                  "windows_flagged", "windows_flagged_as_they_are")
         return {k: int(out[i]) for i, k in enumerate(names)}
 
+    LSH_COUNT_NAMES = (
+        "record_with_neighbours", "record_alone", "wmap_ended_0", "wmap_ended_1", "wmap_ended_2",
+        "wmap_pending_distance", "wmap_pending_many", "wmap_pending_full_bucket",
+        "enum_listed_1", "enum_listed_2", "enum_listed_3", "enum_listed_4", "enum_reordered", "enum_cut",
+        "enum_chain_once", "enum_chain_twice", "enum_giveup_fifth", "enum_giveup_chain", "enum_giveup_tie")
+
+    def lsh_counts(self):
+        """Diagnostics (FS_LSH_COUNT=1 when the index was built): windows by the branch they took in
+        the kernels that read the one-slot maps (second stage of k_lsh_sift / k_lsh_sift2, k_lsh_enum)
+        since the last call -- fs_index_lsh_counts."""
+        out = (C.c_uint64 * abi.FS_LSH_COUNTERS)()
+        _lib.check(_lib.load().fs_index_lsh_counts(self._h, out), "fs_index_lsh_counts")
+        return {k: int(out[i]) for i, k in enumerate(self.LSH_COUNT_NAMES)}
+
     def profile(self, corpus, rows_ptr, cap):
         """Diagnostics: one search of `corpus` (records to the device buffer at `rows_ptr`)
         with a HIP event behind each of its kernels; returns [(kernel name, ms), ...] in

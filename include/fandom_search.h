@@ -1107,6 +1107,22 @@ int fs_index_share_info(const fs_index* ix, uint32_t* flags, uint32_t* component
  * constraint, or no room), 0.  All zero when the counters are off or the rule is not in use. */
 int fs_index_share_counts(fs_index* ix, uint64_t* out8);
 
+/* Diagnostics: with FS_LSH_COUNT=1 in the environment when the index is built, the kernels that read
+ * the one-slot maps count the windows by the branch they took; this reads the FS_LSH_COUNTERS
+ * counters into out[] and sets them to zero.  Second stage of k_lsh_sift / k_lsh_sift2, a window in
+ * one of these at most: [0] has the ids of a script n-gram and took that n-gram's record (its kept
+ * matches, the n-gram itself among them), [1] has them and the n-gram keeps no match; ended by the exact one-slot map with [2] no, [3] one, [4] two script n-grams one
+ * slot away; kept pending [5] by a distance within the threshold, [6] by more than two such
+ * n-grams, [7] by a full bucket (asked first).  k_lsh_enum: [8]..[11] windows listed with one to
+ * four n-grams within the threshold, [12] listed after the sort exchanged two of them, [13] listed
+ * with the list cut at nearest_n (entries of the kept occurrences: the index keeps an n-gram's first
+ * nearest_n); [14] / [15] windows that read one / two buckets of a chain behind
+ * a full one and found its end; windows given up to the bucket walk [16] by a fifth n-gram, [17] by
+ * a chain still full at its third bucket, [18] by two n-grams at the same distance (a window
+ * counts under every reason it has).  The rest 0; all 0 when the counters are off. */
+#define FS_LSH_COUNTERS 24
+int fs_index_lsh_counts(fs_index* ix, uint64_t* out);
+
 /* Diagnostics: one synchronous search of `c` (arguments as fs_search_corpus) with a HIP event
  * behind every kernel of it.  names: the kernels' names in launch order, '\n'-separated;
  * ms[i]: time from the previous mark to the one behind kernel i (its duration when nothing else
