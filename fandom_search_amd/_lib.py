@@ -27,6 +27,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_companions", "fs_companions_rows", "fs_companions_times",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
+           "fs_sources", "fs_sources_times",
            "fs_matrix", "fs_matrix_rows", "fs_matrix_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
@@ -215,6 +216,12 @@ def load():
                                       u64p]
     L.fs_transitions_times.restype = C.c_int
     L.fs_transitions_times.argtypes = [C.POINTER(C.c_double)]
+    L.fs_sources.restype = C.c_int
+    L.fs_sources.argtypes = [C.c_int, C.POINTER(abi.FsSourceCols), C.c_uint32, C.c_uint32,
+                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p,
+                             C.c_uint64, u64p, C.c_void_p, C.c_void_p]
+    L.fs_sources_times.restype = C.c_int
+    L.fs_sources_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_clusters.restype = C.c_int
     L.fs_clusters.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -153,6 +153,49 @@ assert TRANSITION_DTYPE.itemsize == 32
 FS_TRANSITIONS_DENSE = 64
 TRANSITIONS_MS_NAMES = ("sequence", "count", "keep", "place", "total")
 
+
+# fs_source_cols: 40 bytes; fs_source_passage: 80; fs_source_work: 56; fs_source_script and
+# fs_source_pair: 48 each
+class FsSourceCols(C.Structure):
+    _fields_ = [("work", C.POINTER(C.c_uint32)),
+                ("fan_ix", C.POINTER(C.c_uint32)),
+                ("orig_ix", C.POINTER(C.c_uint32)),
+                ("comb", C.POINTER(C.c_double)),
+                ("n", C.c_uint64)]
+
+
+assert C.sizeof(FsSourceCols) == 40
+SOURCE_PASSAGE_DTYPE = np.dtype([("script", np.uint32), ("work", np.uint32),
+                                 ("first", np.uint32), ("n_words", np.uint32),
+                                 ("n_exact", np.uint32), ("fan_first", np.uint32),
+                                 ("fan_last", np.uint32), ("orig_first", np.uint32),
+                                 ("orig_last", np.uint32), ("rivals", np.uint32),
+                                 ("rival_scripts", np.uint32), ("outcome", np.uint32),
+                                 ("best_rival", np.uint32), ("best_rival_words", np.uint32),
+                                 ("best_rival_fan_first", np.uint32), ("reserved", np.uint32),
+                                 ("contested_words", np.uint64), ("sole_words", np.uint64)])
+assert SOURCE_PASSAGE_DTYPE.itemsize == 80
+SOURCE_WORK_DTYPE = np.dtype([("work", np.uint32), ("script", np.uint32),
+                              ("passages", np.uint32), ("alone", np.uint32), ("won", np.uint32),
+                              ("lost", np.uint32), ("work_scripts", np.uint32),
+                              ("primary", np.uint32), ("covered_words", np.uint64),
+                              ("contested_words", np.uint64), ("sole_words", np.uint64)])
+assert SOURCE_WORK_DTYPE.itemsize == 56
+SOURCE_SCRIPT_DTYPE = np.dtype([("works", np.uint32), ("passages", np.uint32),
+                                ("alone", np.uint32), ("won", np.uint32), ("lost", np.uint32),
+                                ("primary_works", np.uint32), ("covered_words", np.uint64),
+                                ("contested_words", np.uint64), ("sole_words", np.uint64)])
+assert SOURCE_SCRIPT_DTYPE.itemsize == 48
+SOURCE_PAIR_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("works_both", np.uint32),
+                              ("reserved", np.uint32), ("contests", np.uint64),
+                              ("shared_words", np.uint64), ("a_wins", np.uint64),
+                              ("b_wins", np.uint64)])
+assert SOURCE_PAIR_DTYPE.itemsize == 48
+FS_SOURCES_MAX_FILES = 64
+FS_SOURCES_MAX_BYTES = 1 << 30
+FS_SOURCE_ALONE, FS_SOURCE_WON, FS_SOURCE_LOST = 0, 1, 2
+SOURCES_MS_NAMES = ("passages", "contest", "union", "rollups", "total")
+
 # fs_cluster_work: 32 bytes; fs_cluster: 48 bytes
 CLUSTER_WORK_DTYPE = np.dtype([("covered", np.uint32), ("root", np.uint32), ("size", np.uint32),
                                ("cluster", np.uint32), ("links", np.uint32), ("best", np.uint32),

@@ -14,7 +14,9 @@ quoted stretch (fandom_search_amd/readings.py), and `retellings`, which lists th
 quote the script in the script's own order (fandom_search_amd/retellings.py), and `companions`,
 which relates the quoted stretches of the script by the works quoting both
 (fandom_search_amd/companions.py), and `transitions`, which counts which stretch the works
-quote next after each stretch (fandom_search_amd/transitions.py).  The
+quote next after each stretch (fandom_search_amd/transitions.py), and `sources`, which joins
+the match files of several scripts and says which script each fan passage quotes
+(fandom_search_amd/sources.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -35,7 +37,7 @@ def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
                     '(MI355X build of the `ao3.py search` path).')
-    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings, companions, transitions or validate')
+    subparsers = parser.add_subparsers(help='search, format, matrix, passages, works, quotes, variants, pairs, groups, clusters, readings, retellings, companions, transitions, sources or validate')
 
     validate_parser = subparsers.add_parser('validate', help='validate script markup')
     validate_parser.add_argument('script', action='store',
@@ -411,6 +413,32 @@ def build_parser():
                                     help='who reads the match csv: the GPU (default) or '
                                          'csv.reader; also FANDOM_SEARCH_READER')
     transitions_parser.set_defaults(func=_transitions)
+
+    sources_parser = subparsers.add_parser(
+        'sources', help='joins the match files of one corpus searched against several scripts: '
+                        'which script each fan passage quotes, where passages of different '
+                        'scripts lie on the same fan words and which of them wins')
+    sources_parser.add_argument('matches', action='store', nargs='+', metavar='matches',
+                                help='filenames for search output (dated or batch files), one '
+                                     'per script, at least two')
+    sources_parser.add_argument('-o', '--output', action='store', required=True,
+                                help='prefix of the four csv files, PREFIX-sources.csv, '
+                                     'PREFIX-sources-works.csv, PREFIX-sources-scripts.csv and '
+                                     'PREFIX-sources-pairs.csv')
+    sources_parser.add_argument('--names', default=None,
+                                help="the scripts' names, comma-separated, one per file "
+                                     "(default: the files' parent directories when they "
+                                     'differ, else the file names without .csv)')
+    sources_parser.add_argument('--min-words', default=6, type=int,
+                                help='fewest matched words a passage has, default 6')
+    sources_parser.add_argument('--max-gap', default=0, type=int,
+                                help='words without a record a passage may step over on each '
+                                     'side at once, default 0')
+    sources_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    sources_parser.add_argument('--reader', default=None, choices=('device', 'python'),
+                                help='who reads the match csvs: the GPU (default) or '
+                                     'csv.reader; also FANDOM_SEARCH_READER')
+    sources_parser.set_defaults(func=_sources)
     return parser
 
 
@@ -574,6 +602,16 @@ def _transitions(args):
         return transitions.process(args)
     except ValueError as e:
         sys.exit('ao3.py transitions: error: %s' % e)
+
+
+def _sources(args):
+    from . import sources
+    if args.min_words < 1 or args.max_gap < 0:
+        sys.exit('ao3.py sources: error: --min-words must be at least 1, --max-gap at least 0')
+    try:
+        return sources.process(args)
+    except ValueError as e:
+        sys.exit('ao3.py sources: error: %s' % e)
 
 
 def main(argv=None):

@@ -26,6 +26,23 @@ __device__ inline T wave_max(T v) {
   return v;
 }
 
+// the same inside every aligned segment of `width` lanes (a power of two up to 64, the same in
+// every lane of the wave)
+template <class T>
+__device__ inline T seg_sum(T v, uint32_t width) {
+  for (uint32_t d = width >> 1; d; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+template <class T>
+__device__ inline T seg_max(T v, uint32_t width) {
+  for (uint32_t d = width >> 1; d; d >>= 1) {
+    const T o = __shfl_xor(v, d);
+    if (o > v) v = o;
+  }
+  return v;
+}
+
 // inclusive scan in lane order
 template <class T>
 __device__ inline T wave_scan(T v) {

@@ -887,6 +887,113 @@ int fs_transitions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uin
  * tools/transitions_bench.py. */
 int fs_transitions_times(double* ms);
 
+/* `ao3.py sources`: which script each fan passage quotes, the join of K searches of one corpus
+ * against K scripts.  File s (script s, 0-based) is the records of one search as columns sorted
+ * by (work, fan_ix), the work numbers shared by all files; its passages are those of
+ * fs_passages under the same min_words and max_gap.  Passage p has a script s(p), a work, the fan
+ * span [fan_first, fan_last] and the script span [orig_first, orig_last] of its first and last
+ * record; its span length is fan_last - fan_first + 1 in 64 bits.
+ *  - q is a rival of p when s(q) != s(p), both are of one work, and q.fan_first <= p.fan_last
+ *    and p.fan_first <= q.fan_last (one common word is enough; adjacent spans are no rivals).
+ *    overlap(p, q) is the length of the intersection.
+ *  - key(p) = (n_words, n_exact, -script), a total order across scripts.  p is alone
+ *    (FS_SOURCE_ALONE) without a rival, won (FS_SOURCE_WON) when key(p) > key(q) for every rival
+ *    q, lost (FS_SOURCE_LOST) otherwise: a local maximum, so a passage that loses to a passage
+ *    which lost itself is still lost.
+ *  - The best rival is the rival with the largest (n_words, n_exact, -script, -fan_first,
+ *    -first).
+ *  - contested_words is the number of fan words of p's span inside at least one rival's span (a
+ *    union: a word two rivals cover counts once); sole_words is the span length less that.
+ *  - A (work, script) row exists where the script has a passage in the work; primary is 1 for
+ *    the script with the most covered_words (the sum of span lengths) in the work, the smaller
+ *    script on a tie.
+ *  - Pair (a, b), a < b: the rival pairs (p of a, q of b) are its contests, shared_words the sum
+ *    of their overlaps, a_wins those with key(p) > key(q), b_wins the rest.  Two passages of one
+ *    file that touch in a word (a file with two records at one fan index) both meet a rival
+ *    that covers it: pair sums count that word twice, contested_words once.
+ * Every value is an integer; adds and maxima commute, ties are settled by total orders and
+ * places come from counts, so no schedule changes the result. */
+#define FS_SOURCES_MAX_FILES 64u
+#define FS_SOURCES_MAX_BYTES (1ull << 30)
+#define FS_SOURCE_ALONE 0u
+#define FS_SOURCE_WON 1u
+#define FS_SOURCE_LOST 2u
+
+typedef struct fs_source_cols {
+  const uint32_t* work;      /* [n] each, sorted by (work, fan_ix)                        */
+  const uint32_t* fan_ix;
+  const uint32_t* orig_ix;
+  const double* comb;
+  uint64_t n;
+} fs_source_cols;            /* 40 bytes                                                  */
+
+typedef struct fs_source_passage {
+  uint32_t script, work;
+  uint32_t first;            /* index of its first record in its file's columns           */
+  uint32_t n_words, n_exact; /* as in fs_passage                                          */
+  uint32_t fan_first, fan_last, orig_first, orig_last;
+  uint32_t rivals;           /* rival passages                                            */
+  uint32_t rival_scripts;    /* distinct scripts among them                               */
+  uint32_t outcome;          /* FS_SOURCE_ALONE / _WON / _LOST                            */
+  uint32_t best_rival;       /* its script; 0xFFFFFFFF when alone                         */
+  uint32_t best_rival_words; /* its n_words and fan_first; 0 when alone                   */
+  uint32_t best_rival_fan_first;
+  uint32_t reserved;         /* 0                                                         */
+  uint64_t contested_words, sole_words;
+} fs_source_passage;         /* 80 bytes                                                  */
+
+typedef struct fs_source_work {
+  uint32_t work, script;
+  uint32_t passages, alone, won, lost;
+  uint32_t work_scripts;     /* scripts with a passage in this work                       */
+  uint32_t primary;          /* 1: the script with the most covered_words in the work     */
+  uint64_t covered_words, contested_words, sole_words;
+} fs_source_work;            /* 56 bytes                                                  */
+
+typedef struct fs_source_script {
+  uint32_t works, passages, alone, won, lost, primary_works;
+  uint64_t covered_words, contested_words, sole_words;
+} fs_source_script;          /* 48 bytes                                                  */
+
+typedef struct fs_source_pair {
+  uint32_t a, b;             /* a < b                                                     */
+  uint32_t works_both;       /* works with a passage of each                              */
+  uint32_t reserved;         /* 0                                                         */
+  uint64_t contests, shared_words, a_wins, b_wins;
+} fs_source_pair;            /* 48 bytes                                                  */
+
+/* Host columns of n_files files in; out, on HIP device `device`: the passages of all files in
+ * (work, fan_first, script, first) order, the (work, script) rows in (work, script) order,
+ * scripts[n_files] and pairs[n_files (n_files - 1) / 2] in (a, b) order ((0, 1), (0, 2) ...).
+ * FS_E_INVALID for null arguments, n_files == 0, min_words == 0, records out of (work, fan_ix)
+ * order or a work >= n_works; FS_E_UNSUPPORTED, before anything is read, for n_files >
+ * FS_SOURCES_MAX_FILES or a file of 2^32 records or more, and for device memory above
+ * FS_SOURCES_MAX_BYTES, which counts 28 bytes per record of the largest file and 12 per work
+ * (refused before anything is read), then 160 bytes per passage and 56 per (work, script) row.
+ * FS_E_CAPACITY with *n_passages and *n_work_rows = the counts required when either cap is
+ * smaller: scripts and pairs are complete then, passages and works untouched.  Files are read
+ * one after the other; a file without records has no passages.
+ * Diagnostics of the environment, read on each call; the output is the same wherever they
+ * stand:
+ *   FS_SOURCES_PACK   1 (default): a wave takes 64 / K2 passages in the contest pass, K2 the
+ *                     power of two at or above n_files; 0: one passage per wave
+ *   FS_SOURCES_UNION  0 (default): contested_words of a passage with rivals of one script is
+ *                     that script's overlaps, only passages with rivals of two or more scripts
+ *                     take the union pass; 1: every contested passage takes it
+ *   FS_SOURCES_DENSE  n_files up to which a workgroup of the contest pass keeps the pair
+ *                     figures in LDS (default and most 64; 0: every figure a global atomic) */
+int fs_sources(int device, const fs_source_cols* files, uint32_t n_files, uint32_t n_works,
+               uint32_t min_words, uint32_t max_gap, fs_source_passage* passages,
+               uint64_t cap_passages, uint64_t* n_passages, fs_source_work* works,
+               uint64_t cap_works, uint64_t* n_work_rows, fs_source_script* scripts,
+               fs_source_pair* pairs);
+/* HIP-event milliseconds of the last fs_sources call on this thread: passages (every file's
+ * uploads, checks, run heads and passage columns), contest (rivals, outcomes, places, pair
+ * figures), union (contested words of the passages that need the union pass), rollups (rows,
+ * scripts, pairs), and the total of the four; 0 for a pass that did not run.
+ * tools/sources_bench.py. */
+int fs_sources_times(double* ms);
+
 /* `ao3.py matrix --engine device`: the n-grams behind the works x phrases matrix.  Records
  * sorted by (work, fan_ix), in the order the command takes them (works by first appearance,
  * stable by fan index).
