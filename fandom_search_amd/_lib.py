@@ -44,6 +44,11 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_matches_parse_double")
 
 
+# the commands with an fs_<name>_times(double *ms) beside their entry points
+TIMED = ("readings", "retellings", "pairs", "companions", "transitions", "sources", "matrix",
+         "clusters", "groups")
+
+
 class FsError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -193,8 +198,6 @@ def load():
     L.fs_pairs_rows.restype = C.c_int
     L.fs_pairs_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
-    L.fs_pairs_times.restype = C.c_int
-    L.fs_pairs_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_companions.restype = C.c_int
     L.fs_companions.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -203,8 +206,6 @@ def load():
     L.fs_companions_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_void_p, C.c_uint64, u64p]
-    L.fs_companions_times.restype = C.c_int
-    L.fs_companions_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_transitions.restype = C.c_int
     L.fs_transitions.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -214,14 +215,10 @@ def load():
                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                       u64p]
-    L.fs_transitions_times.restype = C.c_int
-    L.fs_transitions_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_sources.restype = C.c_int
     L.fs_sources.argtypes = [C.c_int, C.POINTER(abi.FsSourceCols), C.c_uint32, C.c_uint32,
                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p,
                              C.c_uint64, u64p, C.c_void_p, C.c_void_p]
-    L.fs_sources_times.restype = C.c_int
-    L.fs_sources_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_clusters.restype = C.c_int
     L.fs_clusters.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -230,8 +227,6 @@ def load():
     L.fs_clusters_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_uint64, u64p]
-    L.fs_clusters_times.restype = C.c_int
-    L.fs_clusters_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_groups.restype = C.c_int
     L.fs_groups.argtypes = [C.c_int, u32p, u32p, u32p, C.POINTER(C.c_uint8), C.c_uint64,
                             C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, C.c_uint32,
@@ -242,8 +237,6 @@ def load():
                                  C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64,
                                  u64p]
-    L.fs_groups_times.restype = C.c_int
-    L.fs_groups_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_open.restype = C.c_int
     L.fs_matches_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p),
                                   C.POINTER(abi.FsMatchesInfo)]
@@ -260,24 +253,18 @@ def load():
     L.fs_readings.argtypes = [C.c_int, u32p, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                               C.c_void_p, C.c_uint64, u64p, u64p, u64p]
-    L.fs_readings_times.restype = C.c_int
-    L.fs_readings_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_retellings.restype = C.c_int
     L.fs_retellings.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_retellings_rows.restype = C.c_int
     L.fs_retellings_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
-    L.fs_retellings_times.restype = C.c_int
-    L.fs_retellings_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matrix.restype = C.c_int
     L.fs_matrix.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                             C.c_uint32, u32p, C.c_void_p, C.c_uint64, u64p, u64p]
     L.fs_matrix_rows.restype = C.c_int
     L.fs_matrix_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p]
-    L.fs_matrix_times.restype = C.c_int
-    L.fs_matrix_times.argtypes = [C.POINTER(C.c_double)]
     L.fs_matches_intern.restype = C.c_int
     L.fs_matches_intern.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint64, u64p]
     L.fs_matches_intern_times.restype = C.c_int
@@ -297,29 +284,23 @@ def load():
     L.fs_search_kernel_name.argtypes = [C.c_void_p, C.c_void_p]
     L.fs_index_reload_switches.restype = C.c_int
     L.fs_index_reload_switches.argtypes = [C.c_void_p]
-    if hasattr(L, "fs_debug_stamps"):      # (absent from older builds loaded through FS_LIB_FILE)
-        L.fs_debug_stamps.restype = C.c_int
-        L.fs_debug_stamps.argtypes = [C.c_void_p, C.c_uint32, u64p, C.c_uint64, u64p]
-    if hasattr(L, "fs_stream_floor"):
-        L.fs_stream_floor.restype = C.c_int
-        L.fs_stream_floor.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
-    if hasattr(L, "fs_index_share_counts"):
-        L.fs_index_share_counts.restype = C.c_int
-        L.fs_index_share_counts.argtypes = [C.c_void_p, u64p]
-    if hasattr(L, "fs_index_lsh_counts"):
-        L.fs_index_lsh_counts.restype = C.c_int
-        L.fs_index_lsh_counts.argtypes = [C.c_void_p, u64p]
-    if hasattr(L, "fs_index_share_info"):
-        L.fs_index_share_info.restype = C.c_int
-        L.fs_index_share_info.argtypes = [C.c_void_p, u32p, u32p, u32p, C.POINTER(C.c_double)]
-    if hasattr(L, "fs_index_component_sizes"):
-        L.fs_index_component_sizes.restype = C.c_int
-        L.fs_index_component_sizes.argtypes = [C.c_void_p, u32p, C.c_uint64, u64p, u32p]
-    if hasattr(L, "fs_search_profile"):    # (absent from older builds loaded through FS_LIB_FILE)
-        L.fs_search_profile.restype = C.c_int
-        L.fs_search_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
-                                        C.c_char_p, C.c_uint64, C.POINTER(C.c_double), C.c_uint32,
-                                        C.POINTER(C.c_uint32)]
+    for name in TIMED:                 # (the stage times of the command's last call)
+        fn = getattr(L, "fs_%s_times" % name)
+        fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_double)]
+    optional = {                       # (absent from older builds loaded through FS_LIB_FILE)
+        "fs_debug_stamps": [C.c_void_p, C.c_uint32, u64p, C.c_uint64, u64p],
+        "fs_stream_floor": [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)],
+        "fs_index_share_counts": [C.c_void_p, u64p],
+        "fs_index_lsh_counts": [C.c_void_p, u64p],
+        "fs_index_share_info": [C.c_void_p, u32p, u32p, u32p, C.POINTER(C.c_double)],
+        "fs_index_component_sizes": [C.c_void_p, u32p, C.c_uint64, u64p, u32p],
+        "fs_search_profile": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                              C.c_char_p, C.c_uint64, C.POINTER(C.c_double), C.c_uint32,
+                              C.POINTER(C.c_uint32)]}
+    for name, argtypes in optional.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = C.c_int, argtypes
     L.fs_scan_benchmark.restype = C.c_int
     L.fs_scan_benchmark.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32,
                                     C.POINTER(C.c_double)]

@@ -33,6 +33,56 @@ class _Scripts(argparse.Action):
         namespace.script = values[0]
 
 
+_SPANS = (lambda a: a.min_words < 1 or a.max_gap < 0,
+          '--min-words must be at least 1, --max-gap at least 0')
+_SHARE = (lambda a: not 0 <= a.min_share <= 100, '--min-share must be from 0 to 100')
+
+
+def _own(*flags, **kwargs):
+    """An argument of one command, for _analysis to add at its place."""
+    return flags, kwargs
+
+
+def _analysis(subparsers, name, help, output_help, checks, first=(), middle=(), last=(),
+              spans=True, several=False):
+    """The sub-command `name` over a match csv (`several`: over two or more, with a required
+    -o): the arguments every analysis command has -- matches, -o/--output, --min-words and
+    --max-gap (`spans`), --device, --reader -- and the command's own (_own), those of `first`
+    in front of -o, of `middle` behind it and of `last` behind --max-gap.  `checks` is what
+    _command tests before it runs the command."""
+    p = subparsers.add_parser(name, help=help)
+    if several:
+        p.add_argument('matches', action='store', nargs='+', metavar='matches',
+                       help='filenames for search output (dated or batch files), one '
+                            'per script, at least two')
+    else:
+        p.add_argument('matches', action='store',
+                       help='filename for search output (dated or batch file)')
+    for flags, kwargs in first:
+        p.add_argument(*flags, **kwargs)
+    p.add_argument('-o', '--output', action='store', default=None, required=several,
+                   help=output_help)
+    for flags, kwargs in middle:
+        p.add_argument(*flags, **kwargs)
+    if spans:
+        p.add_argument('--min-words', default=6, type=int,
+                       help='fewest matched words a passage has, default 6')
+        p.add_argument('--max-gap', default=0, type=int,
+                       help='words without a record a passage may step over on each '
+                            'side at once, default 0')
+    for flags, kwargs in last:
+        p.add_argument(*flags, **kwargs)
+    p.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+    p.add_argument('--reader', default=None, choices=('device', 'python'),
+                   help='who reads the match %s: the GPU (default) or csv.reader; also '
+                        'FANDOM_SEARCH_READER' % ('csvs' if several else 'csv'))
+
+    def func(args):
+        return _command(name, checks, args)
+    func.__name__ = '_' + name          # (what the command's function was called: args.func)
+    p.set_defaults(func=func)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(
         description='n-gram text-reuse search of fan works against a script '
@@ -113,332 +163,213 @@ def build_parser():
                                     'non-zero cell, to ...-gram-match-cells.csv')
     matrix_parser.set_defaults(func=_matrix)
 
-    passages_parser = subparsers.add_parser(
-        'passages', help='joins the per-word records of a match csv into passages of reuse')
-    passages_parser.add_argument('matches', action='store',
-                                 help='filename for search output (dated or batch file)')
-    passages_parser.add_argument('-o', '--output', action='store', default=None,
-                                 help='filename for the passages csv (default: the input name '
-                                      'with .csv replaced by -passages.csv)')
-    passages_parser.add_argument('--min-words', default=6, type=int,
-                                 help='fewest matched words a passage has, default 6')
-    passages_parser.add_argument('--max-gap', default=0, type=int,
-                                 help='words without a record a passage may step over on each '
-                                      'side at once, default 0')
-    passages_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    passages_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                 help='who reads the match csv: the GPU (default) or csv.reader; also '
-                                      'FANDOM_SEARCH_READER')
-    passages_parser.set_defaults(func=_passages)
+    _analysis(subparsers, 'passages',
+              'joins the per-word records of a match csv into passages of reuse',
+              'filename for the passages csv (default: the input name '
+              'with .csv replaced by -passages.csv)',
+              [_SPANS])
 
-    works_parser = subparsers.add_parser(
-        'works', help='summarises the records of a match csv by fan work: how much each work '
-                      'reuses, and from which scenes and characters')
-    works_parser.add_argument('matches', action='store',
-                              help='filename for search output (dated or batch file)')
-    works_parser.add_argument('-o', '--output', action='store', default=None,
-                              help='prefix of the three csv files, PREFIX-works.csv, '
-                                   'PREFIX-works-scenes.csv and PREFIX-works-characters.csv '
-                                   '(default: the input name without .csv)')
-    works_parser.add_argument('--min-words', default=6, type=int,
-                              help='fewest matched words a passage has, default 6')
-    works_parser.add_argument('--max-gap', default=0, type=int,
-                              help='words without a record a passage may step over on each '
-                                   'side at once, default 0')
-    works_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    works_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                              help='who reads the match csv: the GPU (default) or csv.reader; also '
-                                   'FANDOM_SEARCH_READER')
-    works_parser.set_defaults(func=_works)
+    _analysis(subparsers, 'works',
+              'summarises the records of a match csv by fan work: how much each work '
+              'reuses, and from which scenes and characters',
+              'prefix of the three csv files, PREFIX-works.csv, '
+              'PREFIX-works-scenes.csv and PREFIX-works-characters.csv '
+              '(default: the input name without .csv)',
+              [_SPANS])
 
-    quotes_parser = subparsers.add_parser(
-        'quotes', help='ranks the stretches of the script by the fan works that quote them: '
-                       'per script word and per quoted region, how many works and passages')
-    quotes_parser.add_argument('matches', action='store',
-                               help='filename for search output (dated or batch file)')
-    quotes_parser.add_argument('-o', '--output', action='store', default=None,
-                               help='prefix of the two csv files, PREFIX-quotes.csv and '
-                                    'PREFIX-quotes-words.csv (default: the input name without '
-                                    '.csv)')
-    quotes_parser.add_argument('--min-words', default=6, type=int,
-                               help='fewest matched words a passage has, default 6')
-    quotes_parser.add_argument('--max-gap', default=0, type=int,
-                               help='words without a record a passage may step over on each '
-                                    'side at once, default 0')
-    quotes_parser.add_argument('--min-works', default=1, type=int,
-                               help='fewest different works whose passages cover every word of '
-                                    'a region, default 1')
-    quotes_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    quotes_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                               help='who reads the match csv: the GPU (default) or csv.reader; also '
-                                    'FANDOM_SEARCH_READER')
-    quotes_parser.set_defaults(func=_quotes)
+    _analysis(subparsers, 'quotes',
+              'ranks the stretches of the script by the fan works that quote them: '
+              'per script word and per quoted region, how many works and passages',
+              'prefix of the two csv files, PREFIX-quotes.csv and '
+              'PREFIX-quotes-words.csv (default: the input name without '
+              '.csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0,
+                '--min-words and --min-works must be at least 1, --max-gap at least 0')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='fewest different works whose passages cover every word of '
+                              'a region, default 1')])
 
-    variants_parser = subparsers.add_parser(
-        'variants', help='ranks, under each script word, the spellings fans wrote there: per '
-                         'script word and fan spelling, how many records and works')
-    variants_parser.add_argument('matches', action='store',
-                                 help='filename for search output (dated or batch file)')
-    variants_parser.add_argument('-o', '--output', action='store', default=None,
-                                 help='prefix of the two csv files, PREFIX-variants.csv and '
-                                      'PREFIX-variants-words.csv (default: the input name '
-                                      'without .csv)')
-    variants_parser.add_argument('--top', default=10, type=int,
-                                 help='spellings listed per script word, the most frequent '
-                                      'first; 0: all; default 10')
-    variants_parser.add_argument('--min-records', default=1, type=int,
-                                 help='fewest records a listed spelling has, default 1')
-    variants_parser.add_argument('--fold-case', action='store_true',
-                                 help='spellings equal when lower-cased are one spelling, shown '
-                                      'as its first appearance wrote it')
-    variants_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    variants_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                 help='who reads the match csv: the GPU (default) or csv.reader; '
-                                      'also FANDOM_SEARCH_READER')
-    variants_parser.set_defaults(func=_variants)
+    _analysis(subparsers, 'variants',
+              'ranks, under each script word, the spellings fans wrote there: per '
+              'script word and fan spelling, how many records and works',
+              'prefix of the two csv files, PREFIX-variants.csv and '
+              'PREFIX-variants-words.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: a.top < 0 or a.min_records < 1,
+                '--top must be at least 0, --min-records at least 1')],
+              spans=False,
+              last=[_own('--top', default=10, type=int,
+                         help='spellings listed per script word, the most frequent '
+                              'first; 0: all; default 10'),
+                    _own('--min-records', default=1, type=int,
+                         help='fewest records a listed spelling has, default 1'),
+                    _own('--fold-case', action='store_true',
+                         help='spellings equal when lower-cased are one spelling, shown '
+                              'as its first appearance wrote it')])
 
-    pairs_parser = subparsers.add_parser(
-        'pairs', help='ranks the pairs of fan works by the script words both quote: per pair '
-                      'the shared words and their longest run, per work its closest partner')
-    pairs_parser.add_argument('matches', action='store',
-                              help='filename for search output (dated or batch file)')
-    pairs_parser.add_argument('-o', '--output', action='store', default=None,
-                              help='prefix of the two csv files, PREFIX-pairs.csv and '
-                                   'PREFIX-pairs-works.csv (default: the input name without '
-                                   '.csv)')
-    pairs_parser.add_argument('--min-words', default=6, type=int,
-                              help='fewest matched words a passage has, default 6')
-    pairs_parser.add_argument('--max-gap', default=0, type=int,
-                              help='words without a record a passage may step over on each '
-                                   'side at once, default 0')
-    pairs_parser.add_argument('--min-shared', default=6, type=int,
-                              help='fewest script words the passages of both works of a listed '
-                                   'pair cover, default 6')
-    pairs_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    pairs_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                              help='who reads the match csv: the GPU (default) or csv.reader; also '
-                                   'FANDOM_SEARCH_READER')
-    pairs_parser.set_defaults(func=_pairs)
+    _analysis(subparsers, 'pairs',
+              'ranks the pairs of fan works by the script words both quote: per pair '
+              'the shared words and their longest run, per work its closest partner',
+              'prefix of the two csv files, PREFIX-pairs.csv and '
+              'PREFIX-pairs-works.csv (default: the input name without '
+              '.csv)',
+              [(lambda a: a.min_words < 1 or a.min_shared < 1 or a.max_gap < 0,
+                '--min-words and --min-shared must be at least 1, --max-gap at least 0')],
+              last=[_own('--min-shared', default=6, type=int,
+                         help='fewest script words the passages of both works of a listed '
+                              'pair cover, default 6')])
 
-    groups_parser = subparsers.add_parser(
-        'groups', help='reduces the reuse by groups of fan works taken from the metadata csv '
-                       '(year, month, author, language or tag): per group its works, passages '
-                       'and covered script words, per scene and per script word the works')
-    groups_parser.add_argument('matches', action='store',
-                               help='filename for search output (dated or batch file)')
-    groups_parser.add_argument('meta', action='store',
-                               help='filename for the metadata csv (FILENAME, TITLE, AUTHOR, '
-                                    'SUMMARY, NOTES, PUBLICATION_DATE, LANGUAGE, TAGS)')
-    groups_parser.add_argument('--by', default='year',
-                               help='what groups the works: year, month, author, language, tag '
-                                    'or tag:<Category>; default year')
-    groups_parser.add_argument('-o', '--output', action='store', default=None,
-                               help='prefix of the three csv files, PREFIX-groups.csv, '
-                                    'PREFIX-groups-scenes.csv and PREFIX-groups-words.csv '
-                                    '(default: the input name without .csv)')
-    groups_parser.add_argument('--min-words', default=6, type=int,
-                               help='fewest matched words a passage has, default 6')
-    groups_parser.add_argument('--max-gap', default=0, type=int,
-                               help='words without a record a passage may step over on each '
-                                    'side at once, default 0')
-    groups_parser.add_argument('--min-works', default=1, type=int,
-                               help='fewest works of a group whose passages cover a listed '
-                                    'script word, default 1')
-    groups_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    groups_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                               help='who reads the match csv: the GPU (default) or csv.reader; '
-                                    'also FANDOM_SEARCH_READER')
-    groups_parser.set_defaults(func=_groups)
+    _analysis(subparsers, 'groups',
+              'reduces the reuse by groups of fan works taken from the metadata csv '
+              '(year, month, author, language or tag): per group its works, passages '
+              'and covered script words, per scene and per script word the works',
+              'prefix of the three csv files, PREFIX-groups.csv, '
+              'PREFIX-groups-scenes.csv and PREFIX-groups-words.csv '
+              '(default: the input name without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0,
+                '--min-words and --min-works must be at least 1, --max-gap at least 0')],
+              first=[_own('meta', action='store',
+                          help='filename for the metadata csv (FILENAME, TITLE, AUTHOR, '
+                               'SUMMARY, NOTES, PUBLICATION_DATE, LANGUAGE, TAGS)'),
+                     _own('--by', default='year',
+                          help='what groups the works: year, month, author, language, tag '
+                               'or tag:<Category>; default year')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='fewest works of a group whose passages cover a listed '
+                              'script word, default 1')])
 
-    clusters_parser = subparsers.add_parser(
-        'clusters', help='gathers the fan works quoting the same lines into families (connected '
-                         'components of the works linked by shared script words): per family '
-                         'its size, its hub and the words its members have in common, per work '
-                         'its family')
-    clusters_parser.add_argument('matches', action='store',
-                                 help='filename for search output (dated or batch file)')
-    clusters_parser.add_argument('-o', '--output', action='store', default=None,
-                                 help='prefix of the two csv files, PREFIX-clusters.csv and '
-                                      'PREFIX-clusters-works.csv (default: the input name '
-                                      'without .csv)')
-    clusters_parser.add_argument('--min-words', default=6, type=int,
-                                 help='fewest matched words a passage has, default 6')
-    clusters_parser.add_argument('--max-gap', default=0, type=int,
-                                 help='words without a record a passage may step over on each '
-                                      'side at once, default 0')
-    clusters_parser.add_argument('--min-shared', default=6, type=int,
-                                 help='fewest script words the passages of two linked works '
-                                      'both cover, default 6')
-    clusters_parser.add_argument('--min-jaccard', default=50, type=int,
-                                 help='fewest shared words of two linked works as a whole '
-                                      'percentage of the words either covers, 0 to 100, '
-                                      'default 50')
-    clusters_parser.add_argument('--min-size', default=2, type=int,
-                                 help='fewest works of a listed family, default 2')
-    clusters_parser.add_argument('--common', default=50, type=int,
-                                 help='a script word is common to a family when at least this '
-                                      'whole percentage of its works cover it, 1 to 100, '
-                                      'default 50')
-    clusters_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    clusters_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                 help='who reads the match csv: the GPU (default) or '
-                                      'csv.reader; also FANDOM_SEARCH_READER')
-    clusters_parser.set_defaults(func=_clusters)
+    _analysis(subparsers, 'clusters',
+              'gathers the fan works quoting the same lines into families (connected '
+              'components of the works linked by shared script words): per family '
+              'its size, its hub and the words its members have in common, per work '
+              'its family',
+              'prefix of the two csv files, PREFIX-clusters.csv and '
+              'PREFIX-clusters-works.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_shared < 1 or a.min_size < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-shared and --min-size must be at least 1, --max-gap at '
+                'least 0'),
+               (lambda a: not 0 <= a.min_jaccard <= 100 or not 1 <= a.common <= 100,
+                '--min-jaccard must be from 0 to 100, --common from 1 to 100')],
+              last=[_own('--min-shared', default=6, type=int,
+                         help='fewest script words the passages of two linked works '
+                              'both cover, default 6'),
+                    _own('--min-jaccard', default=50, type=int,
+                         help='fewest shared words of two linked works as a whole '
+                              'percentage of the words either covers, 0 to 100, '
+                              'default 50'),
+                    _own('--min-size', default=2, type=int,
+                         help='fewest works of a listed family, default 2'),
+                    _own('--common', default=50, type=int,
+                         help='a script word is common to a family when at least this '
+                              'whole percentage of its works cover it, 1 to 100, '
+                              'default 50')])
 
-    readings_parser = subparsers.add_parser(
-        'readings', help='collates the wordings fans give each quoted stretch of the script: '
-                         'per span and reading (the fan words of a passage), how many passages '
-                         'and works')
-    readings_parser.add_argument('matches', action='store',
-                                 help='filename for search output (dated or batch file)')
-    readings_parser.add_argument('-o', '--output', action='store', default=None,
-                                 help='prefix of the two csv files, PREFIX-readings.csv and '
-                                      'PREFIX-readings-spans.csv (default: the input name '
-                                      'without .csv)')
-    readings_parser.add_argument('--min-words', default=6, type=int,
-                                 help='fewest matched words a passage has, default 6')
-    readings_parser.add_argument('--max-gap', default=0, type=int,
-                                 help='words without a record a passage may step over on each '
-                                      'side at once, default 0')
-    readings_parser.add_argument('--top', default=10, type=int,
-                                 help='readings listed per span, those of the most works '
-                                      'first; 0: all; default 10')
-    readings_parser.add_argument('--min-works', default=1, type=int,
-                                 help='fewest works a listed reading has, default 1')
-    readings_parser.add_argument('--fold-case', action='store_true',
-                                 help='fan words equal when lower-cased are one spelling')
-    readings_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    readings_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                 help='who reads the match csv: the GPU (default) or '
-                                      'csv.reader; also FANDOM_SEARCH_READER')
-    readings_parser.set_defaults(func=_readings)
+    _analysis(subparsers, 'readings',
+              'collates the wordings fans give each quoted stretch of the script: '
+              'per span and reading (the fan words of a passage), how many passages '
+              'and works',
+              'prefix of the two csv files, PREFIX-readings.csv and '
+              'PREFIX-readings-spans.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0 or a.top < 0,
+                '--min-words and --min-works must be at least 1, --max-gap and --top at '
+                'least 0')],
+              last=[_own('--top', default=10, type=int,
+                         help='readings listed per span, those of the most works '
+                              'first; 0: all; default 10'),
+                    _own('--min-works', default=1, type=int,
+                         help='fewest works a listed reading has, default 1'),
+                    _own('--fold-case', action='store_true',
+                         help='fan words equal when lower-cased are one spelling')])
 
-    retellings_parser = subparsers.add_parser(
-        'retellings', help='lists the fan works that quote the script in its order: per work '
-                           'the heaviest chain of passages that advance through the script as '
-                           'they advance through the work, and every passage with its place '
-                           'in the chain')
-    retellings_parser.add_argument('matches', action='store',
-                                   help='filename for search output (dated or batch file)')
-    retellings_parser.add_argument('-o', '--output', action='store', default=None,
-                                   help='prefix of the two csv files, PREFIX-retellings.csv and '
-                                        'PREFIX-retellings-passages.csv (default: the input name '
-                                        'without .csv)')
-    retellings_parser.add_argument('--min-words', default=6, type=int,
-                                   help='fewest matched words a passage has, default 6')
-    retellings_parser.add_argument('--max-gap', default=0, type=int,
-                                   help='words without a record a passage may step over on each '
-                                        'side at once, default 0')
-    retellings_parser.add_argument('--min-passages', default=2, type=int,
-                                   help='fewest passages in the chain of a listed work, '
-                                        'default 2')
-    retellings_parser.add_argument('--min-share', default=0, type=int,
-                                   help='fewest passage words of a listed work that lie in its '
-                                        'chain, as a whole percentage, 0 to 100, default 0')
-    retellings_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    retellings_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                   help='who reads the match csv: the GPU (default) or '
-                                        'csv.reader; also FANDOM_SEARCH_READER')
-    retellings_parser.set_defaults(func=_retellings)
+    _analysis(subparsers, 'retellings',
+              'lists the fan works that quote the script in its order: per work '
+              'the heaviest chain of passages that advance through the script as '
+              'they advance through the work, and every passage with its place '
+              'in the chain',
+              'prefix of the two csv files, PREFIX-retellings.csv and '
+              'PREFIX-retellings-passages.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_passages < 1 or a.max_gap < 0,
+                '--min-words and --min-passages must be at least 1, --max-gap at least 0'),
+               _SHARE],
+              last=[_own('--min-passages', default=2, type=int,
+                         help='fewest passages in the chain of a listed work, '
+                              'default 2'),
+                    _own('--min-share', default=0, type=int,
+                         help='fewest passage words of a listed work that lie in its '
+                              'chain, as a whole percentage, 0 to 100, default 0')])
 
-    companions_parser = subparsers.add_parser(
-        'companions', help='relates the quoted stretches of the script to each other: per pair '
-                           'of quoted regions, scenes or characters the fan works that quote '
-                           'both, per unit its closest companion')
-    companions_parser.add_argument('matches', action='store',
-                                   help='filename for search output (dated or batch file)')
-    companions_parser.add_argument('-o', '--output', action='store', default=None,
-                                   help='prefix of the two csv files, PREFIX-companions.csv and '
-                                        'PREFIX-companions-units.csv (default: the input name '
-                                        'without .csv)')
-    companions_parser.add_argument('--by', default='region',
-                                   choices=('region', 'scene', 'character'),
-                                   help='the units: the quoted regions of `quotes` (default), '
-                                        'the scenes or the characters of the script')
-    companions_parser.add_argument('--min-words', default=6, type=int,
-                                   help='fewest matched words a passage has, default 6')
-    companions_parser.add_argument('--max-gap', default=0, type=int,
-                                   help='words without a record a passage may step over on each '
-                                        'side at once, default 0')
-    companions_parser.add_argument('--min-works', default=1, type=int,
-                                   help='with --by region: fewest different works whose passages '
-                                        'cover every word of a region, default 1')
-    companions_parser.add_argument('--min-both', default=2, type=int,
-                                   help='fewest works quoting both units of a listed pair, '
-                                        'default 2')
-    companions_parser.add_argument('--min-share', default=0, type=int,
-                                   help='fewest works quoting both units as a whole percentage '
-                                        'of the works of the less quoted one, 0 to 100, default 0')
-    companions_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    companions_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                   help='who reads the match csv: the GPU (default) or '
-                                        'csv.reader; also FANDOM_SEARCH_READER')
-    companions_parser.set_defaults(func=_companions)
+    by_unit = _own('--by', default='region', choices=('region', 'scene', 'character'),
+                   help='the units: the quoted regions of `quotes` (default), '
+                        'the scenes or the characters of the script')
+    region_works = _own('--min-works', default=1, type=int,
+                        help='with --by region: fewest different works whose passages '
+                             'cover every word of a region, default 1')
 
-    transitions_parser = subparsers.add_parser(
-        'transitions', help='counts which stretch of the script the fan works quote next: per '
-                            'pair (from, to) of quoted regions, scenes or characters the steps '
-                            'from one to the other, per unit its most usual successor')
-    transitions_parser.add_argument('matches', action='store',
-                                    help='filename for search output (dated or batch file)')
-    transitions_parser.add_argument('-o', '--output', action='store', default=None,
-                                    help='prefix of the two csv files, PREFIX-transitions.csv and '
-                                         'PREFIX-transitions-units.csv (default: the input name '
-                                         'without .csv)')
-    transitions_parser.add_argument('--by', default='region',
-                                    choices=('region', 'scene', 'character'),
-                                    help='the units: the quoted regions of `quotes` (default), '
-                                         'the scenes or the characters of the script')
-    transitions_parser.add_argument('--min-words', default=6, type=int,
-                                    help='fewest matched words a passage has, default 6')
-    transitions_parser.add_argument('--max-gap', default=0, type=int,
-                                    help='words without a record a passage may step over on each '
-                                         'side at once, default 0')
-    transitions_parser.add_argument('--min-works', default=1, type=int,
-                                    help='with --by region: fewest different works whose passages '
-                                         'cover every word of a region, default 1')
-    transitions_parser.add_argument('--within', default=None, type=int,
-                                    help='most fan words between the two passages of a step, '
-                                         'default any distance')
-    transitions_parser.add_argument('--min-steps', default=1, type=int,
-                                    help='fewest steps of a listed cell, default 1')
-    transitions_parser.add_argument('--min-step-works', default=2, type=int,
-                                    help='fewest different works taking the step of a listed '
-                                         'cell, default 2')
-    transitions_parser.add_argument('--min-share', default=0, type=int,
-                                    help='fewest steps of a listed cell as a whole percentage of '
-                                         'the steps leaving its first unit, 0 to 100, default 0')
-    transitions_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    transitions_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                    help='who reads the match csv: the GPU (default) or '
-                                         'csv.reader; also FANDOM_SEARCH_READER')
-    transitions_parser.set_defaults(func=_transitions)
+    _analysis(subparsers, 'companions',
+              'relates the quoted stretches of the script to each other: per pair '
+              'of quoted regions, scenes or characters the fan works that quote '
+              'both, per unit its closest companion',
+              'prefix of the two csv files, PREFIX-companions.csv and '
+              'PREFIX-companions-units.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_both < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-works and --min-both must be at least 1, --max-gap at '
+                'least 0'),
+               _SHARE],
+              middle=[by_unit],
+              last=[region_works,
+                    _own('--min-both', default=2, type=int,
+                         help='fewest works quoting both units of a listed pair, '
+                              'default 2'),
+                    _own('--min-share', default=0, type=int,
+                         help='fewest works quoting both units as a whole percentage '
+                              'of the works of the less quoted one, 0 to 100, default 0')])
 
-    sources_parser = subparsers.add_parser(
-        'sources', help='joins the match files of one corpus searched against several scripts: '
-                        'which script each fan passage quotes, where passages of different '
-                        'scripts lie on the same fan words and which of them wins')
-    sources_parser.add_argument('matches', action='store', nargs='+', metavar='matches',
-                                help='filenames for search output (dated or batch files), one '
-                                     'per script, at least two')
-    sources_parser.add_argument('-o', '--output', action='store', required=True,
-                                help='prefix of the four csv files, PREFIX-sources.csv, '
-                                     'PREFIX-sources-works.csv, PREFIX-sources-scripts.csv and '
-                                     'PREFIX-sources-pairs.csv')
-    sources_parser.add_argument('--names', default=None,
-                                help="the scripts' names, comma-separated, one per file "
-                                     "(default: the files' parent directories when they "
-                                     'differ, else the file names without .csv)')
-    sources_parser.add_argument('--min-words', default=6, type=int,
-                                help='fewest matched words a passage has, default 6')
-    sources_parser.add_argument('--max-gap', default=0, type=int,
-                                help='words without a record a passage may step over on each '
-                                     'side at once, default 0')
-    sources_parser.add_argument('--device', default=0, type=int, help='HIP device ordinal')
-    sources_parser.add_argument('--reader', default=None, choices=('device', 'python'),
-                                help='who reads the match csvs: the GPU (default) or '
-                                     'csv.reader; also FANDOM_SEARCH_READER')
-    sources_parser.set_defaults(func=_sources)
+    _analysis(subparsers, 'transitions',
+              'counts which stretch of the script the fan works quote next: per '
+              'pair (from, to) of quoted regions, scenes or characters the steps '
+              'from one to the other, per unit its most usual successor',
+              'prefix of the two csv files, PREFIX-transitions.csv and '
+              'PREFIX-transitions-units.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_steps < 1
+                           or a.min_step_works < 1 or a.max_gap < 0),
+                '--min-words, --min-works, --min-steps and --min-step-works must be at least '
+                '1, --max-gap at least 0'),
+               (lambda a: a.within is not None and not 0 <= a.within < 0xFFFFFFFF,
+                '--within must be from 0 to 4294967294 (leave it out for any distance)'),
+               _SHARE],
+              middle=[by_unit],
+              last=[region_works,
+                    _own('--within', default=None, type=int,
+                         help='most fan words between the two passages of a step, '
+                              'default any distance'),
+                    _own('--min-steps', default=1, type=int,
+                         help='fewest steps of a listed cell, default 1'),
+                    _own('--min-step-works', default=2, type=int,
+                         help='fewest different works taking the step of a listed '
+                              'cell, default 2'),
+                    _own('--min-share', default=0, type=int,
+                         help='fewest steps of a listed cell as a whole percentage of '
+                              'the steps leaving its first unit, 0 to 100, default 0')])
+
+    _analysis(subparsers, 'sources',
+              'joins the match files of one corpus searched against several scripts: '
+              'which script each fan passage quotes, where passages of different '
+              'scripts lie on the same fan words and which of them wins',
+              'prefix of the four csv files, PREFIX-sources.csv, '
+              'PREFIX-sources-works.csv, PREFIX-sources-scripts.csv and '
+              'PREFIX-sources-pairs.csv',
+              [_SPANS], several=True,
+              middle=[_own('--names', default=None,
+                           help="the scripts' names, comma-separated, one per file "
+                                "(default: the files' parent directories when they "
+                                'differ, else the file names without .csv)')])
     return parser
 
 
@@ -475,143 +406,21 @@ def _matrix(args):
     return matrix.process(args)
 
 
-def _passages(args):
-    from . import passages
-    if args.min_words < 1 or args.max_gap < 0:
-        sys.exit('ao3.py passages: error: --min-words must be at least 1, --max-gap at least 0')
-    return passages.process(args)
-
-
-def _works(args):
-    from . import works
-    if args.min_words < 1 or args.max_gap < 0:
-        sys.exit('ao3.py works: error: --min-words must be at least 1, --max-gap at least 0')
+def _command(name, checks, args):
+    """Runs the analysis command `name` (its module's process): the first of `checks`, pairs
+    (condition on args, message), that holds ends it with `ao3.py NAME: error: message`, and
+    so does a ValueError of the command."""
+    import importlib
+    for fails, message in checks:
+        if fails(args):
+            sys.exit('ao3.py %s: error: %s' % (name, message))
+    module = importlib.import_module('.' + name, __package__)
     try:
-        return works.process(args)
+        if name == 'groups':
+            module.check_by(args.by)
+        return module.process(args)
     except ValueError as e:
-        sys.exit('ao3.py works: error: %s' % e)
-
-
-def _quotes(args):
-    from . import quotes
-    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0:
-        sys.exit('ao3.py quotes: error: --min-words and --min-works must be at least 1, '
-                 '--max-gap at least 0')
-    try:
-        return quotes.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py quotes: error: %s' % e)
-
-
-def _variants(args):
-    from . import variants
-    if args.top < 0 or args.min_records < 1:
-        sys.exit('ao3.py variants: error: --top must be at least 0, --min-records at least 1')
-    try:
-        return variants.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py variants: error: %s' % e)
-
-
-def _pairs(args):
-    from . import pairs
-    if args.min_words < 1 or args.min_shared < 1 or args.max_gap < 0:
-        sys.exit('ao3.py pairs: error: --min-words and --min-shared must be at least 1, '
-                 '--max-gap at least 0')
-    try:
-        return pairs.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py pairs: error: %s' % e)
-
-
-def _groups(args):
-    from . import groups
-    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0:
-        sys.exit('ao3.py groups: error: --min-words and --min-works must be at least 1, '
-                 '--max-gap at least 0')
-    try:
-        groups.check_by(args.by)
-        return groups.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py groups: error: %s' % e)
-
-
-def _clusters(args):
-    from . import clusters
-    if args.min_words < 1 or args.min_shared < 1 or args.min_size < 1 or args.max_gap < 0:
-        sys.exit('ao3.py clusters: error: --min-words, --min-shared and --min-size must be at '
-                 'least 1, --max-gap at least 0')
-    if not 0 <= args.min_jaccard <= 100 or not 1 <= args.common <= 100:
-        sys.exit('ao3.py clusters: error: --min-jaccard must be from 0 to 100, --common from 1 '
-                 'to 100')
-    try:
-        return clusters.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py clusters: error: %s' % e)
-
-
-def _readings(args):
-    from . import readings
-    if args.min_words < 1 or args.min_works < 1 or args.max_gap < 0 or args.top < 0:
-        sys.exit('ao3.py readings: error: --min-words and --min-works must be at least 1, '
-                 '--max-gap and --top at least 0')
-    try:
-        return readings.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py readings: error: %s' % e)
-
-
-def _retellings(args):
-    from . import retellings
-    if args.min_words < 1 or args.min_passages < 1 or args.max_gap < 0:
-        sys.exit('ao3.py retellings: error: --min-words and --min-passages must be at least 1, '
-                 '--max-gap at least 0')
-    if not 0 <= args.min_share <= 100:
-        sys.exit('ao3.py retellings: error: --min-share must be from 0 to 100')
-    try:
-        return retellings.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py retellings: error: %s' % e)
-
-
-def _companions(args):
-    from . import companions
-    if args.min_words < 1 or args.min_works < 1 or args.min_both < 1 or args.max_gap < 0:
-        sys.exit('ao3.py companions: error: --min-words, --min-works and --min-both must be at '
-                 'least 1, --max-gap at least 0')
-    if not 0 <= args.min_share <= 100:
-        sys.exit('ao3.py companions: error: --min-share must be from 0 to 100')
-    try:
-        return companions.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py companions: error: %s' % e)
-
-
-def _transitions(args):
-    from . import transitions
-    if (args.min_words < 1 or args.min_works < 1 or args.min_steps < 1 or args.min_step_works < 1
-            or args.max_gap < 0):
-        sys.exit('ao3.py transitions: error: --min-words, --min-works, --min-steps and '
-                 '--min-step-works must be at least 1, --max-gap at least 0')
-    if args.within is not None and not 0 <= args.within < 0xFFFFFFFF:
-        sys.exit('ao3.py transitions: error: --within must be from 0 to 4294967294 (leave it '
-                 'out for any distance)')
-    if not 0 <= args.min_share <= 100:
-        sys.exit('ao3.py transitions: error: --min-share must be from 0 to 100')
-    try:
-        return transitions.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py transitions: error: %s' % e)
-
-
-def _sources(args):
-    from . import sources
-    if args.min_words < 1 or args.max_gap < 0:
-        sys.exit('ao3.py sources: error: --min-words must be at least 1, --max-gap at least 0')
-    try:
-        return sources.process(args)
-    except ValueError as e:
-        sys.exit('ao3.py sources: error: %s' % e)
+        sys.exit('ao3.py %s: error: %s' % (name, e))
 
 
 def main(argv=None):

@@ -16,13 +16,13 @@ the GPU (fs_companions), the regions from fs_quotes.  A passage is what `passage
 the same `--min-words` and `--max-gap`.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi, quotes
-from .passages import _CHAR, _FNAME, _ORIG_WORD, _SCENE, read_matches, sort_records
+from .command import grow, n_script_of, prefixed, run, script_labels, work_names
+from .passages import sort_records
 from .quotes import UNKNOWN_WORD, word_labels
 from .works import groups_of_labels
 
@@ -48,20 +48,13 @@ def find_companions(work, fan_ix, orig_ix, n_works, n_script, unit_of, n_units, 
         raise ValueError("a unit map of %d entries for %d script words" % (len(unit_of), n_script))
     L = _lib.load()
     units = np.zeros(n_units, dtype=abi.COMPANION_UNIT_DTYPE)
-    cap = 4096
-    while True:
-        pairs = np.empty(cap, dtype=abi.COMPANION_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_companions(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                             abi.ptr(orig, C.c_uint32), n, int(n_works), int(n_script),
-                             abi.ptr(unit_of, C.c_uint32), n_units, int(min_words), int(max_gap),
-                             int(min_both), int(min_share), units.ctypes.data_as(C.c_void_p),
-                             pairs.ctypes.data_as(C.c_void_p), cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_companions")
-        return units, pairs[:got.value]
+    pairs = grow(lambda out, cap, got: L.fs_companions(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), n, int(n_works), int(n_script), abi.ptr(unit_of, C.c_uint32),
+        n_units, int(min_words), int(max_gap), int(min_both), int(min_share),
+        units.ctypes.data_as(C.c_void_p), out, cap, got),
+        abi.COMPANION_DTYPE, 4096, "fs_companions")
+    return units, pairs
 
 
 def active_works(work, fan_ix, orig_ix, min_words=6, max_gap=0):
@@ -83,10 +76,8 @@ def tables(rows, by='region', min_words=6, max_gap=0, min_works=1, min_both=2, m
     (read_matches)."""
     labels = word_labels(rows)
     _, work, fan, orig, _, comb = sort_records(rows)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    return _tables(labels, names, work, fan, orig, comb, n_script, by, min_words, max_gap,
-                   min_works, min_both, min_share, device)
+    return _tables(labels, work_names(rows), work, fan, orig, comb, n_script_of(orig), by,
+                   min_words, max_gap, min_works, min_both, min_share, device)
 
 
 def tables_device(mf, by='region', min_words=6, max_gap=0, min_works=1, min_both=2, min_share=0,
@@ -94,11 +85,10 @@ def tables_device(mf, by='region', min_words=6, max_gap=0, min_works=1, min_both
     """tables over a matches.MatchFile, the three labels decoded once per script word; None
     when a script word's records spell one in two ways (tables() then decides)."""
     _, work, fan, orig, _, comb = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     return _tables(labels, list(mf.names), work, fan, orig, comb, n_script, by, min_words,
                    max_gap, min_works, min_both, min_share, device)
 
@@ -163,29 +153,14 @@ def _tables(labels, names, work, fan, orig, comb, n_script, by, min_words, max_g
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-companions.csv', prefix + '-companions-units.csv')
+    return prefixed(matches, prefix, ('-companions.csv', '-companions-units.csv'))
 
 
 def process(args):
     """`ao3.py companions matches [-o PREFIX] [--by region|scene|character] [--min-words M]
     [--max-gap G] [--min-works K] [--min-both B] [--min-share P] [--device D]
     [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
     opts = (args.by, args.min_words, args.max_gap, args.min_works, args.min_both, args.min_share,
             args.device)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, *opts)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), *opts)
-    for path, head, part in zip(outs, (PAIR_FIELDS, UNIT_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    return run(args, (PAIR_FIELDS, UNIT_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

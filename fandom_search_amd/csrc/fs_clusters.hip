@@ -529,27 +529,21 @@ extern "C" int fs_clusters(int device, const uint32_t* work, const uint32_t* fan
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
+  HostCols cols;
   DBuf<fs_cluster_work> d_works;
   DBuf<fs_cluster> d_clusters;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_works.reserve(n_works));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  const ColsSrc src = cols.src();
   ClustersJob job;
   FS_TRY(job.families(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_shared,
                       min_jaccard, min_size, common_pct, d_works.p, nullptr));
-  if (n_works)
-    FS_HIP(hipMemcpy(works, d_works.p, (size_t)n_works * sizeof(fs_cluster_work),
-                     hipMemcpyDeviceToHost));
+  if (n_works) FS_TRY(copy_out(works, d_works, n_works));
   *n_clusters = job.a.n_listed;
   if (job.a.n_listed > cap) return FS_E_CAPACITY;
   FS_TRY(d_clusters.reserve(job.a.n_listed));
   FS_TRY(job.write(d_clusters.p, nullptr));
-  if (job.a.n_listed)
-    FS_HIP(hipMemcpy(clusters, d_clusters.p, (size_t)job.a.n_listed * sizeof(fs_cluster),
-                     hipMemcpyDeviceToHost));
+  if (job.a.n_listed) FS_TRY(copy_out(clusters, d_clusters, job.a.n_listed));
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
 }
@@ -587,10 +581,5 @@ extern "C" int fs_clusters_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_r
 }
 
 extern "C" int fs_clusters_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 5; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 5);
 }

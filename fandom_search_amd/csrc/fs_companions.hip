@@ -422,27 +422,24 @@ extern "C" int fs_companions(int device, const uint32_t* work, const uint32_t* f
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig, d_unit_of;
+  HostCols cols;
+  DBuf<uint32_t> d_unit_of;
   DBuf<fs_companion_unit> d_units;
   DBuf<fs_companion> d_pairs;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n_script, nullptr));
   FS_TRY(d_units.reserve(n_units));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  const ColsSrc src = cols.src();
   CompJob job;
   FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
                    max_gap, min_both, min_share, d_units.p, nullptr));
-  FS_HIP(hipMemcpy(units, d_units.p, (size_t)n_units * sizeof(fs_companion_unit),
-                   hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(units, d_units, n_units));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
   if (job.n_pairs) {
     FS_TRY(d_pairs.reserve(job.n_pairs));
     FS_TRY(job.write(d_pairs.p, nullptr));
-    FS_HIP(hipMemcpy(pairs, d_pairs.p, (size_t)job.n_pairs * sizeof(fs_companion),
-                     hipMemcpyDeviceToHost));
+    FS_TRY(copy_out(pairs, d_pairs, job.n_pairs));
   }
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
@@ -482,10 +479,5 @@ extern "C" int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n
 }
 
 extern "C" int fs_companions_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 4; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 4);
 }

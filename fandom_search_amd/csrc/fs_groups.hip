@@ -774,33 +774,27 @@ extern "C" int fs_groups(int device, const uint32_t* work, const uint32_t* fan_i
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
+  HostCols cols;
   DBuf<uint8_t> d_exact;
   DBuf<fs_group> d_groups;
   DBuf<fs_group_cell> d_cells;
   DBuf<fs_group_word> d_words;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_exact.upload(exact, n, nullptr));
   FS_TRY(d_groups.reserve(n_groups));
-  const ExactCols src{{d_work.p, d_fan.p, d_orig.p}, d_exact.p};
+  const ExactCols src{cols.src(), d_exact.p};
   GroupsJob job;
   FS_TRY(job.count(src, nullptr, src, plan, n, n_works, n_script, n_groups, label_of, n_labels,
                    min_words, max_gap, min_works, d_groups.p, nullptr));
-  FS_HIP(hipMemcpy(groups, d_groups.p, (size_t)n_groups * sizeof(fs_group), hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(groups, d_groups, n_groups));
   *n_cells = job.n_cells;
   *n_words = job.n_words;
   if (job.n_cells > cap_cells || job.n_words > cap_words) return FS_E_CAPACITY;
   FS_TRY(d_cells.reserve(job.n_cells));
   FS_TRY(d_words.reserve(job.n_words));
   FS_TRY(job.write(d_cells.p, d_words.p, nullptr));
-  if (job.n_cells)
-    FS_HIP(hipMemcpy(cells, d_cells.p, (size_t)job.n_cells * sizeof(fs_group_cell),
-                     hipMemcpyDeviceToHost));
-  if (job.n_words)
-    FS_HIP(hipMemcpy(words, d_words.p, (size_t)job.n_words * sizeof(fs_group_word),
-                     hipMemcpyDeviceToHost));
+  if (job.n_cells) FS_TRY(copy_out(cells, d_cells, job.n_cells));
+  if (job.n_words) FS_TRY(copy_out(words, d_words, job.n_words));
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
 }
@@ -857,10 +851,5 @@ extern "C" int fs_groups_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
 }
 
 extern "C" int fs_groups_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 4; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 4);
 }

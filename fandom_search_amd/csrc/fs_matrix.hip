@@ -536,24 +536,18 @@ extern "C" int fs_matrix(int device, const uint32_t* work, const uint32_t* fan_i
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig, d_starts;
+  HostCols cols;
+  DBuf<uint32_t> d_starts;
   DBuf<fs_matrix_ngram> d_out;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_starts.reserve(n_script));
   const uint64_t most = n_rows / ngram + 1;                  // n-grams never outnumber this
   FS_TRY(d_out.reserve(cap < most ? cap : most));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
-  const int rc = mx_run(src, n, n_works, n_script, ngram, d_starts.p, d_out.p, cap, n_spans,
-                        n_kept, nullptr);
+  const int rc = mx_run(cols.src(), n, n_works, n_script, ngram, d_starts.p, d_out.p, cap,
+                        n_spans, n_kept, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
-  if (starts && n_script)
-    FS_HIP(hipMemcpy(starts, d_starts.p, (size_t)n_script * sizeof(uint32_t),
-                     hipMemcpyDeviceToHost));
-  if (rc == FS_OK && *n_kept)
-    FS_HIP(hipMemcpy(out, d_out.p, (size_t)*n_kept * sizeof(fs_matrix_ngram),
-                     hipMemcpyDeviceToHost));
+  if (starts && n_script) FS_TRY(copy_out(starts, d_starts, n_script));
+  if (rc == FS_OK && *n_kept) FS_TRY(copy_out(out, d_out, *n_kept));
   FS_HIP(hipDeviceSynchronize());
   return rc;
 }
@@ -588,10 +582,5 @@ extern "C" int fs_matrix_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
 }
 
 extern "C" int fs_matrix_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 6; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 6);
 }

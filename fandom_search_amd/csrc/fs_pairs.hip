@@ -331,27 +331,22 @@ extern "C" int fs_pairs(int device, const uint32_t* work, const uint32_t* fan_ix
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
+  HostCols cols;
   DBuf<fs_pair_work> d_works;
   DBuf<fs_pair> d_pairs;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_works.reserve(n_works));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  const ColsSrc src = cols.src();
   PairsJob job;
   FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_shared,
                    d_works.p, nullptr));
-  if (n_works)
-    FS_HIP(hipMemcpy(works, d_works.p, (size_t)n_works * sizeof(fs_pair_work),
-                     hipMemcpyDeviceToHost));
+  if (n_works) FS_TRY(copy_out(works, d_works, n_works));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
   if (job.n_pairs) {
     FS_TRY(d_pairs.reserve(job.n_pairs));
     FS_TRY(job.write(d_pairs.p, nullptr));
-    FS_HIP(hipMemcpy(pairs, d_pairs.p, (size_t)job.n_pairs * sizeof(fs_pair),
-                     hipMemcpyDeviceToHost));
+    FS_TRY(copy_out(pairs, d_pairs, job.n_pairs));
   }
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
@@ -388,10 +383,5 @@ extern "C" int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows
 }
 
 extern "C" int fs_pairs_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 4; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 4);
 }

@@ -358,14 +358,9 @@ extern "C" int fs_passages(int device, const uint32_t* work, const uint32_t* fan
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
-  DBuf<double> d_dist, d_comb;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
-  FS_TRY(d_dist.upload(dist, n, nullptr));
-  FS_TRY(d_comb.upload(comb, n, nullptr));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, d_dist.p, d_comb.p};
+  HostCols cols;
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, dist, comb));
+  const ColsSrc src = cols.src();
   PassWork w;
   FS_TRY(pass_count(src, n, min_words, max_gap, w, nullptr));
   *n_out = w.n_kept;
@@ -373,8 +368,7 @@ extern "C" int fs_passages(int device, const uint32_t* work, const uint32_t* fan
   DBuf<fs_passage> d_out;
   FS_TRY(d_out.reserve(w.n_kept));
   FS_TRY(pass_write(src, w, d_out.p, nullptr));
-  if (w.n_kept)
-    FS_HIP(hipMemcpy(out, d_out.p, (size_t)w.n_kept * sizeof(fs_passage), hipMemcpyDeviceToHost));
+  if (w.n_kept) FS_TRY(copy_out(out, d_out, w.n_kept));
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
 }

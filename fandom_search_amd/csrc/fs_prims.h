@@ -231,4 +231,54 @@ struct Clock {
   }
 };
 
+// ---- what the entry points over host columns share ----
+
+// the record columns of a host entry point on the device: uploaded on the null stream in the
+// order work, fan, orig, dist, comb, the last two only where the command passes them
+struct HostCols {
+  DBuf<uint32_t> work, fan, orig;
+  DBuf<double> dist, comb;
+  int upload(const uint32_t* h_work, const uint32_t* h_fan, const uint32_t* h_orig, size_t n,
+             const double* h_dist = nullptr, const double* h_comb = nullptr) {
+    FS_TRY(work.upload(h_work, n, nullptr));
+    FS_TRY(fan.upload(h_fan, n, nullptr));
+    FS_TRY(orig.upload(h_orig, n, nullptr));
+    if (h_dist) FS_TRY(dist.upload(h_dist, n, nullptr));
+    if (h_comb) FS_TRY(comb.upload(h_comb, n, nullptr));
+    return FS_OK;
+  }
+  ColsSrc src() const { return ColsSrc{work.p, fan.p, orig.p, dist.p, comb.p}; }
+};
+
+// the first n records of a device buffer to the host, when the device is done with them
+template <class T>
+inline int copy_out(T* host, const DBuf<T>& d, size_t n) {
+  FS_HIP(hipMemcpy(host, d.p, n * sizeof(T), hipMemcpyDeviceToHost));
+  return FS_OK;
+}
+
+// fs_X_times: the n stage times the last call of a unit left in t_ms
+inline int times_out(double* ms, const double* t_ms, int n) {
+  if (!ms) {
+    fs_set_error("null argument");
+    return FS_E_INVALID;
+  }
+  for (int k = 0; k < n; ++k) ms[k] = t_ms[k];
+  return FS_OK;
+}
+
+// the two bounds most units put on their records: fewer than 2^32 of them, and a script of at
+// most FS_WORKS_MAX_SCRIPT words
+inline int record_limits(const char* what, uint64_t n_rows, uint32_t n_script) {
+  if (n_rows >= (1ull << 32)) {
+    fs_set_error("%llu records: %s take fewer than 2^32", (unsigned long long)n_rows, what);
+    return FS_E_UNSUPPORTED;
+  }
+  if (n_script > FS_WORKS_MAX_SCRIPT) {
+    fs_set_error("n_script %u: %s take up to %u", n_script, what, FS_WORKS_MAX_SCRIPT);
+    return FS_E_UNSUPPORTED;
+  }
+  return FS_OK;
+}
+
 }  // namespace

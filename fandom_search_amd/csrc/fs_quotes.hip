@@ -608,25 +608,18 @@ extern "C" int fs_quotes(int device, const uint32_t* work, const uint32_t* fan_i
   // regions never outnumber half the script's words (a word apart at least) nor the records
   uint64_t most = ((uint64_t)n_script + 1) / 2;
   if (most > n_rows) most = n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
-  DBuf<double> d_comb;
+  HostCols cols;
   DBuf<fs_quote_word> d_words;
   DBuf<fs_quote_region> d_regions;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
-  FS_TRY(d_comb.upload(comb, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, nullptr, comb));
   FS_TRY(d_words.reserve(n_script));
   FS_TRY(d_regions.reserve(cap < most ? cap : most));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, nullptr, d_comb.p};
+  const ColsSrc src = cols.src();
   const int rc = quotes_run(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_works,
                             d_words.p, d_regions.p, cap, n_regions, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
-  FS_HIP(hipMemcpy(words, d_words.p, (size_t)n_script * sizeof(fs_quote_word),
-                   hipMemcpyDeviceToHost));
-  if (rc == FS_OK && *n_regions)
-    FS_HIP(hipMemcpy(regions, d_regions.p, (size_t)*n_regions * sizeof(fs_quote_region),
-                     hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(words, d_words, n_script));
+  if (rc == FS_OK && *n_regions) FS_TRY(copy_out(regions, d_regions, *n_regions));
   FS_HIP(hipDeviceSynchronize());
   return rc;
 }

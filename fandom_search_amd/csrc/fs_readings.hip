@@ -346,14 +346,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
     fs_set_error("min_words must be at least 1");
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: readings take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: readings take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("readings", n_rows, n_script));
   *n_readings = *n_spans = *n_passages = 0;
   if (n_rows == 0) return FS_OK;
   if (!work || !fan_ix || !orig_ix || !spell) {
@@ -367,16 +360,15 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   if (!n_works || !n_script || !n_spell) return invalid();
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig, d_spell, d_status;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  HostCols cols;
+  DBuf<uint32_t> d_spell, d_status;
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_spell.upload(spell, n, nullptr));
   FS_TRY(d_status.reserve(4));
   FS_HIP(hipMemsetAsync(d_status.p, 0, 4 * sizeof(uint32_t), nullptr));
   RdArgs a{};
-  a.work = d_work.p;
-  a.orig = d_orig.p;
+  a.work = cols.work.p;
+  a.orig = cols.orig.p;
   a.spell = d_spell.p;
   a.n = n;
   a.n_works = n_works;
@@ -390,7 +382,7 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   hipLaunchKernelGGL(k_rd_check, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, nullptr, a);
   FS_HIP(hipGetLastError());
   RunsGuard runs;
-  FS_TRY(fs_runs_find(nullptr, d_work.p, d_fan.p, d_orig.p, n, min_words, max_gap, nullptr, &runs.r,
+  FS_TRY(fs_runs_find(nullptr, cols.work.p, cols.fan.p, cols.orig.p, n, min_words, max_gap, nullptr, &runs.r,
                       &a.heads, &a.n_runs));
   uint32_t st[2];
   FS_HIP(hipMemcpy(st, d_status.p, sizeof st, hipMemcpyDeviceToHost));
@@ -518,10 +510,5 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
 }
 
 extern "C" int fs_readings_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 6; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 6);
 }

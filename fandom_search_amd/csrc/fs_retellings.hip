@@ -468,24 +468,19 @@ extern "C" int fs_retellings(int device, const uint32_t* work, const uint32_t* f
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig;
+  HostCols cols;
   DBuf<fs_retelling> d_out;
   DBuf<fs_retelling_passage> d_pass;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_out.reserve(n_works));
   const uint64_t most = n_rows / min_words;                  // passages never outnumber this
   FS_TRY(d_pass.reserve(cap < most ? cap : most));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  const ColsSrc src = cols.src();
   const int rc = rt_run(src, nullptr, src, n, n_works, min_words, max_gap, d_out.p, d_pass.p, cap,
                         n_passages, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
-  if (n_works)
-    FS_HIP(hipMemcpy(out, d_out.p, (size_t)n_works * sizeof(fs_retelling), hipMemcpyDeviceToHost));
-  if (rc == FS_OK && *n_passages)
-    FS_HIP(hipMemcpy(passages, d_pass.p, (size_t)*n_passages * sizeof(fs_retelling_passage),
-                     hipMemcpyDeviceToHost));
+  if (n_works) FS_TRY(copy_out(out, d_out, n_works));
+  if (rc == FS_OK && *n_passages) FS_TRY(copy_out(passages, d_pass, *n_passages));
   FS_HIP(hipDeviceSynchronize());
   return rc;
 }
@@ -511,10 +506,5 @@ extern "C" int fs_retellings_rows(fs_index* ix, const fs_row* d_rows, uint64_t n
 }
 
 extern "C" int fs_retellings_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 6; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 6);
 }

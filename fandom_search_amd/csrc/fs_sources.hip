@@ -671,10 +671,5 @@ extern "C" int fs_sources(int device, const fs_source_cols* files, uint32_t n_fi
 }
 
 extern "C" int fs_sources_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 5; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 5);
 }

@@ -539,20 +539,18 @@ extern "C" int fs_transitions(int device, const uint32_t* work, const uint32_t* 
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig, d_unit_of;
+  HostCols cols;
+  DBuf<uint32_t> d_unit_of;
   DBuf<fs_transition_unit> d_units;
   DBuf<fs_transition> d_cells;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n_script, nullptr));
   FS_TRY(d_units.reserve(n_units));
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p};
+  const ColsSrc src = cols.src();
   TrJob job;
   FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
                    max_gap, within, min_steps, min_step_works, min_share, d_units.p, nullptr));
-  FS_HIP(hipMemcpy(units, d_units.p, (size_t)n_units * sizeof(fs_transition_unit),
-                   hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(units, d_units, n_units));
   *n_cells = job.n_cells;
   if (job.n_cells > cap) {
     fs_set_error("%llu cells need room", (unsigned long long)job.n_cells);
@@ -561,8 +559,7 @@ extern "C" int fs_transitions(int device, const uint32_t* work, const uint32_t* 
   if (job.n_cells) {
     FS_TRY(d_cells.reserve(job.n_cells));
     FS_TRY(job.write(d_cells.p, nullptr));
-    FS_HIP(hipMemcpy(cells, d_cells.p, (size_t)job.n_cells * sizeof(fs_transition),
-                     hipMemcpyDeviceToHost));
+    FS_TRY(copy_out(cells, d_cells, job.n_cells));
   }
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
@@ -606,10 +603,5 @@ extern "C" int fs_transitions_rows(fs_index* ix, const fs_row* d_rows, uint64_t 
 }
 
 extern "C" int fs_transitions_times(double* ms) {
-  if (!ms) {
-    fs_set_error("null argument");
-    return FS_E_INVALID;
-  }
-  for (int k = 0; k < 5; ++k) ms[k] = t_ms[k];
-  return FS_OK;
+  return times_out(ms, t_ms, 5);
 }

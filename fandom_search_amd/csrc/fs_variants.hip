@@ -147,14 +147,7 @@ extern "C" int fs_variants(int device, const uint32_t* work, const uint32_t* ori
     fs_set_error("null argument");
     return FS_E_INVALID;
   }
-  if (n >= (1ull << 32)) {
-    fs_set_error("%llu records: variants take fewer than 2^32", (unsigned long long)n);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: variants take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("variants", n, n_script));
   *n_cells = 0;
   if (n == 0) {
     for (uint32_t j = 0; j < n_script; ++j) words[j] = fs_variant_word{0, 0, 0, FS_NONE};
@@ -213,8 +206,7 @@ extern "C" int fs_variants(int device, const uint32_t* work, const uint32_t* ori
   FS_HIP(hipMemcpy(st, d_status.p, sizeof st, hipMemcpyDeviceToHost));
   if (st[0]) return variants_invalid();
   *n_cells = st[1];
-  FS_HIP(hipMemcpy(words, d_words.p, (size_t)n_script * sizeof(fs_variant_word),
-                   hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(words, d_words, n_script));
   if (st[1] > cap) {
     fs_set_error("%u cells need room", st[1]);
     return FS_E_CAPACITY;
@@ -229,8 +221,7 @@ extern "C" int fs_variants(int device, const uint32_t* work, const uint32_t* ori
   hipLaunchKernelGGL(k_var_rank, dim3((a.n_cells + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr,
                      a);
   FS_HIP(hipGetLastError());
-  FS_HIP(hipMemcpy(cells, d_cells.p, (size_t)a.n_cells * sizeof(fs_variant_cell),
-                   hipMemcpyDeviceToHost));
+  FS_TRY(copy_out(cells, d_cells, a.n_cells));
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
 }

@@ -517,30 +517,24 @@ extern "C" int fs_works(int device, const uint32_t* work, const uint32_t* fan_ix
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  DBuf<uint32_t> d_work, d_fan, d_orig, d_counts;
-  DBuf<double> d_comb;
+  HostCols cols;
+  DBuf<uint32_t> d_counts;
   DBuf<fs_work> d_out;
   DBuf<fs_work_cell> d_cells;
-  FS_TRY(d_work.upload(work, n, nullptr));
-  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
-  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
-  FS_TRY(d_comb.upload(comb, n, nullptr));
+  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, nullptr, comb));
   FS_TRY(d_out.reserve(n_works));
   FS_TRY(d_counts.reserve((size_t)n_works * (n_thr + 1)));
   FS_TRY(d_cells.reserve(cap < n_rows ? cap : n_rows));       // a record makes at most one cell
-  const ColsSrc src{d_work.p, d_fan.p, d_orig.p, nullptr, d_comb.p};
+  const ColsSrc src = cols.src();
   const int rc = works_run(src, nullptr, src, n, n_works, n_script, group_of, n_groups, min_words,
                            max_gap, thresholds, n_thr, d_out.p, d_counts.p, d_cells.p, cap, n_cells,
                            nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
   if (n_works) {
-    FS_HIP(hipMemcpy(out, d_out.p, (size_t)n_works * sizeof(fs_work), hipMemcpyDeviceToHost));
-    FS_HIP(hipMemcpy(counts, d_counts.p, (size_t)n_works * (n_thr + 1) * sizeof(uint32_t),
-                     hipMemcpyDeviceToHost));
+    FS_TRY(copy_out(out, d_out, n_works));
+    FS_TRY(copy_out(counts, d_counts, (size_t)n_works * (n_thr + 1)));
   }
-  if (rc == FS_OK && *n_cells)
-    FS_HIP(hipMemcpy(cells, d_cells.p, (size_t)*n_cells * sizeof(fs_work_cell),
-                     hipMemcpyDeviceToHost));
+  if (rc == FS_OK && *n_cells) FS_TRY(copy_out(cells, d_cells, *n_cells));
   FS_HIP(hipDeviceSynchronize());
   return rc;
 }

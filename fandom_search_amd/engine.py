@@ -143,6 +143,56 @@ def torch_ready():
         torch.cuda.current_stream().synchronize()
 
 
+def _first_cap(cap, out_ptrs, first):
+    """The capacity a *_device method begins with: the caller's `cap`; without one, `first`
+    for buffers of the method's own and 0 for the caller's."""
+    if cap is None:
+        return 0 if out_ptrs is not None else first
+    return int(cap)
+
+
+def _rows_call(where, call, fixed, grown, caps, out_ptrs, message):
+    """The fs_*_rows call behind a *_device method of ScriptIndex.  call(fixed, grown, caps,
+    counts) makes it: the device addresses of the fixed outputs, those of the growing outputs,
+    their capacities, and one c_uint64 per growing output for the count the library reports.
+    `fixed` lists (count, dtype) per fixed output, `grown` the growing outputs' dtypes, `caps`
+    their capacities.  With `out_ptrs` (the caller's buffers, the fixed ones first): one call
+    and the count (the counts, as a tuple, of several growing outputs); FsError(FS_E_CAPACITY)
+    saying `message`, with the same in .required, when a buffer is too small.  Without:
+    buffers from torch, the growing ones enlarged to the reported counts until the call fits,
+    and the outputs as a tuple of host arrays, the fixed ones first."""
+    counts = [C.c_uint64(0) for _ in grown]
+    if out_ptrs is not None:
+        rc = call(out_ptrs[:len(fixed)], out_ptrs[len(fixed):], caps, counts)
+        got = int(counts[0].value) if len(counts) == 1 else tuple(int(c.value) for c in counts)
+        if rc == abi.FS_E_CAPACITY:
+            err = _lib.FsError(rc, where, message)
+            err.required = got
+            raise err
+        _lib.check(rc, where)
+        return got
+    import torch
+
+    def device(count, dtype):
+        return torch.empty(max(1, int(count)) * np.dtype(dtype).itemsize, dtype=torch.uint8,
+                           device="cuda")
+
+    def host(buf, count, dtype):
+        return buf[:int(count) * np.dtype(dtype).itemsize].cpu().numpy().view(dtype)
+    held = [device(n, d) for n, d in fixed]
+    caps = [int(c) for c in caps]
+    while True:
+        room = [device(c, d) for c, d in zip(caps, grown)]
+        torch_ready()
+        rc = call([b.data_ptr() for b in held], [b.data_ptr() for b in room], caps, counts)
+        if rc == abi.FS_E_CAPACITY:                      # (the library says how many)
+            caps = [max(c, int(n.value)) for c, n in zip(caps, counts)]
+            continue
+        _lib.check(rc, where)
+        return tuple([host(b, n, d) for b, (n, d) in zip(held, fixed)]
+                     + [host(b, n.value, d) for b, n, d in zip(room, counts, grown)])
+
+
 class PinnedBuffer(object):
     """Page-locked host memory (hipHostMalloc) viewed as a numpy array."""
 
@@ -432,24 +482,17 @@ class ScriptIndex(object):
         number; FsError(FS_E_CAPACITY) with .required when the buffer is too small.  A buffer
         torch has only just produced goes in after torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
+
+        def call(_, grown, caps, counts):
+            return L.fs_passages_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(min_words),
+                                      int(max_gap), C.c_void_p(grown[0]), int(caps[0]),
+                                      C.byref(counts[0]))
         if out_ptr is not None:
-            rc = L.fs_passages_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(min_words),
-                                    int(max_gap), C.c_void_p(out_ptr), int(cap), C.byref(n))
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_passages_rows", "passage buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_passages_rows")
-            return int(n.value)
-        import torch
+            return _rows_call("fs_passages_rows", call, [], [abi.PASSAGE_DTYPE], [cap], [out_ptr],
+                              "passage buffer too small")
         cap = int(n_rows) // max(1, int(min_words)) + 1      # passages never outnumber this
-        out = torch.empty(cap * abi.PASSAGE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        torch_ready()
-        _lib.check(L.fs_passages_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(min_words),
-                                      int(max_gap), C.c_void_p(out.data_ptr()), cap, C.byref(n)),
-                   "fs_passages_rows")
-        return out[:n.value * abi.PASSAGE_DTYPE.itemsize].cpu().numpy().view(abi.PASSAGE_DTYPE)
+        return _rows_call("fs_passages_rows", call, [], [abi.PASSAGE_DTYPE], [cap], None,
+                          "passage buffer too small")[0]
 
     def works_device(self, rows_ptr, n_rows, n_works, group_of=None, n_groups=0, min_words=6,
                      max_gap=0, thresholds=None, out_ptrs=None, cap=0):
@@ -466,37 +509,22 @@ class ScriptIndex(object):
         thr = np.ascontiguousarray(THRESHOLDS if thresholds is None else thresholds,
                                    dtype=np.float64)
         gmap = None if group_of is None else abi.as_u32(group_of)
-        n = C.c_uint64(0)
+        n_works, cols = int(n_works), len(thr) + 1
 
-        def call(out, counts, cells, cap):
-            return L.fs_works_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+        def call(fixed, grown, caps, counts):
+            return L.fs_works_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), n_works,
                                    abi.ptr(gmap, C.c_uint32), int(n_groups), int(min_words),
                                    int(max_gap), abi.ptr(thr, C.c_double), len(thr),
-                                   C.c_void_p(out), C.c_void_p(counts), C.c_void_p(cells),
-                                   int(cap), C.byref(n))
+                                   C.c_void_p(fixed[0]), C.c_void_p(fixed[1]),
+                                   C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]))
+        if out_ptrs is None:
+            cap = min(int(n_rows), n_works * int(n_groups))  # a record makes at most one cell
+        got = _rows_call("fs_works_rows", call,
+                         [(n_works, abi.WORK_DTYPE), (n_works * cols, np.uint32)],
+                         [abi.WORK_CELL_DTYPE], [cap], out_ptrs, "cell buffer too small")
         if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], out_ptrs[2], cap)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_works_rows", "cell buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_works_rows")
-            return int(n.value)
-        import torch
-        n_works, cols = int(n_works), len(thr) + 1
-        out = torch.empty(max(1, n_works) * abi.WORK_DTYPE.itemsize, dtype=torch.uint8,
-                          device="cuda")
-        counts = torch.empty(max(1, n_works * cols), dtype=torch.int32, device="cuda")
-        cap = min(int(n_rows), n_works * int(n_groups))      # a record makes at most one cell
-        cells = torch.empty(max(1, cap) * abi.WORK_CELL_DTYPE.itemsize, dtype=torch.uint8,
-                            device="cuda")
-        torch_ready()
-        _lib.check(call(out.data_ptr(), counts.data_ptr(), cells.data_ptr(), cap),
-                   "fs_works_rows")
-        return (out[:n_works * abi.WORK_DTYPE.itemsize].cpu().numpy().view(abi.WORK_DTYPE),
-                counts[:n_works * cols].cpu().numpy().view(np.uint32).reshape(n_works, cols),
-                cells[:n.value * abi.WORK_CELL_DTYPE.itemsize].cpu().numpy()
-                .view(abi.WORK_CELL_DTYPE))
+            return got
+        return got[0], got[1].reshape(n_works, cols), got[2]
 
     def quotes_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_works=1,
                       out_ptrs=None, cap=0):
@@ -508,33 +536,17 @@ class ScriptIndex(object):
         regions; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the words
         are complete then).  Buffers torch has only just produced go in after torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
+        n_script = int(self.info["n_script"])
 
-        def call(words, regions, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_quotes_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                     int(min_words), int(max_gap), int(min_works),
-                                    C.c_void_p(words), C.c_void_p(regions), int(cap), C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_quotes_rows", "region buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_quotes_rows")
-            return int(n.value)
-        import torch
-        n_script = int(self.info["n_script"])
-        cap = min(int(n_rows), (n_script + 1) // 2)          # regions lie a word apart at least
-        words = torch.empty(max(1, n_script) * abi.QUOTE_WORD_DTYPE.itemsize, dtype=torch.uint8,
-                            device="cuda")
-        regions = torch.empty(max(1, cap) * abi.QUOTE_REGION_DTYPE.itemsize, dtype=torch.uint8,
-                              device="cuda")
-        torch_ready()
-        _lib.check(call(words.data_ptr(), regions.data_ptr(), cap), "fs_quotes_rows")
-        return (words[:n_script * abi.QUOTE_WORD_DTYPE.itemsize].cpu().numpy()
-                .view(abi.QUOTE_WORD_DTYPE),
-                regions[:n.value * abi.QUOTE_REGION_DTYPE.itemsize].cpu().numpy()
-                .view(abi.QUOTE_REGION_DTYPE))
+                                    C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                    C.byref(counts[0]))
+        if out_ptrs is None:
+            cap = min(int(n_rows), (n_script + 1) // 2)      # regions lie a word apart at least
+        return _rows_call("fs_quotes_rows", call, [(n_script, abi.QUOTE_WORD_DTYPE)],
+                          [abi.QUOTE_REGION_DTYPE], [cap], out_ptrs, "region buffer too small")
 
     def pairs_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_shared=6,
                      out_ptrs=None, cap=None):
@@ -546,36 +558,15 @@ class ScriptIndex(object):
         pairs; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the works
         are complete then).  Buffers torch has only just produced go in after torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
 
-        def call(works, pairs, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_pairs_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                    int(min_words), int(max_gap), int(min_shared),
-                                   C.c_void_p(works), C.c_void_p(pairs), int(cap), C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_pairs_rows", "pair buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_pairs_rows")
-            return int(n.value)
-        import torch
-        works = torch.empty(max(1, int(n_works)) * abi.PAIR_WORK_DTYPE.itemsize,
-                            dtype=torch.uint8, device="cuda")
-        cap = 4096 if cap is None else int(cap)
-        while True:
-            pairs = torch.empty(max(1, cap) * abi.PAIR_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            torch_ready()
-            rc = call(works.data_ptr(), pairs.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:                  # (the count pass says how many)
-                cap = int(n.value)
-                continue
-            _lib.check(rc, "fs_pairs_rows")
-            return (works[:int(n_works) * abi.PAIR_WORK_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.PAIR_WORK_DTYPE),
-                    pairs[:n.value * abi.PAIR_DTYPE.itemsize].cpu().numpy().view(abi.PAIR_DTYPE))
+                                   C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                   C.byref(counts[0]))
+        return _rows_call("fs_pairs_rows", call, [(n_works, abi.PAIR_WORK_DTYPE)],
+                          [abi.PAIR_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "pair buffer too small")
 
     def companions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                           max_gap=0, min_both=2, min_share=0, out_ptrs=None, cap=None):
@@ -588,39 +579,16 @@ class ScriptIndex(object):
         .required when that buffer is too small (the units are complete then).  Buffers torch
         has only just produced go in after torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
 
-        def call(units, pairs, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_companions_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                         C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
                                         int(max_gap), int(min_both), int(min_share),
-                                        C.c_void_p(units), C.c_void_p(pairs), int(cap),
-                                        C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_companions_rows", "pair buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_companions_rows")
-            return int(n.value)
-        import torch
-        units = torch.empty(max(1, int(n_units)) * abi.COMPANION_UNIT_DTYPE.itemsize,
-                            dtype=torch.uint8, device="cuda")
-        cap = 4096 if cap is None else int(cap)
-        while True:
-            pairs = torch.empty(max(1, cap) * abi.COMPANION_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            torch_ready()
-            rc = call(units.data_ptr(), pairs.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:                  # (the count pass says how many)
-                cap = int(n.value)
-                continue
-            _lib.check(rc, "fs_companions_rows")
-            return (units[:int(n_units) * abi.COMPANION_UNIT_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.COMPANION_UNIT_DTYPE),
-                    pairs[:n.value * abi.COMPANION_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.COMPANION_DTYPE))
+                                        C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                        C.byref(counts[0]))
+        return _rows_call("fs_companions_rows", call, [(n_units, abi.COMPANION_UNIT_DTYPE)],
+                          [abi.COMPANION_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "pair buffer too small")
 
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
@@ -634,39 +602,17 @@ class ScriptIndex(object):
         cells; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the units
         are complete then).  Buffers torch has only just produced go in after torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
 
-        def call(units, cells, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_transitions_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                          C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
                                          int(max_gap), int(within), int(min_steps),
-                                         int(min_step_works), int(min_share), C.c_void_p(units),
-                                         C.c_void_p(cells), int(cap), C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_transitions_rows", "cell buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_transitions_rows")
-            return int(n.value)
-        import torch
-        units = torch.empty(max(1, int(n_units)) * abi.TRANSITION_UNIT_DTYPE.itemsize,
-                            dtype=torch.uint8, device="cuda")
-        cap = 4096 if cap is None else int(cap)
-        while True:
-            cells = torch.empty(max(1, cap) * abi.TRANSITION_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            torch_ready()
-            rc = call(units.data_ptr(), cells.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:                  # (the keep pass says how many)
-                cap = int(n.value)
-                continue
-            _lib.check(rc, "fs_transitions_rows")
-            return (units[:int(n_units) * abi.TRANSITION_UNIT_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.TRANSITION_UNIT_DTYPE),
-                    cells[:n.value * abi.TRANSITION_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.TRANSITION_DTYPE))
+                                         int(min_step_works), int(min_share),
+                                         C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                         C.byref(counts[0]))
+        return _rows_call("fs_transitions_rows", call, [(n_units, abi.TRANSITION_UNIT_DTYPE)],
+                          [abi.TRANSITION_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "cell buffer too small")
 
     def clusters_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_shared=6,
                         min_jaccard=50, min_size=2, common_pct=50, out_ptrs=None, cap=None):
@@ -679,38 +625,16 @@ class ScriptIndex(object):
         works are complete then).  Buffers torch has only just produced go in after
         torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
 
-        def call(works, found, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_clusters_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                       int(min_words), int(max_gap), int(min_shared),
                                       int(min_jaccard), int(min_size), int(common_pct),
-                                      C.c_void_p(works), C.c_void_p(found), int(cap), C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_clusters_rows", "cluster buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_clusters_rows")
-            return int(n.value)
-        import torch
-        works = torch.empty(max(1, int(n_works)) * abi.CLUSTER_WORK_DTYPE.itemsize,
-                            dtype=torch.uint8, device="cuda")
-        cap = 4096 if cap is None else int(cap)
-        while True:
-            found = torch.empty(max(1, cap) * abi.CLUSTER_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            torch_ready()
-            rc = call(works.data_ptr(), found.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:                  # (the numbering says how many)
-                cap = int(n.value)
-                continue
-            _lib.check(rc, "fs_clusters_rows")
-            return (works[:int(n_works) * abi.CLUSTER_WORK_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.CLUSTER_WORK_DTYPE),
-                    found[:n.value * abi.CLUSTER_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.CLUSTER_DTYPE))
+                                      C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                      C.byref(counts[0]))
+        return _rows_call("fs_clusters_rows", call, [(n_works, abi.CLUSTER_WORK_DTYPE)],
+                          [abi.CLUSTER_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "cluster buffer too small")
 
     def retellings_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, out_ptrs=None,
                           cap=None):
@@ -723,37 +647,15 @@ class ScriptIndex(object):
         (the works are complete then).  Buffers torch has only just produced go in after
         torch_ready()."""
         L = _lib.load()
-        n = C.c_uint64(0)
 
-        def call(works, found, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_retellings_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
-                                        int(min_words), int(max_gap), C.c_void_p(works),
-                                        C.c_void_p(found), int(cap), C.byref(n))
-        if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_retellings_rows", "passage buffer too small")
-                err.required = int(n.value)
-                raise err
-            _lib.check(rc, "fs_retellings_rows")
-            return int(n.value)
-        import torch
-        works = torch.empty(max(1, int(n_works)) * abi.RETELLING_DTYPE.itemsize,
-                            dtype=torch.uint8, device="cuda")
-        cap = int(n_rows) // max(1, int(min_words)) if cap is None else int(cap)
-        while True:
-            found = torch.empty(max(1, cap) * abi.RETELLING_PASSAGE_DTYPE.itemsize,
-                                dtype=torch.uint8, device="cuda")
-            torch_ready()
-            rc = call(works.data_ptr(), found.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:
-                cap = int(n.value)
-                continue
-            _lib.check(rc, "fs_retellings_rows")
-            return (works[:int(n_works) * abi.RETELLING_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.RETELLING_DTYPE),
-                    found[:n.value * abi.RETELLING_PASSAGE_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.RETELLING_PASSAGE_DTYPE))
+                                        int(min_words), int(max_gap), C.c_void_p(fixed[0]),
+                                        C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]))
+        cap = _first_cap(cap, out_ptrs, int(n_rows) // max(1, int(min_words)))
+        return _rows_call("fs_retellings_rows", call, [(n_works, abi.RETELLING_DTYPE)],
+                          [abi.RETELLING_PASSAGE_DTYPE], [cap], out_ptrs,
+                          "passage buffer too small")
 
     def matrix_device(self, rows_ptr, n_rows, n_works, n_script, ngram=6, out_ptrs=None,
                       cap=None):
@@ -765,35 +667,19 @@ class ScriptIndex(object):
         small (starts is complete then).  Buffers torch has only just produced go in after
         torch_ready()."""
         L = _lib.load()
-        spans, kept = C.c_uint64(0), C.c_uint64(0)
+        spans = C.c_uint64(0)
 
-        def call(starts, found, cap):
+        def call(fixed, grown, caps, counts):
             return L.fs_matrix_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
-                                    int(n_script), int(ngram), C.c_void_p(starts),
-                                    C.c_void_p(found), int(cap), C.byref(spans), C.byref(kept))
+                                    int(n_script), int(ngram), C.c_void_p(fixed[0]),
+                                    C.c_void_p(grown[0]), int(caps[0]), C.byref(spans),
+                                    C.byref(counts[0]))
+        cap = _first_cap(cap, out_ptrs, int(n_rows) // max(1, int(ngram)) + 1)
+        got = _rows_call("fs_matrix_rows", call, [(n_script, np.uint32)],
+                         [abi.MATRIX_NGRAM_DTYPE], [cap], out_ptrs, "n-gram buffer too small")
         if out_ptrs is not None:
-            rc = call(out_ptrs[0], out_ptrs[1], cap or 0)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_matrix_rows", "n-gram buffer too small")
-                err.required = int(kept.value)
-                raise err
-            _lib.check(rc, "fs_matrix_rows")
-            return int(spans.value), int(kept.value)
-        import torch
-        starts = torch.empty(max(1, int(n_script)) * 4, dtype=torch.uint8, device="cuda")
-        cap = int(n_rows) // max(1, int(ngram)) + 1 if cap is None else int(cap)
-        while True:
-            found = torch.empty(max(1, cap) * abi.MATRIX_NGRAM_DTYPE.itemsize,
-                                dtype=torch.uint8, device="cuda")
-            torch_ready()
-            rc = call(starts.data_ptr(), found.data_ptr(), cap)
-            if rc == abi.FS_E_CAPACITY:
-                cap = int(kept.value)
-                continue
-            _lib.check(rc, "fs_matrix_rows")
-            return (starts[:int(n_script) * 4].cpu().numpy().view(np.uint32), int(spans.value),
-                    found[:kept.value * abi.MATRIX_NGRAM_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.MATRIX_NGRAM_DTYPE))
+            return int(spans.value), got
+        return got[0], int(spans.value), got[1]
 
     def groups_device(self, rows_ptr, n_rows, n_works, mem_off, mem_grp, n_groups, label_of=None,
                       n_labels=0, min_words=6, max_gap=0, min_works=1, out_ptrs=None, caps=None):
@@ -806,47 +692,21 @@ class ScriptIndex(object):
         groups are complete then).  Buffers torch has only just produced go in after
         torch_ready()."""
         L = _lib.load()
-        nc, nw = C.c_uint64(0), C.c_uint64(0)
         mem_off, mem_grp = abi.as_u64(mem_off), abi.as_u32(mem_grp)
         lab = abi.as_u32(label_of) if n_labels else None
 
-        def call(groups, cells, cap_c, words, cap_w):
+        def call(fixed, grown, caps, counts):
             return L.fs_groups_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
                                     abi.ptr(mem_off, C.c_uint64), abi.ptr(mem_grp, C.c_uint32),
                                     int(n_groups), abi.ptr(lab, C.c_uint32), int(n_labels),
                                     int(min_words), int(max_gap), int(min_works),
-                                    C.c_void_p(groups), C.c_void_p(cells), int(cap_c),
-                                    C.byref(nc), C.c_void_p(words), int(cap_w), C.byref(nw))
-        if out_ptrs is not None:
-            cap_c, cap_w = caps or (0, 0)
-            rc = call(out_ptrs[0], out_ptrs[1], cap_c, out_ptrs[2], cap_w)
-            if rc == abi.FS_E_CAPACITY:
-                err = _lib.FsError(rc, "fs_groups_rows", "cell or word buffer too small")
-                err.required = (int(nc.value), int(nw.value))
-                raise err
-            _lib.check(rc, "fs_groups_rows")
-            return int(nc.value), int(nw.value)
-        import torch
-        groups = torch.empty(max(1, int(n_groups)) * abi.GROUP_DTYPE.itemsize, dtype=torch.uint8,
-                             device="cuda")
-        cap_c, cap_w = caps or (4096, 1 << 16)
-        while True:
-            cells = torch.empty(max(1, cap_c) * abi.GROUP_CELL_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            words = torch.empty(max(1, cap_w) * abi.GROUP_WORD_DTYPE.itemsize, dtype=torch.uint8,
-                                device="cuda")
-            torch_ready()
-            rc = call(groups.data_ptr(), cells.data_ptr(), cap_c, words.data_ptr(), cap_w)
-            if rc == abi.FS_E_CAPACITY:                  # (the count pass says how many)
-                cap_c, cap_w = max(cap_c, int(nc.value)), max(cap_w, int(nw.value))
-                continue
-            _lib.check(rc, "fs_groups_rows")
-            return (groups[:int(n_groups) * abi.GROUP_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.GROUP_DTYPE),
-                    cells[:nc.value * abi.GROUP_CELL_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.GROUP_CELL_DTYPE),
-                    words[:nw.value * abi.GROUP_WORD_DTYPE.itemsize].cpu().numpy()
-                    .view(abi.GROUP_WORD_DTYPE))
+                                    C.c_void_p(fixed[0]), C.c_void_p(grown[0]), int(caps[0]),
+                                    C.byref(counts[0]), C.c_void_p(grown[1]), int(caps[1]),
+                                    C.byref(counts[1]))
+        caps = caps or ((0, 0) if out_ptrs is not None else (4096, 1 << 16))
+        return _rows_call("fs_groups_rows", call, [(n_groups, abi.GROUP_DTYPE)],
+                          [abi.GROUP_CELL_DTYPE, abi.GROUP_WORD_DTYPE], caps, out_ptrs,
+                          "cell or word buffer too small")
 
     def scan_benchmark(self, corpus, reps=20):
         """Average milliseconds of one scan-kernel launch over `corpus`."""

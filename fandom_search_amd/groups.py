@@ -24,7 +24,8 @@ import re
 import numpy as np
 
 from . import _lib, abi
-from .passages import _CHAR, _FNAME, _ORIG_WORD, _SCENE, read_matches, sort_records
+from .command import grow, n_script_of, prefixed, run, script_labels, work_names
+from .passages import sort_records
 from .quotes import UNKNOWN_WORD, word_labels
 from .works import groups_of_labels
 
@@ -154,23 +155,14 @@ def find_groups(work, fan_ix, orig_ix, exact, n_works, n_script, mem_off, mem_gr
             raise ValueError("label_of needs one entry per script word")
     L = _lib.load()
     groups = np.zeros(n_groups, dtype=abi.GROUP_DTYPE)
-    cap_c, cap_w = 4096, 1 << 16
-    while True:
-        cells = np.empty(cap_c, dtype=abi.GROUP_CELL_DTYPE)
-        words = np.empty(cap_w, dtype=abi.GROUP_WORD_DTYPE)
-        nc, nw = C.c_uint64(0), C.c_uint64(0)
-        rc = L.fs_groups(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                         abi.ptr(orig, C.c_uint32), abi.ptr(exact, C.c_uint8), n, n_works,
-                         int(n_script), abi.ptr(mem_off, C.c_uint64), abi.ptr(mem_grp, C.c_uint32),
-                         n_groups, abi.ptr(lab, C.c_uint32), n_labels, int(min_words),
-                         int(max_gap), int(min_works), groups.ctypes.data_as(C.c_void_p),
-                         cells.ctypes.data_as(C.c_void_p), cap_c, C.byref(nc),
-                         words.ctypes.data_as(C.c_void_p), cap_w, C.byref(nw))
-        if rc == abi.FS_E_CAPACITY:
-            cap_c, cap_w = max(cap_c, int(nc.value)), max(cap_w, int(nw.value))
-            continue
-        _lib.check(rc, "fs_groups")
-        return groups, cells[:nc.value], words[:nw.value]
+    cells, words = grow(lambda *outs: L.fs_groups(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), abi.ptr(exact, C.c_uint8), n, n_works, int(n_script),
+        abi.ptr(mem_off, C.c_uint64), abi.ptr(mem_grp, C.c_uint32), n_groups,
+        abi.ptr(lab, C.c_uint32), n_labels, int(min_words), int(max_gap), int(min_works),
+        groups.ctypes.data_as(C.c_void_p), *outs),
+        [abi.GROUP_CELL_DTYPE, abi.GROUP_WORD_DTYPE], [4096, 1 << 16], "fs_groups")
+    return groups, cells, words
 
 
 def tables(rows, meta, by='year', min_words=6, max_gap=0, min_works=1, device=0):
@@ -178,21 +170,18 @@ def tables(rows, meta, by='year', min_words=6, max_gap=0, min_works=1, device=0)
     (read_matches) and the metadata rows `meta` (read_meta)."""
     labels = word_labels(rows)
     _, work, fan, orig, _, comb = sort_records(rows)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    return _tables(labels, names, work, fan, orig, comb, n_script, meta, by, min_words, max_gap,
-                   min_works, device)
+    return _tables(labels, work_names(rows), work, fan, orig, comb, n_script_of(orig), meta, by,
+                   min_words, max_gap, min_works, device)
 
 
 def tables_device(mf, meta, by='year', min_words=6, max_gap=0, min_works=1, device=0):
     """tables over a matches.MatchFile, the three labels decoded once per script word; None
     when a script word's records spell one in two ways (tables() then decides)."""
     _, work, fan, orig, _, comb = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     return _tables(labels, list(mf.names), work, fan, orig, comb, n_script, meta, by, min_words,
                    max_gap, min_works, device)
 
@@ -226,31 +215,16 @@ def _tables(labels, names, work, fan, orig, comb, n_script, meta, by, min_words,
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-groups.csv', prefix + '-groups-scenes.csv', prefix + '-groups-words.csv')
+    return prefixed(matches, prefix,
+                    ('-groups.csv', '-groups-scenes.csv', '-groups-words.csv'))
 
 
 def process(args):
     """`ao3.py groups matches meta [--by B] [-o PREFIX] [--min-words M] [--max-gap G]
     [--min-works K] [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
     meta = read_meta(args.meta, args.by)            # (small: always read on the host)
     for row in meta.values():
         keys_of(row, args.by)                       # (a malformed row stops before the GPU)
-    outs = output_names(args.matches, args.output)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, meta, args.by, args.min_words, args.max_gap,
-                                     args.min_works, args.device)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), meta, args.by, args.min_words, args.max_gap,
-                      args.min_works, args.device)
-    for path, head, part in zip(outs, (GROUP_FIELDS, SCENE_FIELDS, WORD_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    opts = (meta, args.by, args.min_words, args.max_gap, args.min_works, args.device)
+    return run(args, (GROUP_FIELDS, SCENE_FIELDS, WORD_FIELDS),
+               output_names(args.matches, args.output), tables, tables_device, opts)

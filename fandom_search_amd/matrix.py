@@ -142,6 +142,7 @@ def device_tables(data_path, ngram_size, device=0):
     import numpy as np
 
     from . import _lib, abi
+    from .command import n_script_of
     from .matches import MatchFile
     from .passages import _ORIG_WORD
     n = int(ngram_size)
@@ -149,7 +150,7 @@ def device_tables(data_path, ngram_size, device=0):
         if mf.outside or not mf.has_header or any('\r' in name for name in mf.names):
             return None
         _, work, fan, orig, _, _ = mf.sorted()
-        n_script = int(orig.max()) + 1 if len(orig) else 0
+        n_script = n_script_of(orig)
         try:
             kept = find_ngrams(work, fan, orig, len(mf.names), n_script, n, device)[2]
         except _lib.FsError as e:
@@ -198,25 +199,20 @@ def find_ngrams(work, fan_ix, orig_ix, n_works, n_script, ngram, device=0):
     import numpy as np
 
     from . import _lib, abi
+    from .command import grow
     work, fan, orig = (abi.as_u32(v) for v in (work, fan_ix, orig_ix))
     n = len(work)
     if not (len(fan) == len(orig) == n):
         raise ValueError("columns of different lengths")
     L = _lib.load()
     starts = np.zeros(int(n_script), dtype=np.uint32)
-    cap = min(n // max(1, int(ngram)) + 1, 4096)
-    while True:
-        found = np.empty(cap, dtype=abi.MATRIX_NGRAM_DTYPE)
-        spans, got = C.c_uint64(0), C.c_uint64(0)
-        rc = L.fs_matrix(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                         abi.ptr(orig, C.c_uint32), n, int(n_works), int(n_script), int(ngram),
-                         abi.ptr(starts, C.c_uint32), found.ctypes.data_as(C.c_void_p), cap,
-                         C.byref(spans), C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_matrix")
-        return starts, int(spans.value), found[:got.value]
+    spans = C.c_uint64(0)
+    found = grow(lambda found, cap, got: L.fs_matrix(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), n, int(n_works), int(n_script), int(ngram),
+        abi.ptr(starts, C.c_uint32), found, cap, C.byref(spans), got),
+        abi.MATRIX_NGRAM_DTYPE, min(n // max(1, int(ngram)) + 1, 4096), "fs_matrix")
+    return starts, int(spans.value), found
 
 
 def matrix_filename(prefix, ngram_size):

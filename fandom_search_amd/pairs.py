@@ -13,13 +13,13 @@ passages, the coverage bitsets and the work x work product come from the GPU (fs
 passage is what `passages` keeps under the same `--min-words` and `--max-gap`.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import _CHAR, _FNAME, _ORIG_WORD, _SCENE, read_matches, sort_records
+from .command import grow, n_script_of, prefixed, run, script_labels, work_names
+from .passages import sort_records
 from .quotes import UNKNOWN_WORD, word_labels
 
 PAIR_FIELDS = ['FAN_WORK_FILENAME_A', 'FAN_WORK_FILENAME_B', 'COVERED_WORDS_A',
@@ -40,19 +40,12 @@ def find_pairs(work, fan_ix, orig_ix, n_works, n_script, min_words=6, max_gap=0,
         raise ValueError("columns of different lengths")
     L = _lib.load()
     works = np.zeros(n_works, dtype=abi.PAIR_WORK_DTYPE)
-    cap = 4096
-    while True:
-        pairs = np.empty(cap, dtype=abi.PAIR_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_pairs(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                        abi.ptr(orig, C.c_uint32), n, n_works, int(n_script), int(min_words),
-                        int(max_gap), int(min_shared), works.ctypes.data_as(C.c_void_p),
-                        pairs.ctypes.data_as(C.c_void_p), cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_pairs")
-        return works, pairs[:got.value]
+    pairs = grow(lambda out, cap, got: L.fs_pairs(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), n, n_works, int(n_script), int(min_words), int(max_gap),
+        int(min_shared), works.ctypes.data_as(C.c_void_p), out, cap, got),
+        abi.PAIR_DTYPE, 4096, "fs_pairs")
+    return works, pairs
 
 
 def tables(rows, min_words=6, max_gap=0, min_shared=6, device=0):
@@ -60,21 +53,18 @@ def tables(rows, min_words=6, max_gap=0, min_shared=6, device=0):
     (read_matches)."""
     labels = word_labels(rows)
     _, work, fan, orig, _, _ = sort_records(rows)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    return _tables(labels, names, work, fan, orig, n_script, min_words, max_gap, min_shared,
-                   device)
+    return _tables(labels, work_names(rows), work, fan, orig, n_script_of(orig), min_words,
+                   max_gap, min_shared, device)
 
 
 def tables_device(mf, min_words=6, max_gap=0, min_shared=6, device=0):
     """tables over a matches.MatchFile, the three labels decoded once per script word; None
     when a script word's records spell one in two ways (tables() then decides)."""
     _, work, fan, orig, _, _ = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     return _tables(labels, list(mf.names), work, fan, orig, n_script, min_words, max_gap,
                    min_shared, device)
 
@@ -103,28 +93,12 @@ def _tables(labels, names, work, fan, orig, n_script, min_words, max_gap, min_sh
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-pairs.csv', prefix + '-pairs-works.csv')
+    return prefixed(matches, prefix, ('-pairs.csv', '-pairs-works.csv'))
 
 
 def process(args):
     """`ao3.py pairs matches [-o PREFIX] [--min-words M] [--max-gap G] [--min-shared S]
     [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, args.min_words, args.max_gap, args.min_shared,
-                                     args.device)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.min_shared,
-                      args.device)
-    for path, head, part in zip(outs, (PAIR_FIELDS, WORK_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    opts = (args.min_words, args.max_gap, args.min_shared, args.device)
+    return run(args, (PAIR_FIELDS, WORK_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

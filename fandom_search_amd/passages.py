@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, abi
+from .command import grow, write_tables
 from .search import new_record_structure
 
 FIELDS = new_record_structure['fields']
@@ -41,18 +42,10 @@ def find_passages(work, fan_ix, orig_ix, dist, comb, min_words=6, max_gap=0, dev
         raise ValueError("columns of different lengths")
     L = _lib.load()
     cap = n // max(1, int(min_words)) + 1          # passages never outnumber this
-    while True:
-        out = np.empty(cap, dtype=abi.PASSAGE_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_passages(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                           abi.ptr(orig, C.c_uint32), abi.ptr(dist, C.c_double),
-                           abi.ptr(comb, C.c_double), n, int(min_words), int(max_gap),
-                           out.ctypes.data_as(C.c_void_p), cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_passages")
-        return out[:got.value]
+    return grow(lambda out, cap, got: L.fs_passages(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), abi.ptr(dist, C.c_double), abi.ptr(comb, C.c_double), n,
+        int(min_words), int(max_gap), out, cap, got), abi.PASSAGE_DTYPE, cap, "fs_passages")
 
 
 def _distance(text):
@@ -150,8 +143,5 @@ def process(args):
     from .matches import reader_of
     out = args.output or output_name(args.matches)
     body = body_rows(args.matches, reader_of(args), args.min_words, args.max_gap, args.device)
-    with open(out, 'w', newline='', encoding='utf-8') as fh:
-        w = csv.writer(fh)
-        w.writerow(PASSAGE_FIELDS)
-        w.writerows(body)
+    write_tables([out], [PASSAGE_FIELDS], [body])
     return out

@@ -13,14 +13,13 @@ passages, the distinct counts and the regions come from the GPU (fs_quotes).  A 
 between its first and last record, bridged ones included.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import (_CHAR, _FNAME, _ORIG_IX, _ORIG_WORD, _SCENE, read_matches,
-                       sort_records)
+from .command import grow, n_script_of, prefixed, run, script_labels, work_names
+from .passages import _CHAR, _ORIG_IX, _ORIG_WORD, _SCENE, sort_records
 
 REGION_FIELDS = ['ORIGINAL_SCRIPT_WORD_START', 'ORIGINAL_SCRIPT_WORD_END', 'WORDS',
                  'ORIGINAL_SCRIPT_CHARACTER', 'ORIGINAL_SCRIPT_SCENE', 'PASSAGES', 'WORKS',
@@ -43,19 +42,12 @@ def find_quotes(work, fan_ix, orig_ix, comb, n_works, n_script, min_words=6, max
     L = _lib.load()
     words = np.zeros(n_script, dtype=abi.QUOTE_WORD_DTYPE)
     cap = min(n, (n_script + 1) // 2, 4096)         # regions lie a word apart at least
-    while True:
-        regions = np.empty(cap, dtype=abi.QUOTE_REGION_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_quotes(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                         abi.ptr(orig, C.c_uint32), abi.ptr(comb, C.c_double), n, int(n_works),
-                         n_script, int(min_words), int(max_gap), int(min_works),
-                         words.ctypes.data_as(C.c_void_p), regions.ctypes.data_as(C.c_void_p),
-                         cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_quotes")
-        return words, regions[:got.value]
+    regions = grow(lambda out, cap, got: L.fs_quotes(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), abi.ptr(comb, C.c_double), n, int(n_works), n_script,
+        int(min_words), int(max_gap), int(min_works), words.ctypes.data_as(C.c_void_p), out,
+        cap, got), abi.QUOTE_REGION_DTYPE, cap, "fs_quotes")
+    return words, regions
 
 
 def word_labels(rows):
@@ -79,21 +71,18 @@ def tables(rows, min_words=6, max_gap=0, min_works=1, device=0):
     (read_matches)."""
     labels = word_labels(rows)
     _, work, fan, orig, _, comb = sort_records(rows)
-    n_works = len(set(r[_FNAME] for r in rows))
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    return _tables(labels, work, fan, orig, comb, n_works, n_script, min_words, max_gap,
-                   min_works, device)
+    return _tables(labels, work, fan, orig, comb, len(work_names(rows)), n_script_of(orig),
+                   min_words, max_gap, min_works, device)
 
 
 def tables_device(mf, min_words=6, max_gap=0, min_works=1, device=0):
     """tables over a matches.MatchFile, the three labels decoded once per script word; None
     when a script word's records spell one in two ways (tables() then decides)."""
     _, work, fan, orig, _, comb = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     return _tables(labels, work, fan, orig, comb, len(mf.names), n_script, min_words, max_gap,
                    min_works, device)
 
@@ -122,28 +111,12 @@ def _tables(labels, work, fan, orig, comb, n_works, n_script, min_words, max_gap
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-quotes.csv', prefix + '-quotes-words.csv')
+    return prefixed(matches, prefix, ('-quotes.csv', '-quotes-words.csv'))
 
 
 def process(args):
     """`ao3.py quotes matches [-o PREFIX] [--min-words M] [--max-gap G] [--min-works K]
     [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, args.min_words, args.max_gap, args.min_works,
-                                     args.device)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.min_works,
-                      args.device)
-    for path, head, part in zip(outs, (REGION_FIELDS, WORD_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    opts = (args.min_words, args.max_gap, args.min_works, args.device)
+    return run(args, (REGION_FIELDS, WORD_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

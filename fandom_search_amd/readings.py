@@ -16,14 +16,13 @@ The passages, the grouping, the distinct counts and the ranking come from the GP
 each reading's first passage are decoded to text.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import (_CHAR, _FAN_WORD, _FNAME, _ORIG_WORD, _SCENE, read_matches,
-                       sort_records)
+from .command import grow, n_script_of, prefixed, run, script_labels, work_names
+from .passages import _FAN_WORD, sort_records
 from .quotes import UNKNOWN_WORD, word_labels
 from .variants import fold_key, merge_spellings
 
@@ -45,22 +44,14 @@ def find_readings(work, fan_ix, orig_ix, spell, n_works, n_script, n_spell, min_
     if not (len(fan) == len(orig) == len(spell) == n):
         raise ValueError("columns of different lengths")
     L = _lib.load()
-    cap_r = cap_s = n // max(1, int(min_words)) + 1     # passages never outnumber this
-    while True:
-        readings = np.empty(cap_r, dtype=abi.READING_DTYPE)
-        spans = np.empty(cap_s, dtype=abi.READING_SPAN_DTYPE)
-        got_r, got_s, got_p = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = L.fs_readings(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                           abi.ptr(orig, C.c_uint32), abi.ptr(spell, C.c_uint32), n,
-                           int(n_works), int(n_script), int(n_spell), int(min_words),
-                           int(max_gap), readings.ctypes.data_as(C.c_void_p), cap_r,
-                           spans.ctypes.data_as(C.c_void_p), cap_s, C.byref(got_r),
-                           C.byref(got_s), C.byref(got_p))
-        if rc == abi.FS_E_CAPACITY:
-            cap_r, cap_s = int(got_r.value), int(got_s.value)
-            continue
-        _lib.check(rc, "fs_readings")
-        return readings[:got_r.value], spans[:got_s.value], int(got_p.value)
+    cap = n // max(1, int(min_words)) + 1               # passages never outnumber this
+    got_p = C.c_uint64(0)
+    readings, spans = grow(lambda r, cap_r, got_r, s, cap_s, got_s: L.fs_readings(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), abi.ptr(spell, C.c_uint32), n, int(n_works), int(n_script),
+        int(n_spell), int(min_words), int(max_gap), r, cap_r, s, cap_s, got_r, got_s,
+        C.byref(got_p)), [abi.READING_DTYPE, abi.READING_SPAN_DTYPE], [cap, cap], "fs_readings")
+    return readings, spans, int(got_p.value)
 
 
 def tables(rows, min_words=6, max_gap=0, top=10, min_works=1, fold_case=False, device=0):
@@ -69,13 +60,12 @@ def tables(rows, min_words=6, max_gap=0, top=10, min_works=1, fold_case=False, d
     labels = word_labels(rows)
     order, work, fan, orig, _, _ = sort_records(rows)
     spell, _, shown = merge_spellings([r[_FAN_WORD] for r in rows], fold_case)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
-    n_script = int(orig.max()) + 1 if len(orig) else 0
 
     def fan_words(recs):
         return [rows[i][_FAN_WORD] for i in recs]
-    return _tables(labels, names, fan_words, order, work, fan, orig, spell[order], n_script,
-                   len(shown), min_words, max_gap, top, min_works, fold_case, device)
+    return _tables(labels, work_names(rows), fan_words, order, work, fan, orig, spell[order],
+                   n_script_of(orig), len(shown), min_words, max_gap, top, min_works, fold_case,
+                   device)
 
 
 def tables_device(mf, min_words=6, max_gap=0, top=10, min_works=1, fold_case=False, device=0):
@@ -84,11 +74,10 @@ def tables_device(mf, min_words=6, max_gap=0, top=10, min_works=1, fold_case=Fal
     passage; None when a script word's records spell a label in two ways (tables() then
     decides)."""
     order, work, fan, orig, _, _ = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     raw, first = mf.intern(_FAN_WORD)
     remap, _, shown = merge_spellings(mf.text(_FAN_WORD, first), fold_case)
     spell = np.take(remap, raw)[order] if mf.n else np.zeros(0, dtype=np.uint32)
@@ -140,27 +129,12 @@ def _tables(labels, names, fan_words, order, work, fan, orig, spell, n_script, n
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-readings.csv', prefix + '-readings-spans.csv')
+    return prefixed(matches, prefix, ('-readings.csv', '-readings-spans.csv'))
 
 
 def process(args):
     """`ao3.py readings matches [-o PREFIX] [--min-words M] [--max-gap G] [--top K]
     [--min-works W] [--fold-case] [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
     opts = (args.min_words, args.max_gap, args.top, args.min_works, args.fold_case, args.device)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, *opts)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), *opts)
-    for path, head, part in zip(outs, (READING_FIELDS, SPAN_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    return run(args, (READING_FIELDS, SPAN_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

@@ -14,14 +14,13 @@ passage in the chain come from the GPU (fs_retellings); choosing and ordering th
 plumbing, and only the fields the listed rows show are decoded to text.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import (_CHAR, _FAN_WORD, _FNAME, _ORIG_WORD, _SCENE, read_matches,
-                       sort_records)
+from .command import grow, n_script_of, prefixed, run, work_names
+from .passages import _CHAR, _FAN_WORD, _ORIG_WORD, _SCENE, sort_records
 from .quotes import word_labels
 
 WORK_FIELDS = ['FAN_WORK_FILENAME', 'PASSAGES', 'PASSAGE_WORDS', 'CHAIN_PASSAGES', 'CHAIN_WORDS',
@@ -43,19 +42,12 @@ def find_retellings(work, fan_ix, orig_ix, n_works, min_words=6, max_gap=0, devi
         raise ValueError("columns of different lengths")
     L = _lib.load()
     out = np.empty(int(n_works), dtype=abi.RETELLING_DTYPE)
-    cap = min(n // max(1, int(min_words)), 4096)
-    while True:
-        found = np.empty(cap, dtype=abi.RETELLING_PASSAGE_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_retellings(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                             abi.ptr(orig, C.c_uint32), n, int(n_works), int(min_words),
-                             int(max_gap), out.ctypes.data_as(C.c_void_p),
-                             found.ctypes.data_as(C.c_void_p), cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_retellings")
-        return out, found[:got.value]
+    found = grow(lambda found, cap, got: L.fs_retellings(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), n, int(n_works), int(min_words), int(max_gap),
+        out.ctypes.data_as(C.c_void_p), found, cap, got),
+        abi.RETELLING_PASSAGE_DTYPE, min(n // max(1, int(min_words)), 4096), "fs_retellings")
+    return out, found
 
 
 def tables(rows, min_words=6, max_gap=0, min_passages=2, min_share=0, device=0):
@@ -63,11 +55,10 @@ def tables(rows, min_words=6, max_gap=0, min_passages=2, min_share=0, device=0):
     (read_matches)."""
     word_labels(rows)                   # a script word with two labels is an error
     order, work, fan, orig, _, _ = sort_records(rows)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
 
     def field(column, recs):
         return [rows[i][column] for i in recs]
-    return _tables(names, field, order, work, fan, orig, min_words, max_gap, min_passages,
+    return _tables(work_names(rows), field, order, work, fan, orig, min_words, max_gap, min_passages,
                    min_share, device)
 
 
@@ -75,7 +66,7 @@ def tables_device(mf, min_words=6, max_gap=0, min_passages=2, min_share=0, devic
     """tables over a matches.MatchFile, decoding only the fields of the listed works' passages;
     None when a script word's records spell a label in two ways (tables() then decides)."""
     order, work, fan, orig, _, _ = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
+    n_script = n_script_of(orig)
     for column in (_ORIG_WORD, _CHAR, _SCENE) if mf.n else ():
         if mf.label_rows(column, n_script)[1]:
             return None
@@ -133,27 +124,12 @@ def _tables(names, field, order, work, fan, orig, min_words, max_gap, min_passag
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-retellings.csv', prefix + '-retellings-passages.csv')
+    return prefixed(matches, prefix, ('-retellings.csv', '-retellings-passages.csv'))
 
 
 def process(args):
     """`ao3.py retellings matches [-o PREFIX] [--min-words M] [--max-gap G] [--min-passages P]
     [--min-share S] [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
     opts = (args.min_words, args.max_gap, args.min_passages, args.min_share, args.device)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, *opts)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), *opts)
-    for path, head, part in zip(outs, (WORK_FIELDS, PASSAGE_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    return run(args, (WORK_FIELDS, PASSAGE_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

@@ -16,14 +16,14 @@ FAN_WORK_WORD_INDEX) order of each file and writing are host plumbing; the passa
 interval join and every figure come from the GPU (fs_sources).
 """
 
-import csv
 import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import _CHAR, _FAN_WORD, _FNAME, _ORIG_WORD, _SCENE, read_matches, sort_records
+from .command import grow, prefixed, work_names, write_tables
+from .passages import _CHAR, _FAN_WORD, _ORIG_WORD, _SCENE, read_matches, sort_records
 
 PASSAGE_FIELDS = ['SCRIPT', 'FAN_WORK_FILENAME', 'FAN_WORK_WORD_START', 'FAN_WORK_WORD_END',
                   'ORIGINAL_SCRIPT_WORD_START', 'ORIGINAL_SCRIPT_WORD_END', 'MATCHED_WORDS',
@@ -60,20 +60,11 @@ def find_sources(files, n_works, min_words=6, max_gap=0, device=0):
     L = _lib.load()
     scripts = np.zeros(K, dtype=abi.SOURCE_SCRIPT_DTYPE)
     pairs = np.zeros(K * (K - 1) // 2, dtype=abi.SOURCE_PAIR_DTYPE)
-    cap_p = cap_w = 4096
-    while True:
-        passages = np.empty(cap_p, dtype=abi.SOURCE_PASSAGE_DTYPE)
-        works = np.empty(cap_w, dtype=abi.SOURCE_WORK_DTYPE)
-        n_p, n_w = C.c_uint64(0), C.c_uint64(0)
-        rc = L.fs_sources(int(device), cols, K, int(n_works), int(min_words), int(max_gap),
-                          passages.ctypes.data_as(C.c_void_p), cap_p, C.byref(n_p),
-                          works.ctypes.data_as(C.c_void_p), cap_w, C.byref(n_w),
-                          scripts.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p))
-        if rc == abi.FS_E_CAPACITY:
-            cap_p, cap_w = max(cap_p, int(n_p.value)), max(cap_w, int(n_w.value))
-            continue
-        _lib.check(rc, "fs_sources")
-        return passages[:n_p.value], works[:n_w.value], scripts, pairs
+    passages, works = grow(lambda *outs: L.fs_sources(
+        int(device), cols, K, int(n_works), int(min_words), int(max_gap), *outs,
+        scripts.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p)),
+        [abi.SOURCE_PASSAGE_DTYPE, abi.SOURCE_WORK_DTYPE], [4096, 4096], "fs_sources")
+    return passages, works, scripts, pairs
 
 
 def script_names(paths, names=None):
@@ -106,7 +97,7 @@ class _PythonFile:
 
     def __init__(self, path):
         self.rows = read_matches(path)
-        self.names = list(dict.fromkeys(r[_FNAME] for r in self.rows))
+        self.names = work_names(self.rows)
 
     def sorted(self):
         return sort_records(self.rows)
@@ -200,7 +191,7 @@ def _rows_of(found, files, orders, names, work_names):
 
 
 def output_names(prefix):
-    return tuple(prefix + s for s in SUFFIXES)
+    return prefixed(None, prefix, SUFFIXES)
 
 
 def process(args):
@@ -217,10 +208,5 @@ def process(args):
             if hasattr(f, 'close'):
                 f.close()
     outs = output_names(args.output)
-    for path, head, part in zip(outs, (PASSAGE_FIELDS, WORK_FIELDS, SCRIPT_FIELDS, PAIR_FIELDS),
-                                body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
+    write_tables(outs, (PASSAGE_FIELDS, WORK_FIELDS, SCRIPT_FIELDS, PAIR_FIELDS), body)
     return outs

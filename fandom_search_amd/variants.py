@@ -14,13 +14,13 @@ a dict over the rows.  The group-by, the distinct counts and the ranking come fr
 order: nothing here needs them sorted.
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
-from .passages import _FAN_WORD, _FNAME, _ORIG_IX, _ORIG_WORD, _CHAR, _SCENE, read_matches
+from .command import grow, n_script_of, prefixed, run, script_labels
+from .passages import _FAN_WORD, _FNAME, _ORIG_IX
 from .quotes import word_labels
 
 CELL_FIELDS = ['ORIGINAL_SCRIPT_WORD_INDEX', 'ORIGINAL_SCRIPT_WORD', 'ORIGINAL_SCRIPT_CHARACTER',
@@ -39,19 +39,12 @@ def find_variants(work, orig_ix, spell, n_works, n_script, n_spell, device=0):
         raise ValueError("columns of different lengths")
     L = _lib.load()
     words = np.zeros(n_script, dtype=abi.VARIANT_WORD_DTYPE)
-    cap = n                                         # a cell has a record
-    while True:
-        cells = np.empty(cap, dtype=abi.VARIANT_CELL_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_variants(int(device), abi.ptr(work, C.c_uint32), abi.ptr(orig, C.c_uint32),
-                           abi.ptr(spell, C.c_uint32), n, int(n_works), n_script, int(n_spell),
-                           words.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p),
-                           cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_variants")
-        return words, cells[:got.value]
+    cells = grow(lambda out, cap, got: L.fs_variants(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(orig, C.c_uint32),
+        abi.ptr(spell, C.c_uint32), n, int(n_works), n_script, int(n_spell),
+        words.ctypes.data_as(C.c_void_p), out, cap, got),
+        abi.VARIANT_CELL_DTYPE, n, "fs_variants")      # (a cell has a record)
+    return words, cells
 
 
 def fold_key(text, fold_case):
@@ -84,8 +77,7 @@ def tables(rows, top=10, min_records=1, fold_case=False, device=0):
     if len(rows) and (orig.min() < 0 or orig.max() >= 1 << 32):
         raise ValueError("word indices outside 0 .. 2^32 - 1")
     spell, ids, shown = merge_spellings([r[_FAN_WORD] for r in rows], fold_case)
-    n_script = int(orig.max()) + 1 if len(orig) else 0
-    return _tables(labels, ids, shown, work, orig, spell, len(work_of), n_script, top,
+    return _tables(labels, ids, shown, work, orig, spell, len(work_of), n_script_of(orig), top,
                    min_records, fold_case, device)
 
 
@@ -93,11 +85,10 @@ def tables_device(mf, top=10, min_records=1, fold_case=False, device=0):
     """tables over a matches.MatchFile: the fan words numbered on the device, one text decoded
     per spelling and three labels per script word; None when a script word's records spell a
     label in two ways (tables() then decides)."""
-    n_script = int(mf.orig.max()) + 1 if mf.n else 0
-    cols = [mf.labels(c, n_script) for c in (_ORIG_WORD, _CHAR, _SCENE)]
-    if any(c is None for c in cols):
+    n_script = n_script_of(mf.orig)
+    labels = script_labels(mf, n_script)
+    if labels is None:
         return None
-    labels = {o: (w, cols[1][o], cols[2][o]) for o, w in cols[0].items()}
     raw, first = mf.intern(_FAN_WORD)
     remap, ids, shown = merge_spellings(mf.text(_FAN_WORD, first), fold_case)
     spell = np.take(remap, raw) if mf.n else np.zeros(0, dtype=np.uint32)
@@ -140,27 +131,12 @@ def _tables(labels, ids, shown, work, orig, spell, n_works, n_script, top, min_r
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-variants.csv', prefix + '-variants-words.csv')
+    return prefixed(matches, prefix, ('-variants.csv', '-variants-words.csv'))
 
 
 def process(args):
     """`ao3.py variants matches [-o PREFIX] [--top K] [--min-records R] [--fold-case]
     [--device D] [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, args.top, args.min_records, args.fold_case, args.device)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), args.top, args.min_records, args.fold_case,
-                      args.device)
-    for path, head, part in zip(outs, (CELL_FIELDS, WORD_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    opts = (args.top, args.min_records, args.fold_case, args.device)
+    return run(args, (CELL_FIELDS, WORD_FIELDS), output_names(args.matches, args.output),
+               tables, tables_device, opts)

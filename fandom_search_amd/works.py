@@ -13,14 +13,14 @@ group and once with its character.  Scene and character labels come from the rec
 id is its rank by the smallest ORIGINAL_SCRIPT_WORD_INDEX it occurs at (script order).
 """
 
-import csv
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, abi
+from .command import grow, n_script_of, prefixed, run, work_names
 from .format import THRESHOLDS, THRESHOLD_NAMES
-from .passages import _CHAR, _FNAME, _SCENE, read_matches, sort_records
+from .passages import _CHAR, _SCENE, sort_records
 
 WORK_FIELDS = (['FAN_WORK_FILENAME', 'MATCHED_WORDS', 'EXACT_WORDS'] + THRESHOLD_NAMES +
                ['DISTINCT_SCRIPT_WORDS', 'PASSAGES', 'PASSAGE_WORDS', 'LONGEST_PASSAGE',
@@ -54,42 +54,26 @@ def summarise(work, fan_ix, orig_ix, comb, n_works, n_script, group_of=None, n_g
     out = np.zeros(n_works, dtype=abi.WORK_DTYPE)
     counts = np.zeros((n_works, len(thr) + 1), dtype=np.uint32)
     most = min(n, n_works * n_groups)               # a record makes at most one cell
-    cap = min(most, max(4096, n // 8))
-    while True:
-        cells = np.empty(cap, dtype=abi.WORK_CELL_DTYPE)
-        got = C.c_uint64(0)
-        rc = L.fs_works(int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
-                        abi.ptr(orig, C.c_uint32), abi.ptr(comb, C.c_double), n, n_works,
-                        int(n_script), abi.ptr(gmap, C.c_uint32), n_groups, int(min_words),
-                        int(max_gap), abi.ptr(thr, C.c_double), len(thr),
-                        out.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
-                        cells.ctypes.data_as(C.c_void_p), cap, C.byref(got))
-        if rc == abi.FS_E_CAPACITY:
-            cap = int(got.value)
-            continue
-        _lib.check(rc, "fs_works")
-        return out, counts, cells[:got.value]
+    cells = grow(lambda cells, cap, got: L.fs_works(
+        int(device), abi.ptr(work, C.c_uint32), abi.ptr(fan, C.c_uint32),
+        abi.ptr(orig, C.c_uint32), abi.ptr(comb, C.c_double), n, n_works, int(n_script),
+        abi.ptr(gmap, C.c_uint32), n_groups, int(min_words), int(max_gap),
+        abi.ptr(thr, C.c_double), len(thr), out.ctypes.data_as(C.c_void_p),
+        counts.ctypes.data_as(C.c_void_p), cells, cap, got),
+        abi.WORK_CELL_DTYPE, min(most, max(4096, n // 8)), "fs_works")
+    return out, counts, cells
 
 
 def label_groups(orig, labels, what):
     """(group_of[n_script], names): the labels numbered by the smallest script word index they
     occur at; script words without a record get group 0.  ValueError for a script word that
     carries two labels."""
-    n_script = int(orig.max()) + 1 if len(orig) else 0
     label_at = {}
     for o, lab in zip(orig.tolist(), labels):
         if label_at.setdefault(o, lab) != lab:
             raise ValueError("script word %d has two %ss, %r and %r: records of different "
                              "scripts in one file?" % (o, what, label_at[o], lab))
-    ids, names = {}, []
-    group_of = np.zeros(n_script, dtype=np.uint32)
-    for o in sorted(label_at):
-        lab = label_at[o]
-        if lab not in ids:
-            ids[lab] = len(names)
-            names.append(lab)
-        group_of[o] = ids[lab]
-    return group_of, names
+    return groups_of_labels(label_at, n_script_of(orig))
 
 
 def groups_of_labels(label_at, n_script):
@@ -109,12 +93,11 @@ def tables(rows, min_words=6, max_gap=0, device=0):
     """(works, scenes, characters): the three CSVs' rows, without headers, for the records
     `rows` (read_matches)."""
     order, work, fan, orig, _, comb = sort_records(rows)
-    names = list(dict.fromkeys(r[_FNAME] for r in rows))
     srt = [rows[i] for i in order]
-    n_script = int(orig.max()) + 1 if len(orig) else 0
     groups = [label_groups(orig, [r[col] for r in srt], what)
               for col, what in ((_SCENE, 'scene'), (_CHAR, 'character'))]
-    return _tables(names, work, fan, orig, comb, n_script, groups, min_words, max_gap, device)
+    return _tables(work_names(rows), work, fan, orig, comb, n_script_of(orig), groups, min_words,
+                   max_gap, device)
 
 
 def tables_device(mf, min_words=6, max_gap=0, device=0):
@@ -122,7 +105,7 @@ def tables_device(mf, min_words=6, max_gap=0, device=0):
     word's records spell a label in two ways (tables() then says what is wrong, or finds the
     two spellings equal)."""
     _, work, fan, orig, _, comb = mf.sorted()
-    n_script = int(orig.max()) + 1 if len(orig) else 0
+    n_script = n_script_of(orig)
     groups = []
     for col in (_SCENE, _CHAR):
         label_at = mf.labels(col, n_script)
@@ -157,26 +140,13 @@ def _tables(names, work, fan, orig, comb, n_script, groups, min_words, max_gap, 
 
 
 def output_names(matches, prefix=None):
-    if prefix is None:
-        prefix = matches[:-4] if matches.endswith('.csv') else matches
-    return (prefix + '-works.csv', prefix + '-works-scenes.csv', prefix + '-works-characters.csv')
+    return prefixed(matches, prefix,
+                    ('-works.csv', '-works-scenes.csv', '-works-characters.csv'))
 
 
 def process(args):
     """`ao3.py works matches [-o PREFIX] [--min-words M] [--max-gap G] [--device D]
     [--reader {device,python}]`."""
-    from .matches import MatchFile, reader_of
-    outs = output_names(args.matches, args.output)
-    body = None
-    if reader_of(args) == 'device':
-        with MatchFile(args.matches, args.device) as mf:
-            if not mf.outside:
-                body = tables_device(mf, args.min_words, args.max_gap, args.device)
-    if body is None:        # the python reader, or a file the device reader does not take
-        body = tables(read_matches(args.matches), args.min_words, args.max_gap, args.device)
-    for path, head, part in zip(outs, (WORK_FIELDS, SCENE_FIELDS, CHARACTER_FIELDS), body):
-        with open(path, 'w', newline='', encoding='utf-8') as fh:
-            w = csv.writer(fh)
-            w.writerow(head)
-            w.writerows(part)
-    return outs
+    return run(args, (WORK_FIELDS, SCENE_FIELDS, CHARACTER_FIELDS),
+               output_names(args.matches, args.output), tables, tables_device,
+               (args.min_words, args.max_gap, args.device))
