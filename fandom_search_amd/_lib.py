@@ -24,6 +24,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_readings", "fs_readings_times",
            "fs_retellings", "fs_retellings_rows", "fs_retellings_times",
+           "fs_alignments", "fs_alignments_rows", "fs_alignments_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_companions", "fs_companions_rows", "fs_companions_times",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
@@ -45,7 +46,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "pairs", "companions", "transitions", "sources", "matrix",
+TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "transitions", "sources", "matrix",
          "clusters", "groups")
 
 
@@ -259,6 +260,14 @@ def load():
     L.fs_retellings_rows.restype = C.c_int
     L.fs_retellings_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_alignments.restype = C.c_int
+    L.fs_alignments.argtypes = [C.c_int, u32p, u32p, u32p, C.POINTER(C.c_double), C.c_uint64,
+                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_alignments_rows.restype = C.c_int
+    L.fs_alignments_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p,
+                                     C.c_void_p, C.c_uint64, u64p]
     L.fs_matrix.restype = C.c_int
     L.fs_matrix.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                             C.c_uint32, u32p, C.c_void_p, C.c_uint64, u64p, u64p]

@@ -266,6 +266,18 @@ RETELLING_PASSAGE_DTYPE = np.dtype([("first", np.uint64), ("n_words", np.uint32)
 assert RETELLING_PASSAGE_DTYPE.itemsize == 48
 RETELLINGS_MS_NAMES = ("passages", "bins", "chains", "trace", "write", "total")
 
+# fs_alignment 56 bytes
+ALIGNMENT_DTYPE = np.dtype([("first", np.uint64), ("last", np.uint64), ("n_words", np.uint32),
+                            ("n_exact", np.uint32), ("score", np.uint32),
+                            ("fan_skipped", np.uint32), ("orig_skipped", np.uint32),
+                            ("pieces", np.uint32), ("tree_records", np.uint32),
+                            ("reserved", np.uint32), ("path_at", np.uint64)])
+assert ALIGNMENT_DTYPE.itemsize == 56
+FS_ALIGNMENTS_MAX_REACH = 63
+FS_ALIGNMENTS_MAX_MATCH = 16
+FS_ALIGNMENTS_MAX_GAP = 16
+ALIGNMENTS_MS_NAMES = ("segments", "bins", "chain", "keep", "trace", "total")
+
 # fs_matrix_ngram 8 bytes
 FS_MATRIX_MAX_BYTES = 1 << 30
 MATRIX_NGRAM_DTYPE = np.dtype([("work", np.uint32), ("start", np.uint32)])

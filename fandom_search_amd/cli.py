@@ -16,7 +16,8 @@ which relates the quoted stretches of the script by the works quoting both
 (fandom_search_amd/companions.py), and `transitions`, which counts which stretch the works
 quote next after each stretch (fandom_search_amd/transitions.py), and `sources`, which joins
 the match files of several scripts and says which script each fan passage quotes
-(fandom_search_amd/sources.py).  The
+(fandom_search_amd/sources.py), and `alignments`, which aligns every fan work against the script
+with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignments.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -373,6 +374,39 @@ def build_parser():
     return parser
 
 
+def full_parser():
+    """The parser `ao3.py` runs: build_parser(), whose surface tests/golden/cli_surface.json pins
+    as it stands, and behind it the commands added since, each with a pinned surface of its own
+    (`alignments`: tests/golden/alignments_cli.json)."""
+    parser = build_parser()
+    subparsers = parser._subparsers._group_actions[0]
+    subparsers.help = subparsers.help.replace(' or validate', ', alignments or validate')
+
+    _analysis(subparsers, 'alignments',
+              'aligns every fan work against the script with gaps: quotes with '
+              'inserted or dropped words, or a stray record between their halves, '
+              'that `passages` breaks in two; per alignment its words, score and '
+              'skipped words, per work what it gains over its passages',
+              'prefix of the two csv files, PREFIX-alignments.csv and '
+              'PREFIX-alignments-works.csv (default: the input name '
+              'without .csv)',
+              [(lambda a: (a.min_words < 1 or a.match < 1 or not 0 <= a.reach <= 63
+                           or not 0 <= a.gap <= 16 or a.match > 16),
+                '--min-words and --match must be at least 1, --reach from 0 to 63, --gap '
+                'from 0 to 16, --match at most 16')],
+              spans=False,
+              last=[_own('--min-words', default=6, type=int,
+                         help='fewest matched words an alignment has, default 6'),
+                    _own('--reach', default=4, type=int,
+                         help='most words a link skips on either side, 0 to 63, '
+                              'default 4'),
+                    _own('--match', default=2, type=int,
+                         help='what a matched word scores, 1 to 16, default 2'),
+                    _own('--gap', default=1, type=int,
+                         help='what a skipped word costs, 0 to 16, default 1')])
+    return parser
+
+
 def _validate(args):
     from . import search
     return search.validate_cmd(args)
@@ -424,7 +458,7 @@ def _command(name, checks, args):
 
 
 def main(argv=None):
-    parser = build_parser()
+    parser = full_parser()
     args = parser.parse_args(argv)
     if hasattr(args, 'func'):
         args.func(args)

@@ -657,6 +657,29 @@ class ScriptIndex(object):
                           [abi.RETELLING_PASSAGE_DTYPE], [cap], out_ptrs,
                           "passage buffer too small")
 
+    def alignments_device(self, rows_ptr, n_rows, min_words=6, reach=4, match=2, gap=1,
+                          out_ptrs=None, caps=None):
+        """`alignments` over device-resident fs_row records sorted by (work, fan_ix) (after a
+        search or a gather; fs_alignments_rows): the kept alignments in root order and the
+        record indices of their paths.  Without `out_ptrs`: (abi.ALIGNMENT_DTYPE alignments,
+        uint32 path records) on the host.  With `out_ptrs` = device addresses (alignments, a
+        buffer of caps[0]; path records, a buffer of caps[1]): (alignments, path records)
+        written; FsError(FS_E_CAPACITY) with .required = both counts when a buffer is too small
+        (nothing is written then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+
+        def call(_, grown, caps, counts):
+            return L.fs_alignments_rows(self._h, C.c_void_p(rows_ptr), int(n_rows),
+                                        int(min_words), int(reach), int(match), int(gap),
+                                        C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]),
+                                        C.c_void_p(grown[1]), int(caps[1]), C.byref(counts[1]))
+        caps = caps or ((0, 0) if out_ptrs is not None else
+                        (min(int(n_rows) // max(1, int(min_words)), 4096),
+                         min(int(n_rows), 1 << 16)))
+        return _rows_call("fs_alignments_rows", call, [], [abi.ALIGNMENT_DTYPE, np.uint32], caps,
+                          out_ptrs, "alignment or path buffer too small")
+
     def matrix_device(self, rows_ptr, n_rows, n_works, n_script, ngram=6, out_ptrs=None,
                       cap=None):
         """The n-grams of `matrix` over device-resident fs_row records sorted by

@@ -994,6 +994,66 @@ int fs_sources(int device, const fs_source_cols* files, uint32_t n_files, uint32
  * tools/sources_bench.py. */
 int fs_sources_times(double* ms);
 
+/* `ao3.py alignments`: quotes with inserted or dropped words, a gapped local alignment of every
+ * fan work against the script.  Records sorted by (work, fan_ix) as for fs_passages (comb: their
+ * BEST_COMBINED_DISTANCE).  With R = reach, S = match, P = gap, all integers:
+ *  - For records j < i of one work let df = fan_ix(i) - fan_ix(j) and do = orig_ix(i) -
+ *    orig_ix(j), signed.  j may precede i when 1 <= df <= R + 1 and 1 <= do <= R + 1; the link
+ *    costs P * ((df - 1) + (do - 1)).  j need not be i - 1: records between them are skipped.
+ *  - best(i) = S + max(0, max over the j that may precede i of best(j) - cost(j, i)).
+ *  - prev(i) is the j at that maximum when it is above 0, the largest j (the nearest record) on
+ *    a tie; otherwise i is a root.  root(i) = root(prev(i)), or i for a root.
+ *  - The records of one root are a tree.  Its peak is its record with the largest best, the
+ *    smallest index on a tie; its alignment is the path from the root to the peak along prev.
+ *    The tree's other records are side records: counted, not reported as alignments.
+ *  - An alignment is kept when its path has at least min_words records; the kept alignments are
+ *    listed in root order, that is by (work, first fan word).
+ * Every output is an integer below 2^32; candidates are compared as (value, j) and peaks as
+ * (best, ~i), total orders: no schedule changes the result.  At reach 0 every link costs 0, and
+ * on records without two at one fan index the kept alignments are the passages of fs_passages
+ * at max_gap 0. */
+typedef struct fs_alignment {
+  uint64_t first, last;                /* record index of the root and of the peak                */
+  uint32_t n_words, n_exact;           /* path records; those with comb <= 0 (NaN never counts)   */
+  uint32_t score;                      /* best(peak)                                              */
+  uint32_t fan_skipped, orig_skipped;  /* sums of df - 1 and of do - 1 along the path             */
+  uint32_t pieces;                     /* 1 + the links with df != 1 or do != 1                   */
+  uint32_t tree_records;               /* records of the whole tree, side records included        */
+  uint32_t reserved;                   /* 0                                                       */
+  uint64_t path_at;                    /* offset of the path's records in `path`                  */
+} fs_alignment;                        /* 56 bytes (two 8-byte indices, eight words, one offset)  */
+
+/* Host columns in; `cap` alignments and `path_cap` path records out, on HIP device `device`:
+ * path holds the record indices of every kept alignment, path after path, each in path order.
+ * Both entry points: FS_E_INVALID for null arguments, min_words == 0, match == 0, reach > 63,
+ * match or gap above 16, or records out of (work, fan_ix) order; FS_E_UNSUPPORTED for n_rows >=
+ * 2^32 or n_rows * match >= 2^32; FS_E_CAPACITY with *n_out = alignments and *n_path = path
+ * records required when either buffer is too small (both untouched then).  n_rows == 0: FS_OK
+ * with both counts 0, without device work.  Device memory is a dozen words per record.
+ * A record starts a segment when its work changes or its fan index is more than R + 1 past the
+ * record in front of it; no link crosses that.  Segments of up to FS_ALIGNMENTS_SMALL records
+ * (default 8; 0: none) take a lane each, longer ones a wave each with the last 64 records in
+ * registers; candidates behind those 64 (records sharing a fan index) are read back from
+ * global memory, and with FS_ALIGNMENTS_RING=0 every candidate is.  Both are diagnostics of
+ * the environment, read on each call; the output is the same wherever they stand. */
+int fs_alignments(int device, const uint32_t* work, const uint32_t* fan_ix,
+                  const uint32_t* orig_ix, const double* comb, uint64_t n_rows,
+                  uint32_t min_words, uint32_t reach, uint32_t match, uint32_t gap,
+                  fs_alignment* out, uint64_t cap, uint64_t* n_out, uint32_t* path,
+                  uint64_t path_cap, uint64_t* n_path);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (d_out
+ * 8-byte, d_path 4-byte aligned), on the index's device and stream; returns when they are
+ * written. */
+int fs_alignments_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t min_words,
+                       uint32_t reach, uint32_t match, uint32_t gap, fs_alignment* d_out,
+                       uint64_t cap, uint64_t* n_out, uint32_t* d_path, uint64_t path_cap,
+                       uint64_t* n_path);
+/* HIP-event milliseconds of the last fs_alignments / fs_alignments_rows call on this thread:
+ * segments (order check, heads), bins (the segments by class), chain (the recurrence, both
+ * classes), keep (kept roots, their places, the alignment records), trace (the path records),
+ * and the total of the five; 0 for a pass that did not run.  tools/alignments_bench.py. */
+int fs_alignments_times(double* ms);
+
 /* `ao3.py matrix --engine device`: the n-grams behind the works x phrases matrix.  Records
  * sorted by (work, fan_ix), in the order the command takes them (works by first appearance,
  * stable by fan index).
