@@ -138,6 +138,24 @@ assert COMPANION_DTYPE.itemsize == 32
 FS_COMPANIONS_MAX_BYTES = 1 << 30
 COMPANIONS_MS_NAMES = ("incidence", "count", "place", "detail")
 
+# fs_line, fs_line_work, fs_line_cell: 32 bytes each
+LINE_DTYPE = np.dtype([("works", np.uint32), ("whole_works", np.uint32),
+                       ("most_works", np.uint32), ("head_works", np.uint32),
+                       ("tail_works", np.uint32), ("first_work", np.uint32),
+                       ("covered_sum", np.uint64)])
+assert LINE_DTYPE.itemsize == 32
+LINE_WORK_DTYPE = np.dtype([("work", np.uint32), ("lines", np.uint32), ("whole_lines", np.uint32),
+                            ("covered", np.uint32), ("line_words", np.uint32),
+                            ("top_line", np.uint32), ("top_covered", np.uint32),
+                            ("reserved", np.uint32)])
+assert LINE_WORK_DTYPE.itemsize == 32
+LINE_CELL_DTYPE = np.dtype([("line", np.uint32), ("work", np.uint32), ("covered", np.uint32),
+                            ("first", np.uint32), ("last", np.uint32), ("runs", np.uint32),
+                            ("reserved", np.uint32), ("reserved2", np.uint32)])
+assert LINE_CELL_DTYPE.itemsize == 32
+FS_LINES_MAX_BYTES = 1 << 30
+LINES_MS_NAMES = ("tables", "walk", "total")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

@@ -17,7 +17,9 @@ which relates the quoted stretches of the script by the works quoting both
 quote next after each stretch (fandom_search_amd/transitions.py), and `sources`, which joins
 the match files of several scripts and says which script each fan passage quotes
 (fandom_search_amd/sources.py), and `alignments`, which aligns every fan work against the script
-with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignments.py).  The
+with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignments.py), and
+`lines`, which ranks the lines of the script markup by the works quoting them and says how
+completely each is quoted (fandom_search_amd/lines.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -375,9 +377,9 @@ def build_parser():
 
 
 def full_parser():
-    """The parser `ao3.py` runs: build_parser(), whose surface tests/golden/cli_surface.json pins
-    as it stands, and behind it the commands added since, each with a pinned surface of its own
-    (`alignments`: tests/golden/alignments_cli.json)."""
+    """build_parser(), whose surface tests/golden/cli_surface.json pins as it stands, and behind
+    it `alignments`, with a pinned surface of its own (tests/golden/alignments_cli.json) that
+    holds this parser to exactly these commands; ao3_parser() goes on from here."""
     parser = build_parser()
     subparsers = parser._subparsers._group_actions[0]
     subparsers.help = subparsers.help.replace(' or validate', ', alignments or validate')
@@ -404,6 +406,36 @@ def full_parser():
                          help='what a matched word scores, 1 to 16, default 2'),
                     _own('--gap', default=1, type=int,
                          help='what a skipped word costs, 0 to 16, default 1')])
+    return parser
+
+
+def ao3_parser():
+    """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
+    behind it the commands added since (`lines`)."""
+    parser = full_parser()
+    subparsers = parser._subparsers._group_actions[0]
+    subparsers.help = subparsers.help.replace(' or validate', ', lines or validate')
+
+    _analysis(subparsers, 'lines',
+              'ranks the lines of the script markup by the fan works quoting them '
+              'and says how completely: per line the works quoting it whole, mostly, '
+              'from its first word and to its last, per work its lines, per line and '
+              'work the covered words',
+              'prefix of the three csv files, PREFIX-lines.csv, '
+              'PREFIX-lines-works.csv and PREFIX-lines-cells.csv (default: the input '
+              'name without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0,
+                '--min-words and --min-works must be at least 1, --max-gap at least 0'),
+               (lambda a: not 1 <= a.most <= 100, '--most must be from 1 to 100')],
+              first=[_own('script', action='store',
+                          help='filename for the script markup the csv was searched '
+                               'against')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='fewest works quoting a listed line, default 1'),
+                    _own('--most', default=50, type=int,
+                         help='fewest words of a line, as a whole percentage of its '
+                              'words, a work covers to count in MOST_WORKS, 1 to 100, '
+                              'default 50')])
     return parser
 
 
@@ -458,7 +490,7 @@ def _command(name, checks, args):
 
 
 def main(argv=None):
-    parser = full_parser()
+    parser = ao3_parser()
     args = parser.parse_args(argv)
     if hasattr(args, 'func'):
         args.func(args)

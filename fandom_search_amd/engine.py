@@ -590,6 +590,31 @@ class ScriptIndex(object):
                           [abi.COMPANION_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
                           "pair buffer too small")
 
+    def lines_device(self, rows_ptr, n_rows, n_works, line_first_ptr, n_lines, min_words=6,
+                     max_gap=0, most=50, out_ptrs=None, caps=None):
+        """`lines` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident line table of n_lines + 1 entries (fs_lines_rows): per line the works
+        quoting it and how completely, per active work its lines, and the cells (line, work) in
+        that order.  Without `out_ptrs`: (abi.LINE_DTYPE[n_lines], abi.LINE_WORK_DTYPE[active
+        works], abi.LINE_CELL_DTYPE[n_cells]) on the host.  With `out_ptrs` = device addresses
+        (lines; works, cells, buffers of `caps` = (works, cells) of them): (active works,
+        cells); FsError(FS_E_CAPACITY) with .required = both counts when a buffer is too small
+        (the lines are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_lines_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                   C.c_void_p(line_first_ptr), int(n_lines), int(min_words),
+                                   int(max_gap), int(most), C.c_void_p(fixed[0]),
+                                   C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]),
+                                   C.c_void_p(grown[1]), int(caps[1]), C.byref(counts[1]))
+        if caps is None:
+            caps = (0, 0) if out_ptrs is not None else (256, 4096)
+        return _rows_call("fs_lines_rows", call, [(n_lines, abi.LINE_DTYPE)],
+                          [abi.LINE_WORK_DTYPE, abi.LINE_CELL_DTYPE], list(caps), out_ptrs,
+                          "work or cell buffer too small")
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

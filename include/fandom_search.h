@@ -813,6 +813,79 @@ int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint
  * results), place pass, detail pass; 0 for a pass that did not run.  tools/companions_bench.py. */
 int fs_companions_times(double* ms);
 
+/* `ao3.py lines`: the lines of the script by how completely the fan works quote them.  Records,
+ * passages, active works (works with a passage; N of them, numbered in work order) and the
+ * coverage C_w as for fs_pairs.  line_first[n_lines + 1] cuts the script into lines: line l owns
+ * the script words line_first[l] .. line_first[l + 1] - 1, line_first[0] = 0 and
+ * line_first[n_lines] = n_script, strictly ascending (no empty line).  A cell (l, w) exists when
+ * C_w holds a word of line l; covered = the words of the line in C_w, first and last the smallest
+ * and largest of them, runs the maximal stretches of consecutive ones; the cell is whole when
+ * covered = the words of the line.  Every output is an integer. */
+typedef struct fs_line {
+  uint32_t works;            /* cells of the line                                        */
+  uint32_t whole_works;      /* whole ones among them                                    */
+  uint32_t most_works;       /* cells with covered * 100 >= most * words (64 bits;
+                                exactly at the bound counts, whole cells count)          */
+  uint32_t head_works;       /* cells holding the line's first word                      */
+  uint32_t tail_works;       /* cells holding its last word                              */
+  uint32_t first_work;       /* smallest work number with a cell; 0xFFFFFFFF without     */
+  uint64_t covered_sum;      /* covered summed over the cells                            */
+} fs_line;                   /* 32 bytes                                                 */
+
+typedef struct fs_line_work {
+  uint32_t work;             /* work number of this active work                          */
+  uint32_t lines;            /* cells of the work                                        */
+  uint32_t whole_lines;      /* whole ones among them                                    */
+  uint32_t covered;          /* covered summed over its cells = |C_w|                    */
+  uint32_t line_words;       /* the words of the lines it has a cell in                  */
+  uint32_t top_line;         /* the line with the largest covered, the earlier on a tie  */
+  uint32_t top_covered;      /* its covered                                              */
+  uint32_t reserved;         /* 0                                                        */
+} fs_line_work;              /* 32 bytes                                                 */
+
+typedef struct fs_line_cell {
+  uint32_t line;             /* line number                                              */
+  uint32_t work;             /* work number (not active number)                          */
+  uint32_t covered;          /* words of the line in C_w, >= 1                           */
+  uint32_t first, last;      /* smallest and largest of them (script word indices)       */
+  uint32_t runs;             /* maximal runs of consecutive covered words in the line    */
+  uint32_t reserved;         /* 0                                                        */
+  uint32_t reserved2;        /* 0                                                        */
+} fs_line_cell;              /* 32 bytes                                                 */
+
+/* Counted: the coverage, a 64-bit word per 64 script words and active work with the active works
+ * padded to a multiple of 64 (ceil(n_script / 64) * ceil(N / 64) * 64 * 8 bytes), and, per line
+ * and column of 64 active works, the incidence word and the cells in front of the column
+ * (n_lines * ceil(N / 64) * 12 bytes).  Their sum may be up to this. */
+#define FS_LINES_MAX_BYTES (1u << 30)
+
+/* Host columns and the host line table in; lines[n_lines], up to works_cap active works in
+ * active order and up to cells_cap cells in (line, work) order out, on HIP device `device`.
+ * Both entry points: FS_E_INVALID for min_words == 0, most outside 1..100, records out of (work,
+ * fan_ix) order, a work >= n_works, an orig_ix >= n_script or a line_first that is not strictly
+ * ascending from 0 to n_script; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script >
+ * FS_WORKS_MAX_SCRIPT or tables above FS_LINES_MAX_BYTES; FS_E_CAPACITY with *n_active and
+ * *n_cells = the counts required when either cap is smaller (lines is complete then, works and
+ * cells untouched).  n_rows == 0 or n_lines == 0: lines of no works with first_work 0xFFFFFFFF,
+ * *n_active = *n_cells = 0 (fs_lines: without device work, the line table unread). */
+int fs_lines(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+             uint64_t n_rows, uint32_t n_works, uint32_t n_script, const uint32_t* line_first,
+             uint32_t n_lines, uint32_t min_words, uint32_t max_gap, uint32_t most,
+             fs_line* lines, fs_line_work* works, uint64_t works_cap, uint64_t* n_active,
+             fs_line_cell* cells, uint64_t cells_cap, uint64_t* n_cells);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident line
+ * table of n_lines + 1 entries into device buffers (16-byte aligned), n_script taken from the
+ * index, on the index's device and stream; returns when they are written. */
+int fs_lines_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                  const uint32_t* d_line_first, uint32_t n_lines, uint32_t min_words,
+                  uint32_t max_gap, uint32_t most, fs_line* d_lines, fs_line_work* d_works,
+                  uint64_t works_cap, uint64_t* n_active, fs_line_cell* d_cells,
+                  uint64_t cells_cap, uint64_t* n_cells);
+/* HIP-event milliseconds of the last fs_lines / fs_lines_rows call on this thread: tables
+ * (coverage, incidence, the cell offsets), walk (with the per-work records), and their total; 0
+ * for a pass that did not run.  tools/lines_bench.py. */
+int fs_lines_times(double* ms);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
