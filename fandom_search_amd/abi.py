@@ -75,6 +75,22 @@ class FsIndexInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class FsScanShape(C.Structure):
+    _fields_ = [("waves", C.c_uint32),
+                ("blocks", C.c_uint32),
+                ("filter_log2_words", C.c_uint32),
+                ("seeds_lds_bytes", C.c_uint32),
+                ("log2_buckets", C.c_uint32),
+                ("log2_slots", C.c_uint32),
+                ("overflow_buckets", C.c_uint32),
+                ("wide_buckets", C.c_uint32),
+                ("host_wire8", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 # fs_row: 32 bytes
 ROW_DTYPE = np.dtype([("work", np.uint32), ("fan_ix", np.uint32),
                       ("orig_ix", np.uint32), ("lev", np.uint32),

@@ -238,6 +238,11 @@ static int build_gram_index(fs_index* ix, const uint32_t* stok) {
       put(g, slot);
     }
   }
+  // (fs_index_scan_shape: a separable bucket whose seed the byte array cannot hold is "wide")
+  ix->n_overflow = (uint32_t)overflow.size();
+  ix->n_disp_wide = 0;
+  for (uint32_t b = 0; b < n_buckets; ++b)
+    if (!(disp[b] & FS_DISP_OVERFLOW) && disp[b] >= FS_DISP8_WIDE) ++ix->n_disp_wide;
   FS_TRY(ix->d_disp.upload(disp.data(), disp.size(), ix->stream));
   FS_TRY(ix->d_filter.upload(filter.data(), filter.size(), ix->stream));
   // batch table of k_scan_rows (fs_hash.h): same placement, 64-byte entries whose best
@@ -609,6 +614,32 @@ extern "C" const char* fs_search_kernel_name(fs_index* ix, fs_corpus* c) {
     snprintf(name, sizeof name, "k_scan<%d>", n);
   }
   return name;
+}
+
+bool fs_host_wire8(const fs_index* ix, bool exact) {
+  static const bool host8 = !getenv("FS_HOST_WIRE8") || atoi(getenv("FS_HOST_WIRE8")) != 0;
+  return exact && ix->n_script < (1ull << 18) && host8;
+}
+
+// Diagnostics: what a search of `c` would launch, from the functions the launch itself asks
+// (fs_search_corpus_begin); nothing is queued and nothing is built.
+extern "C" int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* out) {
+  if (!ix || !c || !out || c->ix != ix || (c->is_view && !c->base)) { fs_set_error("null argument or a corpus of another index"); return FS_E_INVALID; }
+  if (c->is_view) fs_view_sync(c);
+  *out = fs_scan_shape();
+  const bool exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
+  out->waves = exact ? fs_scan_rows_shape(ix, c, &out->blocks) : 0;
+  int lw = ix->log2_words;
+  uint32_t seeds = 0;
+  if (out->waves) fs_scan_rows_lds(ix, &lw, &seeds);
+  out->filter_log2_words = (uint32_t)lw;
+  out->seeds_lds_bytes = seeds;
+  out->log2_buckets = (uint32_t)ix->log2_buckets;
+  out->log2_slots = (uint32_t)ix->log2_slots;
+  out->overflow_buckets = ix->n_overflow;
+  out->wide_buckets = ix->n_disp_wide;
+  out->host_wire8 = fs_host_wire8(ix, exact) ? 1u : 0u;
+  return FS_OK;
 }
 
 // Diagnostics: the FS_* switches are read at fs_index_create; a test or sweep that
@@ -1217,8 +1248,7 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
   // a view's search reads the base's ids: behind the base's upload on the device
   if (c->is_view) FS_HIP(hipStreamWaitEvent(ln.stream, c->base->ev_ready, 0));
   sl.exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
-  static const bool host8 = !getenv("FS_HOST_WIRE8") || atoi(getenv("FS_HOST_WIRE8")) != 0;
-  sl.host_wire8 = rows_mode == FS_ROWS_HOST && sl.exact && ix->n_script < (1ull << 18) && host8;
+  sl.host_wire8 = rows_mode == FS_ROWS_HOST && fs_host_wire8(ix, sl.exact);
   // (bitmap layout of the chained kernels: the LSH pipeline's scans write four tokens per lane,
   // k_scan_near8 eight)
   sl.tpl = sl.exact ? fs_scan_tpl(ix, T) : (fs_scan_near8(ix) && fs_lsh_prefilter_ok(ix, c)) ? 8 : 4;

@@ -224,6 +224,7 @@ struct fs_index {
   uint64_t n_script = 0, n_windows = 0, n_vec = 0;
   uint32_t n_grams = 0;
   int log2_words = 0, log2_slots = 0, log2_buckets = 0, log2_swords = 0;
+  uint32_t n_overflow = 0, n_disp_wide = 0;   // buckets left to linear probing; separable ones whose seed is no byte
   bool ctab_ok = false;                // d_cproto / d_disp8 built (window sizes k_scan_rows takes)
   int num_cu = 256;
 
@@ -519,6 +520,9 @@ int fs_launch_compact_after_scan_rows(fs_index* ix, uint32_t n_ranges, uint32_t 
                                       fs_status* host_st, hipStream_t s, uint64_t* count_out,
                                       hipEvent_t done);
 uint32_t fs_scan_rows_shape(const fs_index* ix, const fs_corpus* c, uint32_t* blocks);   // waves per workgroup, 0: does not apply
+// what a k_scan_rows launch holds in LDS beside its per-wave state: log2 words of its filter, bytes of seeds (0: read from memory)
+void fs_scan_rows_lds(const fs_index* ix, int* filter_log2_words, uint32_t* seeds_bytes);
+bool fs_host_wire8(const fs_index* ix, bool exact);   // fs_api.hip: a host search brings its records over as 8-byte wire records
 int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blocks, uint32_t rcap, fs_row* d_rows,
                         int wire, uint32_t caprow, fs_status* host_st, hipStream_t s,
                         hipEvent_t e0, hipEvent_t e1, uint64_t* count_out, hipEvent_t done = nullptr,

@@ -1434,6 +1434,11 @@ uint32_t fs_scan_rows_shape(const fs_index* ix, const fs_corpus* c, uint32_t* bl
   return 0;
 }
 
+void fs_scan_rows_lds(const fs_index* ix, int* filter_log2_words, uint32_t* seeds_bytes) {
+  *filter_log2_words = rows_filter_log2(ix);
+  *seeds_bytes = fs_scan_rows_disp_lds(ix);
+}
+
 // tokens -> output records: one launch of fs_scan_rows_blocks() workgroups of `waves` wave ranges
 int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blocks, uint32_t rcap, fs_row* d_rows,
                         int wire, uint32_t caprow, fs_status* host_st, hipStream_t s,

@@ -356,6 +356,14 @@ class ScriptIndex(object):
         """Diagnostics: the kernel that dominates a search of `corpus` (profile name)."""
         return _lib.load().fs_search_kernel_name(self._h, corpus._h).decode()
 
+    def scan_shape(self, corpus):
+        """Diagnostics: what a search of `corpus` would launch (fs_index_scan_shape), as a dict:
+        waves and blocks of k_scan_rows (0: the chained kernels), filter_log2_words,
+        seeds_lds_bytes, log2_buckets, log2_slots, overflow_buckets, wide_buckets, host_wire8."""
+        out = abi.FsScanShape()
+        _lib.check(_lib.load().fs_index_scan_shape(self._h, corpus._h, C.byref(out)), "fs_index_scan_shape")
+        return out.as_dict()
+
     def stream_floor(self, corpus, reps=20):
         """Diagnostics: ms of a kernel that only reads `corpus`' ids in k_scan_rows' launch
         shape (fs_stream_floor)."""

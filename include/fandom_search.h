@@ -1288,6 +1288,32 @@ int fs_index_set_scan_timing(fs_index* ix, uint32_t period);
  * of the search lists first.  Static storage, valid until the next call on this thread. */
 const char* fs_search_kernel_name(fs_index* ix, fs_corpus* c);
 
+/* Diagnostics: what a search of `c` on `ix` would launch as things stand (script length,
+ * corpus size, lanes, switches), answered by the functions the launch itself asks.  The
+ * index build and the launch choose buffer sizes, kernel instances, launch shapes and the
+ * record form by the script's length; a test pins each choice at the length where it flips.
+ * Read-only: nothing is queued or built (a view that has not been searched yet has no
+ * batch table and reports the chained kernels). */
+typedef struct fs_scan_shape {
+  uint32_t waves;              /* waves per workgroup of k_scan_rows; 0: the chained kernels   */
+  uint32_t blocks;             /* its workgroups; 0 with the chained kernels                   */
+  uint32_t filter_log2_words;  /* log2 words of the filter k_scan_rows holds in LDS (the
+                                  sub-shingle filter where it applies); with the chained
+                                  kernels, of their Bloom filter                               */
+  uint32_t seeds_lds_bytes;    /* displacement seeds k_scan_rows holds in LDS; 0: it reads
+                                  them from memory (or the chained kernels run)                */
+  uint32_t log2_buckets;       /* of the exact table's displacement seeds                      */
+  uint32_t log2_slots;         /* of the exact table                                           */
+  uint32_t overflow_buckets;   /* buckets placed by linear probing (n-grams with colliding
+                                  32-bit hashes)                                               */
+  uint32_t wide_buckets;       /* separable buckets whose seed does not fit a byte             */
+  uint32_t host_wire8;         /* 1: an FS_ROWS_HOST search brings 8-byte wire records over
+                                  and expands them on the host (exact pipeline, scripts below
+                                  2^18 tokens); 0: it does not                                 */
+  uint32_t reserved[3];        /* 0                                                            */
+} fs_scan_shape;               /* 48 bytes                                                     */
+int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* out);
+
 /* ---- host text front end (search.py:164-166: read a fan work, tokenise, drop whitespace) ----
  * spaCy's tokenizer splits a text on whitespace and treats every chunk by itself, with a cache
  * chunk -> tokens; fs_textenc is that cache and the splitting, natively and on `threads` host

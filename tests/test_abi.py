@@ -48,6 +48,8 @@ def test_struct_layouts():
     assert abi.FsConfig.distance_threshold.offset == 40
     assert C.sizeof(abi.FsStats) == 64
     assert C.sizeof(abi.FsIndexInfo) == 72
+    assert C.sizeof(abi.FsScanShape) == 48
+    assert abi.FsScanShape.host_wire8.offset == 32
     assert abi.ROW_DTYPE.itemsize == 32
     assert [abi.ROW_DTYPE.fields[n][1] for n in abi.ROW_DTYPE.names] == [0, 4, 8, 12, 16, 24]
 
