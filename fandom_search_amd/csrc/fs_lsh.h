@@ -29,6 +29,7 @@ struct LshDev {
                            // out-of-vocabulary vector is the sum of the rows of its (up to three) hot positions
   const float* ntmax;      // [n][D] >= max_c |nt[k][d][c]|
   float bound_scale;       // n * 2^-22 (times a test factor)
+  float bound_abs;         // 2^-149 (times the same factor): key_bound32's absolute term per addend
   int m_min;               // fewer id-identical slots than this cannot reach the threshold
   int diag;                // diagnostics: 1 = skip candidate walk, 2 = skip key computation,
                            // 3 = walk the buckets but skip the distances
@@ -160,6 +161,19 @@ __device__ __forceinline__ void row32_bound(const LshDev& L, int k, uint32_t id,
   *m += mx[a]; *terms += 1;
   if (b != a) { *m += mx[b]; *terms += 1; }
   if (c != b) { *m += mx[c]; *terms += 1; }
+}
+
+// The decision of the float32 keys, one rule for every kernel that makes it (lsh_window, k_lsh_batch,
+// k_lsh_pkeys, k_lsh_scan): a column's float32 sum decides its sign iff |sum| > key_bound32, and a
+// window with a column that does not is redone in float64.  am, terms: what row32_bound added up
+// over the window's slots.  The relative term, terms * 2^-22 * am, is four times the worst case of
+// `terms` roundings to float32 of entries whose magnitudes add up to am at most and of the float32
+// additions behind them.  That holds only while an entry's rounding is relative: below 2^-126 it is
+// absolute, up to 2^-150 per entry whatever its size (a float32 sum of subnormals is exact), and a
+// relative bound then falls below one float32 spacing and trusts every sum that is not 0 -- hence
+// the absolute term, terms * 2^-149.  (inf or NaN, from rows beyond float32: never > the bound.)
+__device__ __forceinline__ float key_bound32(const LshDev& L, float am, int terms) {
+  return L.bound_scale * am * ((float)terms / (float)L.n) + L.bound_abs * (float)terms;
 }
 
 __device__ __forceinline__ double q_of(const LshDev& L, uint32_t id) {

@@ -231,7 +231,7 @@ __device__ __forceinline__ int lsh_window(const CorpusDev& c, const LshDev& L, c
     am = __shfl(am, 0);
     terms = __shfl(terms, 0);
     if (!__any(oov)) {
-      const float bnd = L.bound_scale * am * ((float)terms / (float)L.n);
+      const float bnd = key_bound32(L, am, terms);
       const int col = 4 * lane;
       const int left = L.C - col;
       const uint32_t cmask = left >= 4 ? 0xFu : left > 0 ? (1u << left) - 1 : 0u;
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(256, 5) void k_lsh_batch(CorpusDev c, LshDev L, Gra
 #pragma unroll
       for (int d = 8; d > 0; d >>= 1) { am += __shfl_xor(am, d); terms += __shfl_xor(terms, d); oov |= (uint32_t)__shfl_xor((int)oov, d); }
       if (k == 0 && S.ok[w]) {
-        S.bnd[w] = L.bound_scale * am * ((float)terms / (float)N);
+        S.bnd[w] = key_bound32(L, am, terms);
         if (oov || !L.atab32 || L.C > 256) S.ok[w] = 2u;
       }
     }
@@ -892,7 +892,7 @@ __global__ __launch_bounds__(256) void k_lsh_pkeys(CorpusDev c, LshDev L, const 
 #pragma unroll
       for (int d = 8; d > 0; d >>= 1) { am += __shfl_xor(am, d); oov |= (uint32_t)__shfl_xor((int)oov, d); }
       if (k == 0 && S.ok[w]) {
-        S.bnd[w] = L.bound_scale * am;
+        S.bnd[w] = key_bound32(L, am, N);            // (no OOV id here: one addend a slot)
         if (oov || !L.atab32 || L.C > 256) S.ok[w] = 2u;
       }
     }

@@ -337,6 +337,7 @@ LshDev lsh_dev(const fs_index* ix) {
     // n * 2^-22; FS_LSH_F32_SLACK multiplies it (tests force the float64 fallback),
     // FS_LSH_F32=0 disables the float32 path
     L.bound_scale = (float)((double)ix->cfg.window_size * ldexp(1.0, -22) * ix->sw.lsh_f32_slack);
+    L.bound_abs = (float)(ldexp(1.0, -149) * ix->sw.lsh_f32_slack);
     if (!ix->sw.lsh_f32) L.atab32 = nullptr;
     L.m_min = ix->lsh_m_min;
     L.diag = ix->sw.lsh_diag;

@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256) void k_lsh_scan(CorpusDev c, LshDev L, const u
       }
       // (an out-of-vocabulary slot is up to three float32 addends instead of one: the bound's
       // n becomes the number of addends)
-      s_bound[w] = (L.atab32 == nullptr || (f64 && oov)) ? -1.0f : L.bound_scale * m * ((float)terms / (float)n);
+      s_bound[w] = (L.atab32 == nullptr || (f64 && oov)) ? -1.0f : key_bound32(L, m, terms);
       s_key[w] = oov ? 1u : 0u;                    // (phase 1 only: s_key is written behind it)
     }
     __syncthreads();
@@ -529,7 +529,8 @@ __global__ __launch_bounds__(256) void k_lsh_scan(CorpusDev c, LshDev L, const u
     // float32 sum is farther from zero than its worst-case distance to the canonical
     // float64 sum:  |s32 - s64| <= n * 2^-23 * sum_k max_c|A[k][t_k][c]|  (rounding
     // of the n table entries to float32 plus n-1 float32 additions; the float64
-    // additions contribute 2^-53 terms).  A window with any column inside twice
+    // additions contribute 2^-53 terms; below 2^-126 a rounding is absolute, not
+    // relative: key_bound32's second term).  A window with any column inside twice
     // that distance, or with an out-of-vocabulary token, is redone in float64.
     uint32_t* s_bits = reinterpret_cast<uint32_t*>(s_bal);           // [256][2 NW]
     for (int c0 = 0; c0 < L.C && L.diag != 2; c0 += 256) {

@@ -6,6 +6,8 @@ stops reaching its branch fails.
 
 Boundaries (fs_lsh*.hip, fs_api.hip) and the cases on either side of them:
   float32 keys iff C = H * B <= 256          c256 (16 x 16)      | c272 (16 x 17)
+    (signs that a wrong decision would flip)   test_gpu_hostile_keys.py: c255_last, c256_last,
+                                               c256_col252 | c272_last
   k_lsh_batch / k_lsh_pkeys ballot words     c256, c272          | c336, enum_c336 (16 x 21: a
     (5 words up to C = 320, 6 up to 384)                            sixth word and the zero word)
   wave NearestFilter iff N <= 48             N48                 | N49, N64, serial_N10 (one lane walks)
