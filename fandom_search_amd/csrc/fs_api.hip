@@ -140,6 +140,15 @@ void fs_read_switches(fs_switches* sw) {
   if (const char* e = getenv("FS_STR_FUSED")) sw->str_fused = e[0] != '0';
   sw->rows_waves = num("FS_ROWS_WAVES");
   sw->rows_blocks_per_cu = num("FS_ROWS_BLOCKS_PER_CU");
+  sw->host_wire8 = !getenv("FS_HOST_WIRE8") || num("FS_HOST_WIRE8") != 0;
+  sw->host_zerocopy = !getenv("FS_HOST_ZEROCOPY") || num("FS_HOST_ZEROCOPY") != 0;
+  sw->trace_begin = getenv("FS_TRACE_BEGIN") != nullptr;
+  sw->lanes = num("FS_LANES");
+  if (const char* e = getenv("FS_FILTER_LOG2_WORDS")) sw->filter_log2_words = atoi(e);
+  if (const char* e = getenv("FS_SFILTER_LOG2_WORDS")) sw->sfilter_log2_words = atoi(e);
+  sw->build_times = getenv("FS_BUILD_TIMES") != nullptr;
+  sw->share_count = getenv("FS_SHARE_COUNT") != nullptr;
+  sw->lsh_count = getenv("FS_LSH_COUNT") != nullptr;
 }
 
 static int ceil_log2(uint64_t x) {
@@ -180,7 +189,7 @@ static int build_gram_index(fs_index* ix, const uint32_t* stok) {
 
   // filter: about one 32-bit word per n-gram, 4 KiB .. 128 KiB (it lives in LDS)
   int lw = ceil_log2(std::max<uint64_t>(1, (uint64_t)G * 3 / 4));
-  if (const char* e = getenv("FS_FILTER_LOG2_WORDS")) lw = atoi(e);
+  if (ix->sw.filter_log2_words != FS_SWITCH_UNSET) lw = ix->sw.filter_log2_words;
   lw = std::min(15, std::max(10, lw));
   ix->log2_words = lw;
   ix->log2_slots = std::max(4, ceil_log2((uint64_t)G * 2 + 1));
@@ -271,7 +280,7 @@ static int build_gram_index(fs_index* ix, const uint32_t* stok) {
   if (const int K = fs_sub_k((int)n)) {
     const double dens = std::pow(2e-3, 1.0 / (double)(n - K + 1));
     int ls = ceil_log2((uint64_t)((double)std::max<uint64_t>(1, ix->n_script) / (32.0 * dens)) + 1);
-    if (const char* e = getenv("FS_SFILTER_LOG2_WORDS")) ls = atoi(e);
+    if (ix->sw.sfilter_log2_words != FS_SWITCH_UNSET) ls = ix->sw.sfilter_log2_words;
     ls = std::min(FS_SUB_MAX_LOG2_WORDS, std::max(10, ls));
     ix->log2_swords = ls;
     std::vector<uint32_t> sub(1u << ls, 0u);
@@ -459,7 +468,7 @@ extern "C" int fs_index_create(const fs_config* cfg, const uint32_t* script_vec,
   for (int l = 0; l < FS_LANES; ++l)
     FS_HIP(hipStreamCreateWithFlags(&ix->lanes[l].stream, hipStreamNonBlocking));
   ix->stream = ix->lanes[0].stream;
-  if (const char* e = getenv("FS_LANES")) ix->n_lanes = std::min(FS_LANES, std::max(1, atoi(e)));
+  if (ix->sw.lanes) ix->n_lanes = std::min(FS_LANES, std::max(1, ix->sw.lanes));   // (kept: a reload does not move searches between lanes)
   FS_HIP(hipEventCreate(&ix->ev_scan0));      // fs_scan_benchmark
   FS_HIP(hipEventCreate(&ix->ev_scan1));
   FS_HIP(hipHostMalloc((void**)&ix->h_status, sizeof(fs_status), hipHostMallocDefault));
@@ -480,7 +489,7 @@ extern "C" int fs_index_create(const fs_config* cfg, const uint32_t* script_vec,
   }
 
   // FS_BUILD_TIMES=1: seconds per stage of the index build on stderr
-  const bool times = getenv("FS_BUILD_TIMES") != nullptr;
+  const bool times = ix->sw.build_times;
   auto t_last = std::chrono::steady_clock::now();
   auto tick = [&](const char* what) {
     if (!times) return;
@@ -596,39 +605,20 @@ extern "C" int fs_index_lsh_counts(fs_index* ix, uint64_t* out) {
 }
 
 extern "C" const char* fs_search_kernel_name(fs_index* ix, fs_corpus* c) {
-  static thread_local char name[64];
   if (!ix || !c || c->ix != ix || (c->is_view && !c->base)) return "";
   if (c->is_view) fs_view_sync(c);
-  const int n = (int)ix->cfg.window_size;
-  const bool exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
-  if (!exact) {
-    snprintf(name, sizeof name, !fs_lsh_prefilter_ok(ix, c) ? ((ix->share_flags & 32) ? "k_share_scan<%d>" : "k_lsh_scan") :
-                                fs_near_fused(ix, c) ? "k_near_sift<%d>" :
-                                fs_scan_near8(ix) ? "k_scan_near8<%d>" : "k_scan_near<%d>", n);
-  } else if (uint32_t blocks = 0; fs_scan_rows_shape(ix, c, &blocks)) {
-    const int k = ix->sw.scan_sub && ix->d_sfilter.p ? fs_sub_k(n) : 0;
-    snprintf(name, sizeof name, "k_scan_rows<%d,%d>", n, k);
-  } else if (fs_scan_tpl(ix, c->n_tok) == 8) {
-    snprintf(name, sizeof name, "k_scan8<%d>", n);
-  } else {
-    snprintf(name, sizeof name, "k_scan<%d>", n);
-  }
-  return name;
+  return fs_plan_kernel_name(ix, fs_plan_search(ix, c, FS_ROWS_HOST, ix->lanes[0], false));
 }
 
-bool fs_host_wire8(const fs_index* ix, bool exact) {
-  static const bool host8 = !getenv("FS_HOST_WIRE8") || atoi(getenv("FS_HOST_WIRE8")) != 0;
-  return exact && ix->n_script < (1ull << 18) && host8;
-}
-
-// Diagnostics: what a search of `c` would launch, from the functions the launch itself asks
-// (fs_search_corpus_begin); nothing is queued and nothing is built.
+// Diagnostics: what a search of `c` with host rows would launch, from the plan the launch itself
+// follows (fs_search_corpus_begin); nothing is queued and nothing is built.
 extern "C" int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* out) {
   if (!ix || !c || !out || c->ix != ix || (c->is_view && !c->base)) { fs_set_error("null argument or a corpus of another index"); return FS_E_INVALID; }
   if (c->is_view) fs_view_sync(c);
   *out = fs_scan_shape();
-  const bool exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
-  out->waves = exact ? fs_scan_rows_shape(ix, c, &out->blocks) : 0;
+  const fs_plan p = fs_plan_search(ix, c, FS_ROWS_HOST, ix->lanes[0], false);
+  out->waves = p.waves;
+  out->blocks = p.blocks;
   int lw = ix->log2_words;
   uint32_t seeds = 0;
   if (out->waves) fs_scan_rows_lds(ix, &lw, &seeds);
@@ -638,7 +628,7 @@ extern "C" int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* ou
   out->log2_slots = (uint32_t)ix->log2_slots;
   out->overflow_buckets = ix->n_overflow;
   out->wide_buckets = ix->n_disp_wide;
-  out->host_wire8 = fs_host_wire8(ix, exact) ? 1u : 0u;
+  out->host_wire8 = p.host_wire8 ? 1u : 0u;
   return FS_OK;
 }
 
@@ -1041,23 +1031,23 @@ static int search_enqueue(fs_index* ix, fs_index::Slot& sl) {
   hipStream_t s = ln.stream;
   fs_corpus* c = sl.c;
   const uint32_t nn = ix->cfg.nearest_n;
-  const uint32_t n_bm = sl.n_bm;
-  if (sl.fused_waves) {                // k_scan_rows: nothing between scan and records
-  } else if (sl.capw) {                // direct path: records instead of a bitmap
-    FS_TRY(ln.w_recs.reserve((size_t)FS_CHUNKS * 4 * sl.capw));
+  const fs_plan& pl = sl.plan;
+  const uint32_t n_bm = pl.n_bm;
+  if (pl.path == FS_PATH_DIRECT) {     // records instead of a bitmap
+    FS_TRY(ln.w_recs.reserve((size_t)FS_CHUNKS * 4 * pl.capw));
     FS_TRY(ln.w_info.reserve((size_t)FS_CHUNKS * 4));
-  } else {
-    FS_TRY(ln.w_qbm.reserve((size_t)n_bm * sl.tpl));
+  } else if (pl.path != FS_PATH_ROWS) {   // (k_scan_rows: nothing between scan and records)
+    FS_TRY(ln.w_qbm.reserve((size_t)n_bm * pl.tpl));
     FS_TRY(ln.w_qcnt.reserve(n_bm));
   }
-  if (!sl.caprow) {                    // the per-candidate arrays of the chained kernels
-    FS_TRY(ln.w_cpos.reserve(sl.ccap));
-    FS_TRY(ln.w_cg.reserve(sl.ccap));
-    FS_TRY(ln.w_cw.reserve(sl.ccap));
-    FS_TRY(ln.w_hv.reserve(sl.ccap));
-    FS_TRY(ln.w_hcomb.reserve(sl.ccap));
-    FS_TRY(ln.w_mlev.reserve(sl.exact && c->has_str ? sl.ccap * nn : 1));
-    FS_TRY(ln.w_cbest.reserve(!sl.exact || c->has_str ? sl.ccap : 1));
+  if (pl.path != FS_PATH_ROWS) {       // the per-candidate arrays of the chained kernels
+    FS_TRY(ln.w_cpos.reserve(pl.ccap));
+    FS_TRY(ln.w_cg.reserve(pl.ccap));
+    FS_TRY(ln.w_cw.reserve(pl.ccap));
+    FS_TRY(ln.w_hv.reserve(pl.ccap));
+    FS_TRY(ln.w_hcomb.reserve(pl.ccap));
+    FS_TRY(ln.w_mlev.reserve(pl.exact && c->has_str ? pl.ccap * nn : 1));
+    FS_TRY(ln.w_cbest.reserve(!pl.exact || c->has_str ? pl.ccap : 1));
   }
   fs_row* d_rows = sl.rows;
   uint64_t* count_out = nullptr;
@@ -1067,9 +1057,8 @@ static int search_enqueue(fs_index* ix, fs_index::Slot& sl) {
   }
   // (host rows of the exact pipeline leave the device as 8-byte records: a quarter of the
   // bytes over PCIe; w_rows is sized in fs_row either way)
-  static const bool zero_copy = !getenv("FS_HOST_ZEROCOPY") || atoi(getenv("FS_HOST_ZEROCOPY")) != 0;
   sl.host_direct = false;
-  if (sl.mode == FS_ROWS_HOST && sl.host_wire8 && zero_copy) {
+  if (sl.mode == FS_ROWS_HOST && pl.host_wire8 && ix->sw.host_zerocopy) {
     // the search's last kernel stores the 8-byte records straight into pinned host memory
     // (2.4 MB per C2 batch over PCIe as the workgroups finish): no copy to queue and wait
     // for behind the search
@@ -1084,10 +1073,10 @@ static int search_enqueue(fs_index* ix, fs_index::Slot& sl) {
     d_rows = reinterpret_cast<fs_row*>(ix->d_stage);
     sl.host_direct = true;
   } else if (sl.mode == FS_ROWS_HOST) {
-    FS_TRY(ln.w_rows.reserve(sl.host_wire8 ? (sl.rcap + 3) / 4 : sl.rcap));
+    FS_TRY(ln.w_rows.reserve(pl.host_wire8 ? (sl.rcap + 3) / 4 : sl.rcap));
     d_rows = ln.w_rows.p;
   }
-  const int wire = sl.mode == FS_ROWS_DEVICE_PACKED ? 16 : (sl.mode == FS_ROWS_DEVICE_PACKED8 || sl.host_wire8) ? 8 : 0;
+  const int wire = sl.mode == FS_ROWS_DEVICE_PACKED ? 16 : (sl.mode == FS_ROWS_DEVICE_PACKED8 || pl.host_wire8) ? 8 : 0;
 
   // the status block is cleared by the chain's first kernel (k_reduce) and its final
   // state is written to sl.h_status by the last one (k_rows)
@@ -1101,46 +1090,51 @@ static int search_enqueue(fs_index* ix, fs_index::Slot& sl) {
   sl.whole_timed = whole;
   if (ix->prof.on) fs_prof_mark(ix, s, "<begin>");
   hipEvent_t e0 = sl.timed ? sl.ev_scan0 : nullptr, e1 = sl.timed ? sl.ev_scan1 : nullptr;
-  const uint32_t ccap32 = (uint32_t)std::min<uint64_t>(sl.ccap, 0xFFFFFFFFull);
+  const uint32_t ccap32 = (uint32_t)std::min<uint64_t>(pl.ccap, 0xFFFFFFFFull);
   const uint32_t rcap32 = (uint32_t)std::min<uint64_t>(sl.rcap, 0xFFFFFFFFull);
   bool end_attached = false;           // sl.ev_end rides on the last dispatch (no marker of its own)
-  if (sl.exact && sl.fused_waves) {
-    // (the whole-search timing of the synchronous call keeps its own end marker)
-    FS_TRY(fs_launch_scan_rows(ix, c, sl.fused_waves, sl.fused_blocks, rcap32, d_rows, wire, sl.caprow, sl.h_status, s,
-                               e0, e1, count_out, whole || ix->prof.on ? nullptr : sl.ev_end, &end_attached));
-    if (ix->prof.on) fs_prof_mark(ix, s, ix->n_lanes > 1 ? "k_scan_rows+k_compact" : fs_search_kernel_name(ix, c));
-  } else if (sl.exact) {
-    fs_scan_extra ex;
-    ex.bsum = ln.w_bsum.p; ex.zero = ln.d_status.p;
-    if (sl.capw) { ex.recs = ln.w_recs.p; ex.info = ln.w_info.p; ex.capw = sl.capw; }
-    FS_TRY(fs_launch_scan(ix, c->dev(), ln.w_qbm.p, ln.w_qcnt.p, n_bm, s, e0, e1, &ex));
-    if (ix->prof.on) fs_prof_mark(ix, s, fs_search_kernel_name(ix, c));
-    FS_TRY(fs_launch_post(ix, c, n_bm, sl.tpl, ccap32, rcap32, d_rows, wire, sl.h_status, s, ex, count_out));
-    if (ix->prof.on) fs_prof_mark(ix, s, "verify .. k_rows");
-  } else {
-    // tables whose proof fails by one slot only: the integer prefilter flags the windows
-    // that can have a neighbour at all, the LSH work runs on those
-    fs_scan_extra ex;
-    ex.bsum = ln.w_bsum.p; ex.zero = ln.d_status.p;
-    if (sl.caps) {
+  fs_scan_extra ex;
+  ex.bsum = ln.w_bsum.p; ex.zero = ln.d_status.p;
+  switch (pl.path) {
+    case FS_PATH_ROWS:
+      // (the whole-search timing of the synchronous call keeps its own end marker)
+      FS_TRY(fs_launch_scan_rows(ix, c, pl.waves, pl.blocks, rcap32, d_rows, wire, pl.caprow, sl.h_status, s,
+                                 e0, e1, count_out, whole || ix->prof.on ? nullptr : sl.ev_end, &end_attached));
+      if (ix->prof.on) fs_prof_mark(ix, s, ix->n_lanes > 1 ? "k_scan_rows+k_compact" : fs_plan_kernel_name(ix, pl));
+      break;
+    case FS_PATH_DIRECT:
+      ex.recs = ln.w_recs.p; ex.info = ln.w_info.p; ex.capw = pl.capw;
+      [[fallthrough]];
+    case FS_PATH_BITMAP:
+      FS_TRY(fs_launch_scan(ix, c->dev(), ln.w_qbm.p, ln.w_qcnt.p, n_bm, s, e0, e1, &ex));
+      if (ix->prof.on) fs_prof_mark(ix, s, fs_plan_kernel_name(ix, pl));
+      FS_TRY(fs_launch_post(ix, c, n_bm, pl.tpl, ccap32, rcap32, d_rows, wire, sl.h_status, s, ex, count_out));
+      if (ix->prof.on) fs_prof_mark(ix, s, "verify .. k_rows");
+      break;
+    case FS_PATH_NEAR_SIFT: {
       // the prefilter and the wildcard filter in one kernel, the survivors in lists per wave
       // range: no bitmap, no k_expand, an eighth of the entries for everything behind
-      FS_TRY(ln.w_slist.reserve((size_t)fs_near_ranges() * sl.caps));
+      FS_TRY(ln.w_slist.reserve((size_t)fs_near_ranges() * pl.caps));
       FS_TRY(ln.w_scount.reserve(fs_near_ranges()));
-      FS_TRY(fs_launch_near_sift(ix, c, ln.w_slist.p, sl.caps, ln.w_scount.p, ln.w_bsum.p, ln.d_status.p, s, e0, e1));
-      if (ix->prof.on) fs_prof_mark(ix, s, fs_search_kernel_name(ix, c));
-      const fs_near_lists near{ln.w_slist.p, ln.w_scount.p, sl.caps};
+      FS_TRY(fs_launch_near_sift(ix, c, ln.w_slist.p, pl.caps, ln.w_scount.p, ln.w_bsum.p, ln.d_status.p, s, e0, e1));
+      if (ix->prof.on) fs_prof_mark(ix, s, fs_plan_kernel_name(ix, pl));
+      const fs_near_lists near{ln.w_slist.p, ln.w_scount.p, pl.caps};
       FS_TRY(fs_launch_lsh_verify(ix, c, ccap32, s, &near));
-    } else {
-      if (fs_lsh_prefilter_ok(ix, c))
+      break;
+    }
+    case FS_PATH_NEAR_CHAIN:
+    case FS_PATH_KEY_SCAN:
+      if (pl.path == FS_PATH_NEAR_CHAIN)
         FS_TRY(fs_launch_scan_near(ix, c, ln.w_qbm.p, ln.w_qcnt.p, n_bm, s, e0, e1, &ex));
       else
         FS_TRY(fs_launch_lsh_scan(ix, c->dev(), ln.w_qbm.p, ln.w_qcnt.p, n_bm, s, e0, e1));
-      if (ix->prof.on) fs_prof_mark(ix, s, fs_search_kernel_name(ix, c));
-      FS_TRY(fs_launch_expand(ix, c, n_bm, ccap32, sl.tpl, s, ex.counted));
+      if (ix->prof.on) fs_prof_mark(ix, s, fs_plan_kernel_name(ix, pl));
+      FS_TRY(fs_launch_expand(ix, c, n_bm, ccap32, pl.tpl, s, ex.counted));
       if (ix->prof.on) fs_prof_mark(ix, s, ex.counted ? "k_expand" : "k_reduce+k_expand");
       FS_TRY(fs_launch_lsh_verify(ix, c, ccap32, s));
-    }
+      break;
+  }
+  if (!pl.exact) {
     FS_TRY(fs_launch_rows(ix, c, ln.w_cbest.p, 1, ccap32, rcap32, d_rows, 0, sl.h_status, s, count_out));
     if (ix->prof.on) fs_prof_mark(ix, s, "k_hitrows+k_rows");
   }
@@ -1224,7 +1218,6 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
                  "FS_ROWS_DEVICE_PACKED8");
     return FS_E_INVALID;
   }
-  static const bool trace_begin = getenv("FS_TRACE_BEGIN") != nullptr;
   const auto tb0 = std::chrono::steady_clock::now();
   FS_ENTER(ix->device);
   FS_TRY(corpus_ready(ix, c));              // no-op unless an upload is in flight (own corpus)
@@ -1247,57 +1240,23 @@ extern "C" int fs_search_corpus_begin(fs_index* ix, fs_corpus* c, fs_row* rows, 
   const fs_index::Lane& ln = ix->lanes[sl.lane];
   // a view's search reads the base's ids: behind the base's upload on the device
   if (c->is_view) FS_HIP(hipStreamWaitEvent(ln.stream, c->base->ev_ready, 0));
-  sl.exact = ix->info.path == FS_MODE_EXACT && !c->has_oov;
-  sl.host_wire8 = rows_mode == FS_ROWS_HOST && fs_host_wire8(ix, sl.exact);
-  // (bitmap layout of the chained kernels: the LSH pipeline's scans write four tokens per lane,
-  // k_scan_near8 eight)
-  sl.tpl = sl.exact ? fs_scan_tpl(ix, T) : (fs_scan_near8(ix) && fs_lsh_prefilter_ok(ix, c)) ? 8 : 4;
-  sl.n_bm = (uint32_t)((T + 64 * sl.tpl - 1) / (64 * sl.tpl));
-  if (rows_mode == FS_ROWS_DEVICE_PACKED8 && (!sl.exact || ix->n_script >= (1ull << 18))) {
+  sl.plan = fs_plan_search(ix, c, rows_mode, ln, false);
+  if (rows_mode == FS_ROWS_DEVICE_PACKED8 && (!sl.plan.exact || ix->n_script >= (1ull << 18))) {
     fs_set_error("8-byte rows exist for the exact n-gram pipeline and scripts below 2^18 tokens");
     return FS_E_UNSUPPORTED;
   }
-  if (rows_mode == FS_ROWS_DEVICE_PACKED && !sl.exact) {
+  if (rows_mode == FS_ROWS_DEVICE_PACKED && !sl.plan.exact) {
     fs_set_error("packed rows exist for the exact n-gram pipeline only (there the distance is a "
                  "function of the matched script window)");
     return FS_E_UNSUPPORTED;
   }
-  // direct path (the scan writes candidate records per wave range): 64 records per
-  // range to start with (C2 needs about 20), more once a search has asked for it
-  sl.capw = 0;
-  if (sl.exact && fs_scan_direct_ok(ix, T)) {
-    sl.capw = std::max<uint32_t>(64, ln.capw_hint);
-    if (ix->sw.scan_capw > 0) sl.capw = (uint32_t)ix->sw.scan_capw;   // tests: force the growth path
-  }
-  // k_scan_rows (tokens -> records in one kernel): staged records per wave range, more once
-  // a search has asked for it
-  sl.caprow = 0;
-  sl.fused_waves = sl.exact ? fs_scan_rows_shape(ix, c, &sl.fused_blocks) : 0;
-  if (sl.fused_waves) {
-    const uint32_t ranges = sl.fused_blocks * sl.fused_waves;
-    // staged records per wave range: a sixteenth of its tokens (C2: 305, 72 used on average)
-    const uint32_t dflt = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(128, T / ranges / 16), 1u << 20);
-    sl.caprow = std::max<uint32_t>(dflt, ln.caprow_hint);
-    if (ix->sw.ranges_caprow > 0) sl.caprow = (uint32_t)ix->sw.ranges_caprow;
-  }
-  if (sl.fused_waves) { sl.capw = 0; sl.tpl = 8; sl.n_bm = (uint32_t)((T + 511) / 512); }
-  // k_near_sift: list entries per wave range -- an eighth of its tokens to start with (a C2
-  // batch uses 17 of 305 on average at n = 8, 112 over component ids at n = 6), more once a
-  // search has asked for it
-  sl.caps = 0;
-  if (!sl.exact && fs_near_fused(ix, c)) {
-    sl.caps = std::max<uint32_t>((uint32_t)std::min<uint64_t>(std::max<uint64_t>(64, T / fs_near_ranges() / 8), 1u << 20),
-                                 ln.caps_hint);
-    if (ix->sw.scan_capw > 0) sl.caps = (uint32_t)ix->sw.scan_capw;   // tests: force the growth path
-  }
-  // capacities: grown from the device totals when a stage overflows
-  sl.ccap = std::max<uint64_t>(std::max<uint64_t>(4096, T / 16), ln.w_cpos.n);
+  // rows: grown from the device totals when the stage overflows, as the plan's capacities are
   sl.rcap = rows_mode != FS_ROWS_HOST
                 ? cap
                 : std::max<uint64_t>(std::max<uint64_t>(4096, T / 16), ln.w_rows.n);
   const auto tb1 = std::chrono::steady_clock::now();
   FS_TRY(search_enqueue(ix, sl));
-  if (trace_begin) {
+  if (ix->sw.trace_begin) {
     const auto tb2 = std::chrono::steady_clock::now();
     fprintf(stderr, "fs_search_corpus_begin: set-up %.1f us, enqueue %.1f us\n",
             std::chrono::duration<double, std::micro>(tb1 - tb0).count(),
@@ -1447,11 +1406,11 @@ extern "C" int fs_search_corpus_end(fs_index* ix, uint32_t ticket, uint64_t* n_r
     if (ix->sw.end_query && ix->lanes[sl.lane].enqueued == sl.lane_seq)
       (void)hipStreamQuery(ix->lanes[sl.lane].stream);
     scan_ms = 0;
-    if (sl.n_bm && sl.timed) FS_HIP(hipEventElapsedTime(&scan_ms, sl.ev_scan0, sl.ev_scan1));
+    if (sl.plan.n_bm && sl.timed) FS_HIP(hipEventElapsedTime(&scan_ms, sl.ev_scan0, sl.ev_scan1));
     total_ms = 0;
     if (sl.whole_timed) FS_HIP(hipEventElapsedTime(&total_ms, sl.ev_begin, sl.ev_end));
     const fs_status& hs = *sl.h_status;
-    if (!sl.exact && ((ix->sw.lsh_diag & 0x780000) || hs.max_rows >= 0x70000000u)) fprintf(stderr, "lsh diag: %u (0x%x) bucket members / code for %u pending windows\n", hs.max_rows, hs.max_rows, hs.lsh_pending);
+    if (!sl.plan.exact && ((ix->sw.lsh_diag & 0x780000) || hs.max_rows >= 0x70000000u)) fprintf(stderr, "lsh diag: %u (0x%x) bucket members / code for %u pending windows\n", hs.max_rows, hs.max_rows, hs.lsh_pending);
     if (hs.bad_string) { fs_set_error("fan string id outside the string table"); return FS_E_INVALID; }
     if (hs.lev_overflow) {
       fs_set_error("an n-gram text exceeds %d code points", FS_LEV_MAX);
@@ -1464,13 +1423,8 @@ extern "C" int fs_search_corpus_end(fs_index* ix, uint32_t ticket, uint64_t* n_r
       // search again through the chained kernels (no hand-off inside a launch).
       *gave_up = 0;
       gave_up[1] = 0;
-      if (!sl.caprow) { fs_set_error("in-launch wait flagged on a search without one"); return FS_E_DEVICE; }
-      const uint64_t T = sl.c->n_tok;
-      sl.caprow = 0; sl.fused_waves = 0;
-      sl.tpl = fs_scan_tpl(ix, T);
-      sl.n_bm = (uint32_t)((T + 64 * sl.tpl - 1) / (64 * sl.tpl));
-      sl.capw = fs_scan_direct_ok(ix, T) ? std::max<uint32_t>(64, ix->lanes[sl.lane].capw_hint) : 0;
-      sl.ccap = std::max<uint64_t>(std::max<uint64_t>(4096, T / 16), ix->lanes[sl.lane].w_cpos.n);
+      if (sl.plan.path != FS_PATH_ROWS) { fs_set_error("in-launch wait flagged on a search without one"); return FS_E_DEVICE; }
+      sl.plan = fs_plan_search(ix, sl.c, sl.mode, ix->lanes[sl.lane], true);
       ix->wait_fallbacks++;
       sl.fallbacks++;
       FS_TRY(search_enqueue(ix, sl));
@@ -1484,20 +1438,21 @@ extern "C" int fs_search_corpus_end(fs_index* ix, uint32_t ticket, uint64_t* n_r
       gave_up[1] = 0;
       again = true;
     }
-    if (!sl.caprow && hs.n_cands > sl.ccap) { sl.ccap = (uint64_t)hs.n_cands + hs.n_cands / 8; again = true; }
-    if (sl.caprow && hs.max_rows > sl.caprow) {
-      sl.caprow = (hs.max_rows + hs.max_rows / 4 + 7) & ~7u;
-      ix->lanes[sl.lane].caprow_hint = sl.caprow;
+    fs_plan& pl = sl.plan;             // the path stays; the capacity that goes with it grows
+    if (pl.path != FS_PATH_ROWS && hs.n_cands > pl.ccap) { pl.ccap = (uint64_t)hs.n_cands + hs.n_cands / 8; again = true; }
+    if (pl.path == FS_PATH_ROWS && hs.max_rows > pl.caprow) {
+      pl.caprow = (hs.max_rows + hs.max_rows / 4 + 7) & ~7u;
+      ix->lanes[sl.lane].caprow_hint = pl.caprow;
       again = true;
     }
-    if (sl.caps && hs.max_recs > sl.caps) {
-      sl.caps = (hs.max_recs + hs.max_recs / 4 + 7) & ~7u;
-      ix->lanes[sl.lane].caps_hint = sl.caps;
+    if (pl.path == FS_PATH_NEAR_SIFT && hs.max_recs > pl.caps) {
+      pl.caps = (hs.max_recs + hs.max_recs / 4 + 7) & ~7u;
+      ix->lanes[sl.lane].caps_hint = pl.caps;
       again = true;
     }
-    if (sl.capw && hs.max_recs > sl.capw) {
-      sl.capw = (hs.max_recs + hs.max_recs / 4 + 7) & ~7u;
-      ix->lanes[sl.lane].capw_hint = sl.capw;
+    if (pl.path == FS_PATH_DIRECT && hs.max_recs > pl.capw) {
+      pl.capw = (hs.max_recs + hs.max_recs / 4 + 7) & ~7u;
+      ix->lanes[sl.lane].capw_hint = pl.capw;
       again = true;
     }
     else if (sl.mode == FS_ROWS_HOST && hs.n_rows > sl.rcap && hs.n_rows <= sl.cap) {
@@ -1519,16 +1474,16 @@ extern "C" int fs_search_corpus_end(fs_index* ix, uint32_t ticket, uint64_t* n_r
     st->rows = hs.n_rows;
     st->scan_ms = scan_ms;
     st->total_ms = total_ms;
-    st->path = sl.exact ? FS_MODE_EXACT : FS_MODE_GENERAL;
+    st->path = sl.plan.exact ? FS_MODE_EXACT : FS_MODE_GENERAL;
     st->scan_launches = sl.launches;
-    st->lsh_pending = sl.exact ? 0 : hs.lsh_pending;
+    st->lsh_pending = sl.plan.exact ? 0 : hs.lsh_pending;
     st->handoff_fallbacks = sl.fallbacks;
   }
-  if (!sl.exact) ix->lanes[sl.lane].pend_hint = hs.lsh_pending;
+  if (!sl.plan.exact) ix->lanes[sl.lane].pend_hint = hs.lsh_pending;
   if (hs.n_rows > sl.cap) return FS_E_CAPACITY;
   if (sl.mode == FS_ROWS_HOST && hs.n_rows) {
     fs_index::Lane& ln = ix->lanes[sl.lane];
-    if (sl.host_wire8) {
+    if (sl.plan.host_wire8) {
       // 8-byte records into pinned memory (a quarter of fs_row over PCIe, and no pageable
       // landing buffer in the copy's way), then fs_row on the host cores
       const size_t bytes = (size_t)hs.n_rows * 8;
@@ -1594,9 +1549,9 @@ extern "C" int fs_scan_benchmark(fs_index* ix, fs_corpus* c, uint32_t reps, doub
   FS_ENTER(ix->device);
   if (c->is_view) FS_TRY(corpus_ready(ix, c));
   hipStream_t s = ix->stream;
-  const int tpl = fs_scan_tpl(ix, c->n_tok);
-  const uint32_t n_bm = (uint32_t)((c->n_tok + 64 * tpl - 1) / (64 * tpl));
-  FS_TRY(ix->cur->w_qbm.reserve((size_t)n_bm * tpl));
+  const fs_plan pl = fs_plan_search(ix, c, FS_ROWS_DEVICE, *ix->cur, true);   // the chained kernels' scan
+  const uint32_t n_bm = pl.n_bm;
+  FS_TRY(ix->cur->w_qbm.reserve((size_t)n_bm * pl.tpl));
   FS_TRY(ix->cur->w_qcnt.reserve(n_bm));
   FS_TRY(fs_launch_scan(ix, c->dev(), ix->cur->w_qbm.p, ix->cur->w_qcnt.p, n_bm, s));   // warm
   FS_HIP(hipEventRecord(ix->ev_scan0, s));

@@ -165,6 +165,8 @@ struct alignas(16) fs_spos {
 
 struct fs_corpus;
 
+#define FS_SWITCH_UNSET (-0x7fffffff - 1)   // fs_switches: a size the environment does not name
+
 // Diagnostic switches (FS_* environment variables), read once at fs_index_create and
 // again only on fs_index_reload_switches: nothing on the per-search path calls getenv.
 struct fs_switches {
@@ -211,8 +213,47 @@ struct fs_switches {
   bool rows_coop = true;          // FS_ROWS_COOP=0: no shared rounds (every wave works off its own range's candidates)
   int rows_xpool = 0;             // FS_ROWS_XPOOL: records in a workgroup's pool for the shared rounds (tests: force the growth)
   int ranges_caprow = 0;          // FS_RANGES_CAPROW: staged records per wave range of k_scan_rows to start with (tests)
+  bool host_wire8 = true;         // FS_HOST_WIRE8=0: host rows of the exact pipeline cross PCIe as 32-byte fs_row, not as 8-byte records
+  bool host_zerocopy = true;      // FS_HOST_ZEROCOPY=0: those 8-byte records are copied behind the search instead of stored into pinned host memory by its last kernel
+  bool trace_begin = false;       // FS_TRACE_BEGIN: host time of every fs_search_corpus_begin on stderr (set-up, enqueue)
+  // read when the index is built (fs_index_create keeps what it used: a reload changes no layout)
+  int lanes = 0;                  // FS_LANES: streams the searches are spread over, 1 .. FS_LANES (0: FS_LANES_DEFAULT)
+  int filter_log2_words = FS_SWITCH_UNSET;    // FS_FILTER_LOG2_WORDS: size of the Bloom filter (clamped to 10 .. 15)
+  int sfilter_log2_words = FS_SWITCH_UNSET;   // FS_SFILTER_LOG2_WORDS: size of the sub-shingle filter
+  bool build_times = false;       // FS_BUILD_TIMES: seconds per stage of the index build on stderr
+  bool share_count = false;       // FS_SHARE_COUNT: counters of k_share_scan (fs_index_share_counts)
+  bool lsh_count = false;         // FS_LSH_COUNT: counters of k_lsh_sift* and k_lsh_enum (fs_index_lsh_counts)
 };
 void fs_read_switches(fs_switches* sw);
+
+// What one search launches (fs_plan.hip): decided once, by fs_plan_search, from the index, the
+// corpus, the rows mode and the lane's hints.  search_enqueue switches on `path`, the name, the
+// scan shape and the benchmark read the same plan.  Which capacity applies follows from the path;
+// fs_search_corpus_end grows that one and queues the same path again.
+enum fs_path {
+  FS_PATH_ROWS,        // k_scan_rows (tokens -> records in one kernel; k_compact behind it with several lanes)
+  FS_PATH_DIRECT,      // k_scan8 writing candidate records, k_verify_direct .. k_rows
+  FS_PATH_BITMAP,      // k_scan8 / k_scan_simple writing a bitmap, k_expand, k_verify .. k_rows
+  FS_PATH_NEAR_SIFT,   // general pipeline: k_near_sift (prefilter + wildcard filter, lists), the LSH work on those
+  FS_PATH_NEAR_CHAIN,  // general pipeline: k_scan_near8 / k_scan_near, k_expand, the LSH work on the candidates
+  FS_PATH_KEY_SCAN     // general pipeline, no integer prefilter: k_lsh_scan, or k_share_scan under the share rule
+};
+struct fs_plan {
+  fs_path path = FS_PATH_BITMAP;
+  bool exact = false;        // the exact n-gram pipeline (else the general one): fs_stats.path
+  bool near8 = false;        // NEAR_CHAIN: k_scan_near8 (else k_scan_near)
+  bool share_scan = false;   // KEY_SCAN: k_share_scan (else k_lsh_scan)
+  bool host_wire8 = false;   // FS_ROWS_HOST: 8-byte records cross PCIe, fs_row made on the host
+  int tpl = 4;               // tokens per lane of the bitmap layout
+  uint32_t n_bm = 0;         // sub-tiles of 64 * tpl tokens
+  uint32_t waves = 0, blocks = 0;   // ROWS: waves per workgroup, workgroups
+  int sub_k = 0;             // ROWS: K of the K-gram runs the kernel tests (0: the Bloom test of the n-gram)
+  // capacities to start with
+  uint32_t caprow = 0;       // ROWS: staged records per wave range
+  uint32_t capw = 0;         // DIRECT: candidate records per wave range
+  uint32_t caps = 0;         // NEAR_SIFT: list entries per wave range
+  uint64_t ccap = 0;         // every path but ROWS: entries of the per-candidate arrays
+};
 
 struct fs_index {
   fs_config cfg;
@@ -335,22 +376,15 @@ struct fs_index {
     uint64_t lane_seq = 0;            // Lane::enqueued when this search went in
     fs_corpus* c = nullptr;
     fs_row* rows = nullptr;
-    uint64_t cap = 0, ccap = 0, rcap = 0;
+    uint64_t cap = 0, rcap = 0;
     int mode = 0;
     bool header = false;              // FS_ROWS_HEADER: rows = 32-byte header + records
-    bool host_wire8 = false;          // FS_ROWS_HOST: 8-byte records cross PCIe, fs_row made on the host
-    bool host_direct = false;         //   ... stored into pinned host memory by the search's last kernel
-    bool exact = false;
-    uint32_t n_bm = 0, launches = 0, fallbacks = 0;
+    bool host_direct = false;         // FS_ROWS_HOST, plan.host_wire8: the records are stored into pinned host memory by the search's last kernel
+    fs_plan plan;                     // what this search launches; the path is fixed for the life of the ticket
+    uint32_t launches = 0, fallbacks = 0;
     bool timed = false;               // this search's scan carries timing events
     bool whole_timed = false;         // ... and ev_begin / ev_end bracket the whole search
-    int tpl = 4;                      // tokens per lane of the bitmap layout
     int lane = 0;                     // the lane (stream + workspaces) it was queued on
-    uint32_t capw = 0;                // direct path: record capacity per wave range (0: bitmap path)
-    uint32_t caps = 0;                // k_near_sift: list entries per wave range (0: the chained prefilter)
-    uint32_t caprow = 0;              // k_scan_rows: staged records per wave range
-    uint32_t fused_waves = 0;         // k_scan_rows: waves per workgroup (0: separate kernels)
-    uint32_t fused_blocks = 0;        //              workgroups
   };
   Slot slots[FS_SEARCH_SLOTS];
   bool sync_call = false;              // inside fs_search_corpus (begin + end in one call)
@@ -419,6 +453,14 @@ struct fs_corpus {
 
 void fs_view_sync(fs_corpus* v);       // fs_api.hip: a view's batch members from its base
 
+// fs_plan.hip.  A pure host-side function: nothing is queued and nothing is built.  `ln`: the lane
+// whose hints and workspaces size the starting capacities.  chained_only: the chained kernels of
+// the exact pipeline whatever else applies -- what a k_scan_rows search is repeated through when
+// its in-launch wait gave up, and what fs_scan_benchmark times.
+fs_plan fs_plan_search(const fs_index* ix, const fs_corpus* c, int rows_mode, const fs_index::Lane& ln,
+                       bool chained_only);
+const char* fs_plan_kernel_name(const fs_index* ix, const fs_plan& p);   // the kernel that dominates it (profile name)
+
 // ---- kernel launchers (fs_scan.hip / fs_post.hip / fs_build.hip) ----------
 // What a scan launch may produce beyond the bitmap (eight-tokens-per-lane kernel only):
 //   bsum/zero  the FS_CHUNKS chunk sums the next kernel needs and a cleared status block
@@ -443,7 +485,7 @@ int fs_launch_scan(const fs_index* ix, const CorpusDev& c, uint64_t* qbm, uint32
                    hipEvent_t e1 = nullptr, fs_scan_extra* extra = nullptr);
 bool fs_scan_direct_ok(const fs_index* ix, uint64_t n_tok);   // the direct path applies
 uint32_t fs_scan_pad_tokens();
-int fs_scan_tpl(const fs_index* ix, uint64_t n_tok);   // tokens per lane (bitmap layout)
+int fs_scan_tpl(const fs_index* ix);   // tokens per lane (bitmap layout)
 
 int fs_launch_post(fs_index* ix, fs_corpus* c, uint32_t n_sub, int tpl, uint32_t ccap,
                    uint32_t rcap, fs_row* d_rows, int wire, fs_status* host_st, hipStream_t s,
@@ -476,14 +518,11 @@ int fs_prof_mark(fs_index* ix, hipStream_t s, const char* name);      // fs_api.
 void fs_lsh_wild_of(const fs_index* ix, const fs_corpus* c, const uint32_t** wild, int* log2_wild,
                     const uint32_t** wild_tok);                        // fs_lsh.hip
 int fs_launch_stream_floor(fs_index* ix, fs_corpus* c, uint32_t reps, double* avg_ms);   // fs_scan.hip
-bool fs_near_fused(const fs_index* ix, const fs_corpus* c);            // fs_scan.hip: k_near_sift takes this search's prefilter
 uint32_t fs_near_ranges();                                              // wave ranges of k_near_sift
 int fs_launch_near_sift(const fs_index* ix, const fs_corpus* c, uint32_t* slist, uint32_t caps, uint32_t* scount,
                         uint32_t* bsum, fs_status* zero, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 // fs_scan.hip: the integer prefilter of the LSH pipeline ("all but one slot identical")
-bool fs_lsh_prefilter_ok(const fs_index* ix, const fs_corpus* c);
 bool fs_scan_near8_wanted(const fs_index* ix);
-bool fs_scan_near8(const fs_index* ix);
 int fs_scan_near_log2(const fs_index* ix);
 void fs_scan_near_bit(const fs_index* ix, const uint32_t* t, uint32_t* word, uint32_t* bit);
 int fs_launch_scan_near(const fs_index* ix, const fs_corpus* c, uint64_t* qbm, uint32_t* qcnt,
@@ -522,7 +561,6 @@ int fs_launch_compact_after_scan_rows(fs_index* ix, uint32_t n_ranges, uint32_t 
 uint32_t fs_scan_rows_shape(const fs_index* ix, const fs_corpus* c, uint32_t* blocks);   // waves per workgroup, 0: does not apply
 // what a k_scan_rows launch holds in LDS beside its per-wave state: log2 words of its filter, bytes of seeds (0: read from memory)
 void fs_scan_rows_lds(const fs_index* ix, int* filter_log2_words, uint32_t* seeds_bytes);
-bool fs_host_wire8(const fs_index* ix, bool exact);   // fs_api.hip: a host search brings its records over as 8-byte wire records
 int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blocks, uint32_t rcap, fs_row* d_rows,
                         int wire, uint32_t caprow, fs_status* host_st, hipStream_t s,
                         hipEvent_t e0, hipEvent_t e1, uint64_t* count_out, hipEvent_t done = nullptr,

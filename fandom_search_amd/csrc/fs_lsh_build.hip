@@ -774,7 +774,7 @@ static int fs_build_share(fs_index* ix) {
       ix->log2_smap = lm;
     }
   }
-  if (getenv("FS_SHARE_COUNT")) {
+  if (ix->sw.share_count) {
     FS_TRY(ix->d_share_cnt.reserve(16));
     FS_HIP(hipMemsetAsync(ix->d_share_cnt.p, 0, 16 * sizeof(uint32_t), s));
   }
@@ -949,7 +949,7 @@ int fs_lsh_build(fs_index* ix) {
     FS_HIP(hipStreamSynchronize(s));           // the scratch buffers die with this scope
   }
   static_assert(kCntLsh <= FS_LSH_COUNTERS, "fs_index_lsh_counts returns every counter");
-  if (getenv("FS_LSH_COUNT")) {
+  if (ix->sw.lsh_count) {
     FS_TRY(ix->d_lsh_cnt.reserve(2 * FS_LSH_COUNTERS));
     FS_HIP(hipMemsetAsync(ix->d_lsh_cnt.p, 0, FS_LSH_COUNTERS * sizeof(uint64_t), s));
   }

@@ -1247,8 +1247,7 @@ int launch_tpl8(const fs_index* ix, const CorpusDev& c, uint64_t* qbm, uint32_t*
 
 // tokens per lane (bitmap layout) of the chained kernels' scan: eight with k_scan8
 // (n = 2..8), four with k_scan_simple (any n; FS_SCAN_TPL=4 or FS_SCAN_VARIANT=simple ask for it)
-int fs_scan_tpl(const fs_index* ix, uint64_t n_tok) {
-  (void)n_tok;
+int fs_scan_tpl(const fs_index* ix) {
   if (ix->sw.scan_simple || ix->sw.scan_tpl == 4) return 4;
   const int n = ix->cfg.window_size;
   return n >= 2 && n <= 8 ? 8 : 4;
@@ -1262,7 +1261,7 @@ uint32_t fs_scan_pad_tokens() { return 512 * 8 + 64; }
 // which is also the limit of the eight-tokens-per-lane kernel unless it is forced.
 bool fs_scan_direct_ok(const fs_index* ix, uint64_t n_tok) {
   if (!ix->sw.scan_direct) return false;
-  return fs_scan_tpl(ix, n_tok) == 8 && n_tok + 1024 < (1ull << 26);
+  return fs_scan_tpl(ix) == 8 && n_tok + 1024 < (1ull << 26);
 }
 
 // extra (optional, see fs_scan_extra): honoured by the eight-tokens-per-lane kernel
@@ -1272,7 +1271,7 @@ int fs_launch_scan(const fs_index* ix, const CorpusDev& c, uint64_t* qbm, uint32
                    fs_scan_extra* extra) {
   if (extra) { extra->counted = false; extra->direct = false; }
   const int n = ix->cfg.window_size;
-  if (fs_scan_tpl(ix, c.n_tok) == 8) {
+  if (fs_scan_tpl(ix) == 8) {
     switch (n) {
       case 2: return launch_tpl8<2>(ix, c, qbm, qcnt, n_bm_words, s, e0, e1, extra);
       case 3: return launch_tpl8<3>(ix, c, qbm, qcnt, n_bm_words, s, e0, e1, extra);
@@ -1550,7 +1549,6 @@ int fs_lsh_prefilter_mode(const fs_index* ix, const fs_corpus* c) {
     return n == 6 || n == 7 || n == 8 || n == 9 || n == 10 || n == 12 ? 2 : 0;
   return 0;
 }
-bool fs_lsh_prefilter_ok(const fs_index* ix, const fs_corpus* c) { return fs_lsh_prefilter_mode(ix, c) != 0; }
 int fs_scan_near_k(int n) { return fs_near_k(n); }
 // n >= 7: the eight-tokens-per-lane form (k_scan_near8: polynomial 3-gram hash, at most 2^14
 // filter words, k_scan8's bitmap); n = 6 keeps k_scan_near with its second filter
@@ -1561,12 +1559,8 @@ bool fs_scan_near8_wanted(const fs_index* ix) {
   // the better prefilter there)
   return ix->sw.scan_near8 && (n >= 7 || (n == 6 && ix->sw.near_fused)) && (n <= 10 || n == 12);
 }
-// k_near_sift (prefilter + wildcard filter in one kernel, lists per wave range) takes the search
-bool fs_near_fused(const fs_index* ix, const fs_corpus* c) {
-  return ix->sw.near_fused && fs_scan_near8(ix) && fs_lsh_prefilter_ok(ix, c);
-}
 uint32_t fs_near_ranges() { return (uint32_t)fsdev::kNB * 4u; }
-bool fs_scan_near8(const fs_index* ix) { return ix->near8; }
+static bool fs_scan_near8(const fs_index* ix) { return ix->near8; }
 int fs_scan_near_log2(const fs_index* ix) {
   return fs_scan_near8(ix) ? std::min(ix->log2_words, FS_SUB_MAX_LOG2_WORDS) : ix->log2_words;
 }

@@ -274,6 +274,8 @@ def test_host_rows_stored_by_the_search_or_copied(synth_base, monkeypatch):
             monkeypatch.setenv(k, v)
         ix = ScriptIndex(script, swords, emb, synth.lsh_normals(6), cfg=cfg)
         c = ix.corpus(tok, off, synth_base["chars"], synth_base["off"])
+        # (the switches are read per index: this one's form of the host records)
+        assert ix.scan_shape(c)["host_wire8"] == (0 if env.get("FS_HOST_WIRE8") == "0" else 1)
         got, st = ix.search(c, cap=16)                   # (grows to what the search reports)
         again, _ = ix.search(c, reuse=True)
         assert len(got) > 500 and got.tobytes() == again.tobytes()
