@@ -172,6 +172,21 @@ assert LINE_CELL_DTYPE.itemsize == 32
 FS_LINES_MAX_BYTES = 1 << 30
 LINES_MS_NAMES = ("tables", "walk", "total")
 
+# fs_fragment, fs_fragment_work: 32 bytes each
+FRAGMENT_DTYPE = np.dtype([("first", np.uint32), ("last", np.uint32), ("works", np.uint32),
+                           ("exact_works", np.uint32), ("start_works", np.uint32),
+                           ("end_works", np.uint32), ("first_work", np.uint32),
+                           ("reserved", np.uint32)])
+assert FRAGMENT_DTYPE.itemsize == 32
+FRAGMENT_WORK_DTYPE = np.dtype([("work", np.uint32), ("runs", np.uint32), ("covered", np.uint32),
+                                ("held", np.uint32), ("exact", np.uint32),
+                                ("longest_first", np.uint32), ("longest_last", np.uint32),
+                                ("longest_works", np.uint32)])
+assert FRAGMENT_WORK_DTYPE.itemsize == 32
+FS_FRAGMENTS_MAX_WORDS = 4096
+FS_FRAGMENTS_MAX_BYTES = 1 << 30
+FRAGMENTS_MS_NAMES = ("runs", "spread", "list", "works", "total")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

@@ -19,7 +19,9 @@ the match files of several scripts and says which script each fan passage quotes
 (fandom_search_amd/sources.py), and `alignments`, which aligns every fan work against the script
 with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignments.py), and
 `lines`, which ranks the lines of the script markup by the works quoting them and says how
-completely each is quoted (fandom_search_amd/lines.py).  The
+completely each is quoted (fandom_search_amd/lines.py), and `fragments`, which lists the
+phrases the works quote word for word, each with the works quoting it in full
+(fandom_search_amd/fragments.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -411,10 +413,10 @@ def full_parser():
 
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
-    behind it the commands added since (`lines`)."""
+    behind it the commands added since (`lines`, `fragments`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -436,6 +438,30 @@ def ao3_parser():
                          help='fewest words of a line, as a whole percentage of its '
                               'words, a work covers to count in MOST_WORKS, 1 to 100, '
                               'default 50')])
+
+    _analysis(subparsers, 'fragments',
+              'lists the phrases the fan works quote word for word: every stretch of '
+              'the script that --min-works works quote in full and that loses a work '
+              'with one more word on either side, a phrase inside a longer quote '
+              'included; per work its unbroken runs and the fragments they hold',
+              'prefix of the two csv files, PREFIX-fragments.csv and '
+              'PREFIX-fragments-works.csv (default: the input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_length < 1
+                           or a.max_gap < 0 or a.top < 0),
+                '--min-words, --min-works and --min-length must be at least 1, --max-gap '
+                'and --top at least 0'),
+               (lambda a: not a.min_length <= a.max_words <= 4096,
+                '--max-words must be from --min-length to 4096')],
+              last=[_own('--min-works', default=2, type=int,
+                         help='fewest works quoting a listed fragment in full, default 2'),
+                    _own('--min-length', default=3, type=int,
+                         help='fewest words of a listed fragment, default 3'),
+                    _own('--max-words', default=128, type=int,
+                         help='most words of a listed fragment, up to 4096, default 128; '
+                              'longer ones are not listed, and a stretch of this many '
+                              'words that goes on with the same works is none'),
+                    _own('--top', default=0, type=int,
+                         help='keep the first N fragments of the ranking, default 0: all')])
     return parser
 
 

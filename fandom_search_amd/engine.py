@@ -623,6 +623,30 @@ class ScriptIndex(object):
                           [abi.LINE_WORK_DTYPE, abi.LINE_CELL_DTYPE], list(caps), out_ptrs,
                           "work or cell buffer too small")
 
+    def fragments_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, min_works=2,
+                         min_length=3, max_words=128, out_ptrs=None, caps=None):
+        """`fragments` over device-resident fs_row records sorted by (work, fan_ix)
+        (fs_fragments_rows): the closed frequent intervals of the script in (words, first)
+        order, and per active work its runs and the fragments they hold.  Without `out_ptrs`:
+        (abi.FRAGMENT_DTYPE[n_frags], abi.FRAGMENT_WORK_DTYPE[active works]) on the host.  With
+        `out_ptrs` = device addresses (fragments, works, buffers of `caps` = (fragments, works)
+        of them): (fragments, active works); FsError(FS_E_CAPACITY) with .required = both
+        counts when a buffer is too small (both untouched then).  Buffers torch has only just
+        produced go in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_fragments_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                       int(min_words), int(max_gap), int(min_works),
+                                       int(min_length), int(max_words), C.c_void_p(grown[0]),
+                                       int(caps[0]), C.byref(counts[0]), C.c_void_p(grown[1]),
+                                       int(caps[1]), C.byref(counts[1]))
+        if caps is None:
+            caps = (0, 0) if out_ptrs is not None else (4096, 256)
+        return _rows_call("fs_fragments_rows", call, [], [abi.FRAGMENT_DTYPE,
+                                                          abi.FRAGMENT_WORK_DTYPE], list(caps),
+                          out_ptrs, "fragment or work buffer too small")
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

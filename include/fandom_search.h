@@ -886,6 +886,86 @@ int fs_lines_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t 
  * for a pass that did not run.  tools/lines_bench.py. */
 int fs_lines_times(double* ms);
 
+/* `ao3.py fragments`: the phrases the fan works quote word for word, the closed frequent
+ * intervals of the script.  Records, passages, active works (N of them, numbered in work order)
+ * and the coverage C_w as for fs_pairs: every script word from a passage's first record to its
+ * last, bridged words included, a word quoted twice once.
+ *  - A run of a work is a maximal stretch of consecutive script words in C_w; passages of one
+ *    work that abut or overlap make one run.  A work holds [a, b] when one of its runs contains
+ *    it.  S(a, b) is the number of active works holding [a, b]; 0 outside the script.
+ *  - [a, b] of k = b - a + 1 words is a fragment when min_length <= k <= max_words, S(a, b) >=
+ *    min_works, and it is closed: S(a, b) > S(a - 1, b) and S(a, b) > S(a, b + 1).  Closedness
+ *    looks at every length: a stretch of max_words words whose extension has the same support is
+ *    no fragment, and a fragment longer than max_words is not listed.  Runs longer than max_words
+ *    count for every interval inside them.
+ * Every output is an integer: sums and minima, places from scanned counts. */
+typedef struct fs_fragment {
+  uint32_t first, last;      /* script word indices                                      */
+  uint32_t works;            /* S(first, last)                                           */
+  uint32_t exact_works;      /* runs that are exactly [first, last]                      */
+  uint32_t start_works;      /* runs starting at first and reaching last = S(first, last)
+                                - S(first - 1, last), >= 1                               */
+  uint32_t end_works;        /* runs ending at last that hold first = S(first, last) -
+                                S(first, last + 1), >= 1                                 */
+  uint32_t first_work;       /* smallest work number with a run counted in start_works   */
+  uint32_t reserved;         /* 0                                                        */
+} fs_fragment;               /* 32 bytes                                                 */
+
+typedef struct fs_fragment_work {
+  uint32_t work;             /* work number of this active work                          */
+  uint32_t runs;             /* its runs                                                 */
+  uint32_t covered;          /* |C_w|                                                    */
+  uint32_t held;             /* listed fragments inside one of its runs (modulo 2^32)    */
+  uint32_t exact;            /* its runs that are themselves listed fragments            */
+  uint32_t longest_first;    /* its longest run, the first among equals                  */
+  uint32_t longest_last;
+  uint32_t longest_works;    /* S of that run; 0xFFFFFFFF when its length is outside
+                                [min_length, max_words]                                  */
+} fs_fragment_work;          /* 32 bytes                                                 */
+
+#define FS_FRAGMENTS_MAX_WORDS 4096u
+/* Counted: the coverage (ceil(n_script / 64) * ceil(N / 64) * 64 * 8 bytes), the run list (12
+ * bytes per passage of the records, kept or not, and with the dedupe 16 bytes per slot of its
+ * table, the power of two at or above twice that number), and four tables (runs starting, runs
+ * ending, first work, exact runs) of (min(max_words, n_script) - min_length + 1) * n_script
+ * 32-bit words each.  Their sum may be up to this. */
+#define FS_FRAGMENTS_MAX_BYTES (1u << 30)
+
+/* Host columns in; up to frags_cap fragments in (words, first) ascending order and up to
+ * works_cap active works in active order out, on HIP device `device`.  Both entry points:
+ * FS_E_INVALID for null arguments, min_words == 0, min_length == 0, max_words < min_length,
+ * records out of (work, fan_ix) order, a work >= n_works or an orig_ix >= n_script;
+ * FS_E_UNSUPPORTED for max_words > FS_FRAGMENTS_MAX_WORDS, n_rows >= 2^32, n_script >
+ * FS_WORKS_MAX_SCRIPT or tables above FS_FRAGMENTS_MAX_BYTES (the message names both factors of
+ * a table and says to lower max_words); FS_E_CAPACITY with *n_frags and *n_active = the counts
+ * required when either cap is smaller (both buffers untouched then).  n_rows == 0: both counts
+ * 0, without device work.
+ * Diagnostics of the environment, read on each call; the output is the same wherever they
+ * stand:
+ *   FS_FRAGMENTS_DEDUP      1 (default): the runs are reduced to the distinct (first, last) with
+ *                           a count and a smallest work before they are spread over the tables;
+ *                           0: every run is spread by itself
+ *   FS_FRAGMENTS_HASH_BITS  keeps that many bits of the hash behind the dedupe (0: every key
+ *                           probes from slot 0) */
+int fs_fragments(int device, const uint32_t* work, const uint32_t* fan_ix,
+                 const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                 uint32_t min_words, uint32_t max_gap, uint32_t min_works, uint32_t min_length,
+                 uint32_t max_words, fs_fragment* frags, uint64_t frags_cap, uint64_t* n_frags,
+                 fs_fragment_work* works, uint64_t works_cap, uint64_t* n_active);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when they
+ * are written. */
+int fs_fragments_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                      uint32_t min_words, uint32_t max_gap, uint32_t min_works,
+                      uint32_t min_length, uint32_t max_words, fs_fragment* d_frags,
+                      uint64_t frags_cap, uint64_t* n_frags, fs_fragment_work* d_works,
+                      uint64_t works_cap, uint64_t* n_active);
+/* HIP-event milliseconds of the last fs_fragments / fs_fragments_rows call on this thread: runs
+ * (coverage and the run list), spread (the dedupe and the tables), list (both row scans and the
+ * offsets between them), works (held fragments, the per-work records), and the total
+ * of the four; 0 for a pass that did not run.  tools/fragments_bench.py. */
+int fs_fragments_times(double* ms);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
