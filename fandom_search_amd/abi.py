@@ -187,6 +187,21 @@ FS_FRAGMENTS_MAX_WORDS = 4096
 FS_FRAGMENTS_MAX_BYTES = 1 << 30
 FRAGMENTS_MS_NAMES = ("runs", "spread", "list", "works", "total")
 
+# fs_digest_pick, fs_digest_work: 32 bytes each
+DIGEST_PICK_DTYPE = np.dtype([("work", np.uint32), ("covered", np.uint32),
+                              ("new_words", np.uint32), ("new_runs", np.uint32),
+                              ("longest_first", np.uint32), ("longest_words", np.uint32),
+                              ("cum_words", np.uint32), ("reserved", np.uint32)])
+assert DIGEST_PICK_DTYPE.itemsize == 32
+DIGEST_WORK_DTYPE = np.dtype([("work", np.uint32), ("covered", np.uint32),
+                              ("pick_rank", np.uint32), ("in_picks", np.uint32),
+                              ("subsumed_at", np.uint32), ("best_pick", np.uint32),
+                              ("best_shared", np.uint32), ("reserved", np.uint32)])
+assert DIGEST_WORK_DTYPE.itemsize == 32
+FS_DIGEST_MAX_BYTES = 1 << 30
+# fs_digest_times: three passes and their total in ms, then two counts
+DIGEST_MS_NAMES = ("coverage", "rounds", "works", "total", "rounds_enqueued", "tiles_read")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

@@ -21,7 +21,8 @@ with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignmen
 `lines`, which ranks the lines of the script markup by the works quoting them and says how
 completely each is quoted (fandom_search_amd/lines.py), and `fragments`, which lists the
 phrases the works quote word for word, each with the works quoting it in full
-(fandom_search_amd/fragments.py).  The
+(fandom_search_amd/fragments.py), and `digest`, which picks the fewest works that together show
+everything the works quote (fandom_search_amd/digest.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -413,10 +414,10 @@ def full_parser():
 
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
-    behind it the commands added since (`lines`, `fragments`)."""
+    behind it the commands added since (`lines`, `fragments`, `digest`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -462,6 +463,27 @@ def ao3_parser():
                               'words that goes on with the same works is none'),
                     _own('--top', default=0, type=int,
                          help='keep the first N fragments of the ranking, default 0: all')])
+
+    _analysis(subparsers, 'digest',
+              'picks the fewest fan works that together show what the works quote: '
+              'the work covering most of the script first, then always the work that '
+              'adds most words to what the picks so far cover; per pick what it adds '
+              'and how much of the quoted script the picks cover by then, per work how '
+              'much of it the picks show and which pick is most like it',
+              'prefix of the two csv files, PREFIX-digest.csv and '
+              'PREFIX-digest-works.csv (default: the input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_gain < 1 or a.max_gap < 0
+                           or a.picks < 0),
+                '--min-words and --min-gain must be at least 1, --max-gap and --picks at '
+                'least 0'),
+               (lambda a: not 1 <= a.cover <= 100, '--cover must be from 1 to 100')],
+              last=[_own('--picks', default=0, type=int,
+                         help='most works to pick, default 0: no limit'),
+                    _own('--cover', default=100, type=int,
+                         help='stop once the picks cover this whole percentage of the '
+                              'script words any work quotes, 1 to 100, default 100'),
+                    _own('--min-gain', default=1, type=int,
+                         help='stop when no work adds this many new words, default 1')])
     return parser
 
 

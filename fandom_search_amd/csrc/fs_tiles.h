@@ -1,6 +1,7 @@
 // fs_tiles.h -- the coverage matrix of the active works and its tiled AND/popcount product,
-// shared by fs_pairs.hip and fs_clusters.hip: the passes from the run heads to the row
-// popcounts (CoverJob) and the 64 x 64 counts of a row tile against a column tile (tile_counts).
+// shared by fs_pairs.hip, fs_clusters.hip, fs_lines.hip, fs_fragments.hip and fs_digest.hip: the
+// passes from the run heads to the row popcounts (CoverJob) and the 64 x 64 counts of a row tile
+// against a column tile (tile_counts), of the matrix itself or of another in its layout.
 //
 // The matrix is stored by tiles of 64 active works, k-major: word k of row r of tile t is at
 // cov[(t * nk + k) * 64 + r].  A K-slice of a tile is one contiguous piece, staged by a straight
@@ -92,18 +93,17 @@ __global__ __launch_bounds__(kTile) void k_pairs_covered(CoverArgs a) {
   a.covered[(size_t)blockIdx.x * kTile + threadIdx.x] = c;
 }
 
-// The 64 x 64 counts of row tile ti against column tile tj into s_sh (stride kShStride), by a
-// workgroup of kBlock threads with s_a and s_b of kSlice * kTile words each; the workgroup is
-// synchronised on return.
-__device__ inline void tile_counts(const CoverArgs& a, uint32_t ti, uint32_t tj,
-                                   unsigned long long* s_a, unsigned long long* s_b,
+// The 64 x 64 counts of the row tile at ga against the column tile at gb, two tiles of nk words
+// in the matrix's layout (16-byte aligned), into s_sh (stride kShStride), by a workgroup of
+// kBlock threads with s_a and s_b of kSlice * kTile words each; the workgroup is synchronised on
+// return.
+__device__ inline void tile_counts(const unsigned long long* ga, const unsigned long long* gb,
+                                   uint32_t nk, unsigned long long* s_a, unsigned long long* s_b,
                                    uint32_t* s_sh) {
   const uint32_t ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   uint32_t acc[4][4] = {};
-  const unsigned long long* ga = a.cov + (size_t)ti * a.nk * kTile;
-  const unsigned long long* gb = a.cov + (size_t)tj * a.nk * kTile;
-  for (uint32_t k0 = 0; k0 < a.nk; k0 += kSlice) {
-    const uint32_t kc = a.nk - k0 < kSlice ? a.nk - k0 : kSlice;
+  for (uint32_t k0 = 0; k0 < nk; k0 += kSlice) {
+    const uint32_t kc = nk - k0 < kSlice ? nk - k0 : kSlice;
     const ulonglong2* va = reinterpret_cast<const ulonglong2*>(ga + (size_t)k0 * kTile);
     const ulonglong2* vb = reinterpret_cast<const ulonglong2*>(gb + (size_t)k0 * kTile);
     for (uint32_t v = threadIdx.x; v < kc * (kTile / 2); v += kBlock) {
@@ -129,6 +129,14 @@ __device__ inline void tile_counts(const CoverArgs& a, uint32_t ti, uint32_t tj,
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) s_sh[(ty * 4 + i) * kShStride + tx * 4 + j] = acc[i][j];
   __syncthreads();
+}
+
+// the same for row tile ti against column tile tj of the coverage matrix
+__device__ inline void tile_counts(const CoverArgs& a, uint32_t ti, uint32_t tj,
+                                   unsigned long long* s_a, unsigned long long* s_b,
+                                   uint32_t* s_sh) {
+  tile_counts(a.cov + (size_t)ti * a.nk * kTile, a.cov + (size_t)tj * a.nk * kTile, a.nk, s_a,
+              s_b, s_sh);
 }
 
 // The shared passes of one call, in this order: number(), the caller's own refusals over

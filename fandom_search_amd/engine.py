@@ -647,6 +647,33 @@ class ScriptIndex(object):
                                                           abi.FRAGMENT_WORK_DTYPE], list(caps),
                           out_ptrs, "fragment or work buffer too small")
 
+    def digest_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, picks=0,
+                      cover=100, min_gain=1, out_ptrs=None, caps=None):
+        """`digest` over device-resident fs_row records sorted by (work, fan_ix)
+        (fs_digest_rows): the greedy picks in pick order, per active work what the picks show
+        of it, and TOTAL, the script words any work covers.  Without `out_ptrs`:
+        (abi.DIGEST_PICK_DTYPE[picks made], abi.DIGEST_WORK_DTYPE[active works], TOTAL) on the
+        host.  With `out_ptrs` = device addresses (picks, works, buffers of `caps` = (picks,
+        works) of them): (picks made, active works, TOTAL); FsError(FS_E_CAPACITY) with
+        .required = both counts when a buffer is too small (both untouched then).  Buffers torch
+        has only just produced go in after torch_ready()."""
+        L = _lib.load()
+        total = C.c_uint64(0)
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_digest_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    int(min_words), int(max_gap), int(picks), int(cover),
+                                    int(min_gain), C.c_void_p(grown[0]), int(caps[0]),
+                                    C.byref(counts[0]), C.c_void_p(grown[1]), int(caps[1]),
+                                    C.byref(counts[1]), C.byref(total))
+        if caps is None:                    # (neither count is above the works)
+            room = max(1, min(int(n_works), int(n_rows)))
+            caps = (0, 0) if out_ptrs is not None else (room, room)
+        got = _rows_call("fs_digest_rows", call, [], [abi.DIGEST_PICK_DTYPE,
+                                                      abi.DIGEST_WORK_DTYPE], list(caps),
+                         out_ptrs, "pick or work buffer too small")
+        return tuple(got) + (int(total.value),)
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

@@ -966,6 +966,87 @@ int fs_fragments_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint3
  * of the four; 0 for a pass that did not run.  tools/fragments_bench.py. */
 int fs_fragments_times(double* ms);
 
+/* `ao3.py digest`: the fewest works that show what the fan works quote, greedy maximum coverage.
+ * Records, passages, active works (N of them, numbered in work order) and the coverage C_w as
+ * for fs_pairs.  U is the union of every C_w and TOTAL = |U|.
+ *  - K_0 is empty.  In round r = 1, 2, ... gain_r(w) = |C_w \ K_{r-1}|; the pick p_r is the
+ *    active work with the largest gain, the smaller work number on a tie; K_r = K_{r-1} | C_{p_r},
+ *    and every word of C_{p_r} \ K_{r-1}, the new words of the pick, gets the stamp r.
+ *  - Tested before pick r is made: stop when max_picks != 0 and r - 1 == max_picks; when the
+ *    largest gain is below min_gain; when |K_{r-1}| * 100 >= cover * TOTAL (64 bits; exactly at
+ *    the bound stops).  With max_picks 0, cover 100 and min_gain 1 the rounds end at K = U.  R,
+ *    the picks made, is at most min(N, TOTAL).
+ * Every output is an integer. */
+typedef struct fs_digest_pick {
+  uint32_t work;             /* work number of the pick; record r - 1 is pick r          */
+  uint32_t covered;          /* |C_w|                                                    */
+  uint32_t new_words;        /* its gain, >= min_gain                                    */
+  uint32_t new_runs;         /* maximal runs of consecutive new words                    */
+  uint32_t longest_first;    /* the longest of them, the first among equals: its first   */
+  uint32_t longest_words;    /* script word and its length                               */
+  uint32_t cum_words;        /* |K_r|                                                    */
+  uint32_t reserved;         /* 0                                                        */
+} fs_digest_pick;            /* 32 bytes                                                 */
+
+typedef struct fs_digest_work {
+  uint32_t work;             /* work number of this active work                          */
+  uint32_t covered;          /* |C_w|                                                    */
+  uint32_t pick_rank;        /* r when it is pick r; 0xFFFFFFFF when it was not picked   */
+  uint32_t in_picks;         /* |C_w & K_R|                                              */
+  uint32_t subsumed_at;      /* the largest stamp over C_w when K_R holds all of C_w: the
+                                fewest first picks that show all it quotes; else
+                                0xFFFFFFFF                                               */
+  uint32_t best_pick;        /* the rank of the pick sharing most words with it, the
+                                earlier pick on a tie; 0xFFFFFFFF when none shares one   */
+  uint32_t best_shared;      /* |C_w & C_pick| of that pick; 0 without                   */
+  uint32_t reserved;         /* 0                                                        */
+} fs_digest_work;            /* 32 bytes                                                 */
+
+/* Counted: the coverage matrix (ceil(n_script / 64) * ceil(N / 64) * 64 * 8 bytes), the rows of
+ * the picks gathered for the best-pick pass (the same per 64 picks, for min(N, n_script) picks or
+ * max_picks if that is fewer), and the arrays per work (16 bytes), per 64 script words (272
+ * bytes) and per pick (32 bytes).  Their sum may be up to this. */
+#define FS_DIGEST_MAX_BYTES (1u << 30)
+
+/* Host columns in; the R picks in pick order, the N active works in active order and TOTAL out,
+ * on HIP device `device`.  Both entry points: FS_E_INVALID for null arguments, min_words == 0,
+ * min_gain == 0, cover outside 1..100, records out of (work, fan_ix) order, a work >= n_works or
+ * an orig_ix >= n_script; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or
+ * tables above FS_DIGEST_MAX_BYTES (the message names the three parts); FS_E_CAPACITY with
+ * *n_picks and *n_active = the counts required when either cap is smaller (both buffers untouched
+ * then; *total_words is set).  n_rows == 0: all three counts 0, without device work.
+ * Diagnostics of the environment, read on each call; the output is the same wherever they
+ * stand:
+ *   FS_DIGEST_LAZY   1 (default): a tile of 64 works is left unread in a round when the largest
+ *                    gain its works had when last computed is below the gain already found; 0:
+ *                    every tile with a work left is read in every round
+ *   FS_DIGEST_SEED_TILES  the next round's best is seeded, with the recomputed gain of the work
+ *                    that had the largest gain when last computed, above this many tiles of 64
+ *                    active works, default 256; below, every tile's workgroup runs at once and
+ *                    a tile left unread shortens no round
+ *   FS_DIGEST_BATCH  rounds enqueued between two looks at the device's done word, default 64
+ *   FS_DIGEST_COUNT  1: the tiles read are counted (fs_digest_times) */
+int fs_digest(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t min_words,
+              uint32_t max_gap, uint32_t max_picks, uint32_t cover, uint32_t min_gain,
+              fs_digest_pick* picks, uint64_t picks_cap, uint64_t* n_picks,
+              fs_digest_work* works, uint64_t works_cap, uint64_t* n_active,
+              uint64_t* total_words);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when they
+ * are written. */
+int fs_digest_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   uint32_t min_words, uint32_t max_gap, uint32_t max_picks, uint32_t cover,
+                   uint32_t min_gain, fs_digest_pick* d_picks, uint64_t picks_cap,
+                   uint64_t* n_picks, fs_digest_work* d_works, uint64_t works_cap,
+                   uint64_t* n_active, uint64_t* total_words);
+/* Six numbers of the last fs_digest / fs_digest_rows call on this thread.  HIP-event
+ * milliseconds: coverage (with the union and the first bounds), rounds (every batch and the
+ * host's looks between them), works (the best-pick product and the per-work records), and the
+ * total of the three; 0 for a pass that did not run.  Then the rounds enqueued, and the tiles
+ * the gain pass read in them (0 unless FS_DIGEST_COUNT=1).  tools/digest_bench.py. */
+int fs_digest_times(double* ms);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
