@@ -85,10 +85,12 @@ class FsScanShape(C.Structure):
                 ("overflow_buckets", C.c_uint32),
                 ("wide_buckets", C.c_uint32),
                 ("host_wire8", C.c_uint32),
-                ("reserved", C.c_uint32 * 3)]
+                ("ids16", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
 
     def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+        # (the launch shape; which id stream the scan reads is ScriptIndex.scan_ids16)
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name not in ("reserved", "ids16")}
 
 
 # fs_row: 32 bytes

@@ -61,6 +61,7 @@ GramIndexDev fs_index::gram_dev() const {
 CorpusDev fs_corpus::dev() const {
   CorpusDev c;
   c.tok = d_tok.p; c.str = has_str ? d_str.p : nullptr; c.work_off = d_work_off.p;
+  c.tok16 = tok16_ok ? d_tok16.p : nullptr;
   c.blk_work = reinterpret_cast<const uint2*>(d_blk_work.p);
   c.blk4 = reinterpret_cast<const uint4*>(d_blk4.p);
   c.ctab = reinterpret_cast<const uint4*>(d_ctab.p);
@@ -100,6 +101,7 @@ void fs_read_switches(fs_switches* sw) {
   sw->scan_capw = num("FS_SCAN_CAPW");
   if (const char* e = getenv("FS_SCAN_ROWS")) sw->scan_rows = e[0] != '0';
   if (const char* e = getenv("FS_SCAN_SUB")) sw->scan_sub = e[0] != '0';
+  sw->scan_ids16 = !getenv("FS_SCAN_IDS16") || num("FS_SCAN_IDS16") != 0;
   sw->ranges_caprow = num("FS_RANGES_CAPROW");
   sw->diag = num("FS_DIAG");
   if (const char* e = getenv("FS_LSH_GRAMTAB")) sw->lsh_gramtab = atoi(e) != 0;
@@ -629,6 +631,7 @@ extern "C" int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* ou
   out->overflow_buckets = ix->n_overflow;
   out->wide_buckets = ix->n_disp_wide;
   out->host_wire8 = p.host_wire8 ? 1u : 0u;
+  out->ids16 = p.ids16 ? 1u : 0u;
   return FS_OK;
 }
 
@@ -659,6 +662,7 @@ void fs_view_sync(fs_corpus* v) {
   v->n_tok = b->n_tok; v->n_works = b->n_works; v->n_str = b->n_str;
   v->windows = b->windows; v->has_oov = b->has_oov; v->has_str = b->has_str;
   v->d_tok.p = b->d_tok.p; v->d_tok.n = b->d_tok.n;
+  v->d_tok16.p = b->d_tok16.p; v->d_tok16.n = b->d_tok16.n; v->tok16_ok = b->tok16_ok;
   v->d_str.p = b->d_str.p; v->d_str.n = b->d_str.n;
   v->d_chars.p = b->d_chars.p; v->d_chars.n = b->d_chars.n;
   v->d_blk_work.p = b->d_blk_work.p; v->d_blk_work.n = b->d_blk_work.n;
@@ -669,6 +673,7 @@ void fs_view_sync(fs_corpus* v) {
 
 static void fs_view_unalias(fs_corpus* v) {
   v->d_tok.p = nullptr; v->d_tok.n = 0;
+  v->d_tok16.p = nullptr; v->d_tok16.n = 0; v->tok16_ok = false;
   v->d_str.p = nullptr; v->d_str.n = 0;
   v->d_chars.p = nullptr; v->d_chars.n = 0;
   v->d_blk_work.p = nullptr; v->d_blk_work.n = 0;
@@ -737,6 +742,11 @@ extern "C" int fs_corpus_update_begin(fs_corpus* c, const uint32_t* tok_vec,
   FS_TRY(c->d_tok.reserve(T + pad));
   FS_HIP(hipMemsetAsync(c->d_tok.p + T, 0, pad * sizeof(uint32_t), cs));
   if (T) FS_HIP(hipMemcpyAsync(c->d_tok.p, tok_vec, T * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+  // the ids once more as 16-bit words (2 bytes per token, written by the check below, which
+  // reads every id anyway); whether they fit is known when the check is read
+  c->tok16_ok = false;
+  FS_TRY(c->d_tok16.reserve(T + pad));
+  FS_HIP(hipMemsetAsync(c->d_tok16.p + T, 0, pad * sizeof(uint16_t), cs));
   if (tok_str) {
     FS_TRY(c->d_str.reserve(T + FS_MAX_WINDOW + 1));
     FS_HIP(hipMemsetAsync(c->d_str.p + T, 0, (FS_MAX_WINDOW + 1) * sizeof(uint32_t), cs));
@@ -753,7 +763,7 @@ extern "C" int fs_corpus_update_begin(fs_corpus* c, const uint32_t* tok_vec,
   FS_TRY(c->d_check.reserve(4));
   FS_HIP(hipMemsetAsync(c->d_check.p, 0, 4 * sizeof(uint32_t), cs));
   FS_TRY(fs_launch_corpus_check(c->d_tok.p, tok_str ? c->d_str.p : nullptr, (uint32_t)T,
-                                c->d_check.p, cs));
+                                c->d_check.p, c->d_tok16.p, cs));
   FS_HIP(hipMemcpyAsync(c->h_check, c->d_check.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
   FS_HIP(hipEventRecord(c->ev_ready, cs));
   c->pending = true;
@@ -784,6 +794,7 @@ static int corpus_finish_upload(fs_corpus* c, const fs_index* ix) {
     return FS_E_INVALID;
   }
   c->has_oov = any_oov != 0;
+  c->tok16_ok = max_row_plus1 <= 65536u && !any_oov;
   c->prep_due = true;
   return FS_OK;
 }
@@ -1098,7 +1109,7 @@ static int search_enqueue(fs_index* ix, fs_index::Slot& sl) {
   switch (pl.path) {
     case FS_PATH_ROWS:
       // (the whole-search timing of the synchronous call keeps its own end marker)
-      FS_TRY(fs_launch_scan_rows(ix, c, pl.waves, pl.blocks, rcap32, d_rows, wire, pl.caprow, sl.h_status, s,
+      FS_TRY(fs_launch_scan_rows(ix, c, pl.waves, pl.blocks, rcap32, d_rows, wire, pl.caprow, pl.ids16, sl.h_status, s,
                                  e0, e1, count_out, whole || ix->prof.on ? nullptr : sl.ev_end, &end_attached));
       if (ix->prof.on) fs_prof_mark(ix, s, ix->n_lanes > 1 ? "k_scan_rows+k_compact" : fs_plan_kernel_name(ix, pl));
       break;

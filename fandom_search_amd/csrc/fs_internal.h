@@ -125,6 +125,8 @@ struct GramIndexDev {
 
 struct CorpusDev {
   const uint32_t* tok;       // [n_tok + pad] vector ids
+  const uint16_t* tok16;     // [n_tok + pad] the same ids as 16-bit words (padded and zeroed alike), or nullptr:
+                             // an id of 2^16 or more, or an out-of-vocabulary id (k_scan_rows' id stream only)
   const uint32_t* str;       // [n_tok] string ids or nullptr (== vector ids)
   const uint64_t* work_off;  // [n_works + 1]
   const uint2* blk_work;     // [ceil(n_tok / 256)] {work of token 256*i, end of that work}
@@ -177,6 +179,7 @@ struct fs_switches {
   int scan_capw = 0;              // FS_SCAN_CAPW: records per wave range to start with (tests)
   bool scan_rows = true;          // FS_SCAN_ROWS=0: separate scan and post-scan kernels
   bool scan_sub = true;           // FS_SCAN_SUB=0: k_scan_rows tests the full n-gram (Bloom) instead of K-gram runs
+  bool scan_ids16 = true;         // FS_SCAN_IDS16=0: k_scan_rows streams the 32-bit ids also where the corpus has a 16-bit copy
   int diag = 0;                   // FS_DIAG bits: 1 k_scan_rows without its rounds (results invalid), 2 in-kernel
                                   // timeline stamps (fs_debug_stamps), 16 equal shares per wave, bits 8..: flush threshold
   int wait_spins = -1;            // FS_WAIT_SPINS: polls before finish_rows gives up (tests: 0)
@@ -248,6 +251,7 @@ struct fs_plan {
   uint32_t n_bm = 0;         // sub-tiles of 64 * tpl tokens
   uint32_t waves = 0, blocks = 0;   // ROWS: waves per workgroup, workgroups
   int sub_k = 0;             // ROWS: K of the K-gram runs the kernel tests (0: the Bloom test of the n-gram)
+  bool ids16 = false;        // ROWS: the scan streams the corpus' 16-bit copy of the ids, two pairs of sub-tiles in flight
   // capacities to start with
   uint32_t caprow = 0;       // ROWS: staged records per wave range
   uint32_t capw = 0;         // DIRECT: candidate records per wave range
@@ -405,7 +409,7 @@ struct fs_index {
 };
 
 // Two kinds of member.  Batch data -- the sizes and flags of the works, the host work offsets,
-// d_tok, d_str, d_work_off, d_blk_work, d_blk4, d_check, the fan string table d_chars / d_coff /
+// d_tok, d_tok16, d_str, d_work_off, d_blk_work, d_blk4, d_check, the fan string table d_chars / d_coff /
 // n_str, the copy stream and its event -- belong to the corpus that uploads them.  Index-derived
 // data -- d_levtab, d_gbest, d_strrec, d_ctab, d_gramtab_*, d_ctok, d_selflev and their *_ready
 // flags -- are made for one index.  A view (fs_corpus_view) owns only the second kind: its batch
@@ -419,6 +423,8 @@ struct fs_corpus {
   bool has_oov = false;
   bool has_str = false;
   DBuf<uint32_t> d_tok, d_str, d_chars, d_levtab, d_blk_work, d_blk4, d_check;
+  DBuf<uint16_t> d_tok16;              // the vector ids as 16-bit words, written by the upload's check (k_corpus_check)
+  bool tok16_ok = false;               // ... and every id fits: below 2^16, none out of vocabulary
   hipStream_t copy_stream = nullptr;   // uploads run here, beside the search stream
   hipEvent_t ev_ready = nullptr;
   uint32_t* h_check = nullptr;         // pinned: {max table id + 1, any OOV, max string id + 1}
@@ -529,7 +535,7 @@ int fs_launch_scan_near(const fs_index* ix, const fs_corpus* c, uint64_t* qbm, u
                         uint32_t n_bm_words, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                         fs_scan_extra* ex);
 int fs_launch_corpus_check(const uint32_t* tok, const uint32_t* str, uint32_t n_tok,
-                           uint32_t* check, hipStream_t s);
+                           uint32_t* check, uint16_t* tok16, hipStream_t s);
 int fs_launch_histogram(const uint32_t* d_orig, const double* d_comb, const fs_row* d_rows,
                         uint64_t n_rows, uint64_t n_script, const double* d_thr, uint32_t n_thr,
                         uint32_t* d_counts, hipStream_t s);
@@ -562,7 +568,7 @@ uint32_t fs_scan_rows_shape(const fs_index* ix, const fs_corpus* c, uint32_t* bl
 // what a k_scan_rows launch holds in LDS beside its per-wave state: log2 words of its filter, bytes of seeds (0: read from memory)
 void fs_scan_rows_lds(const fs_index* ix, int* filter_log2_words, uint32_t* seeds_bytes);
 int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blocks, uint32_t rcap, fs_row* d_rows,
-                        int wire, uint32_t caprow, fs_status* host_st, hipStream_t s,
+                        int wire, uint32_t caprow, bool ids16, fs_status* host_st, hipStream_t s,
                         hipEvent_t e0, hipEvent_t e1, uint64_t* count_out, hipEvent_t done = nullptr,
                         bool* done_attached = nullptr);
 

@@ -24,6 +24,9 @@ fs_plan fs_plan_search(const fs_index* ix, const fs_corpus* c, int rows_mode, co
     p.path = FS_PATH_ROWS;
     p.sub_k = sw.scan_sub && ix->d_sfilter.p ? fs_sub_k(n) : 0;
     p.tpl = 8;
+    // the 16-bit copy of the ids where the batch has one (every id below 2^16) and no string ids
+    // of its own (that instance keeps the 32-bit stream)
+    p.ids16 = sw.scan_ids16 && c->tok16_ok && c->d_tok16.p && !c->has_str;
     const uint32_t ranges = p.blocks * p.waves;
     const uint32_t dflt = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(128, T / ranges / 16), 1u << 20);
     p.caprow = std::max<uint32_t>(dflt, ln.caprow_hint);

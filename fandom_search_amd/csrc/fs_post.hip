@@ -756,13 +756,17 @@ __global__ void k_blk_work(const uint64_t* __restrict__ work_off, uint32_t n_wor
 }
 
 // validation of an uploaded batch: largest embedding row id + 1, "any OOV id",
-// largest string id + 1 (string id == vector id when str is null)
+// largest string id + 1 (string id == vector id when str is null).  The pass reads every id
+// anyway, so it also writes them as 16-bit words (tok16: k_scan_rows' id stream; whether they
+// fit is what the host reads off the check: largest id + 1 <= 2^16 and no OOV id)
 __global__ __launch_bounds__(256) void k_corpus_check(const uint32_t* __restrict__ tok,
                                                       const uint32_t* __restrict__ str,
-                                                      uint32_t n_tok, uint32_t* __restrict__ check) {
+                                                      uint32_t n_tok, uint32_t* __restrict__ check,
+                                                      uint16_t* __restrict__ tok16) {
   uint32_t max_row = 0, oov = 0, max_str = 0;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_tok; i += gridDim.x * blockDim.x) {
     const uint32_t id = tok[i];
+    if (tok16) tok16[i] = (uint16_t)id;
     if (id & FS_OOV_FLAG) oov = 1; else max_row = max(max_row, id + 1);
     const uint32_t sid = str ? str[i] : id;
     if (str || !(id & FS_OOV_FLAG)) max_str = max(max_str, sid + 1);
@@ -788,11 +792,11 @@ __global__ __launch_bounds__(256) void k_corpus_check(const uint32_t* __restrict
 }  // namespace
 
 int fs_launch_corpus_check(const uint32_t* tok, const uint32_t* str, uint32_t n_tok,
-                           uint32_t* check, hipStream_t s) {
+                           uint32_t* check, uint16_t* tok16, hipStream_t s) {
   if (!n_tok) return FS_OK;
   uint32_t blocks = (n_tok + 256 * 16 - 1) / (256 * 16);
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(k_corpus_check, dim3(blocks), dim3(256), 0, s, tok, str, n_tok, check);
+  hipLaunchKernelGGL(k_corpus_check, dim3(blocks), dim3(256), 0, s, tok, str, n_tok, check, tok16);
   FS_HIP(hipGetLastError());
   return FS_OK;
 }

@@ -33,6 +33,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -780,7 +781,11 @@ struct alignas(16) FusedLds {         // per wave
 
 // (the instance that leaves the hand-off to k_compact runs beside other searches' kernels:
 // five waves per SIMD -- 96 registers -- leave their waves a slot where four of 121 do not)
-template <int N, int K, bool NT, bool LW14, bool STR = false, bool INL = true>
+// I16: the ids come from the corpus' 16-bit copy (CorpusDev::tok16, every vector id below 2^16).  A
+// pair is then 12 landing registers instead of 24, and the wave keeps TWO pairs in flight in the
+// registers one pair takes otherwise: twice the tokens under way per wave at the same register
+// budget, half the bytes.  The premixed ids, and so everything behind them, are the same.
+template <int N, int K, bool NT, bool LW14, bool STR = false, bool INL = true, bool I16 = false>
 __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, GramIndexDev g,
                                                     uint32_t n_sub, fsdev::RangeOut out,
                                                     fsdev::RowSync sy, fsdev::RowFinal fin,
@@ -789,6 +794,7 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
                                                     StrFast strf, uint4 shares) {
   using namespace fsdev;
   static_assert(N >= 2 && N <= 8, "halo must fit in the next lane's eight tokens");
+  static_assert(!(I16 && (STR || NT)), "the 16-bit stream: vector ids only, plain loads");
   static_assert(kRecQueue >= 192, "a pair of sub-tiles adds up to 128 records to a queue of up to 63");
   // FS_DIAG & 2: twenty words per wave range {entry, filter in LDS, scan done, rounds done,
   // finished, rounds, flushes, records, six phase sums of the rounds (RoundClock), three stamps
@@ -857,28 +863,39 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
 
   // Sub-tiles go in pairs: per lane its eight ids of sub-tile A (a*), of sub-tile B (b*)
   // and the first eight ids behind B (h*: lane 63's halo in B; A's halo is lane 0's b*).
+  // (I16: eight ids are one 16-byte register, two to a dword)
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-  struct Pair { v4u a0, a1, b0, b1, h0, h1; };
+  struct Pair32 { v4u a0, a1, b0, b1, h0, h1; };
+  struct Pair16 { v4u a, b, h; };
+  using Pair = typename std::conditional<I16, Pair16, Pair32>::type;
   auto request = [&](uint32_t sub) {
     Pair r;
-    const v4u* p = reinterpret_cast<const v4u*>(tok + sub * SUB + 8 * lane);
-    if constexpr (NT) {
-      r.a0 = __builtin_nontemporal_load(&p[0]);
-      r.a1 = __builtin_nontemporal_load(&p[1]);
-      r.b0 = __builtin_nontemporal_load(&p[SUB / 4]);
-      r.b1 = __builtin_nontemporal_load(&p[SUB / 4 + 1]);
+    if constexpr (I16) {
+      const uint16_t* __restrict__ t16 = c.tok16;
+      const v4u* p = reinterpret_cast<const v4u*>(t16 + sub * SUB + 8 * lane);
+      r.a = p[0]; r.b = p[SUB / 8];
+      r.h = *reinterpret_cast<const v4u*>(t16 + sub * SUB + 2 * SUB);            // the buffer is padded
     } else {
-      r.a0 = p[0]; r.a1 = p[1]; r.b0 = p[SUB / 4]; r.b1 = p[SUB / 4 + 1];
+      const v4u* p = reinterpret_cast<const v4u*>(tok + sub * SUB + 8 * lane);
+      if constexpr (NT) {
+        r.a0 = __builtin_nontemporal_load(&p[0]);
+        r.a1 = __builtin_nontemporal_load(&p[1]);
+        r.b0 = __builtin_nontemporal_load(&p[SUB / 4]);
+        r.b1 = __builtin_nontemporal_load(&p[SUB / 4 + 1]);
+      } else {
+        r.a0 = p[0]; r.a1 = p[1]; r.b0 = p[SUB / 4]; r.b1 = p[SUB / 4 + 1];
+      }
+      const v4u* hp = reinterpret_cast<const v4u*>(tok + sub * SUB + 2 * SUB);   // the buffer is padded
+      r.h0 = hp[0]; r.h1 = hp[1];
     }
-    const v4u* hp = reinterpret_cast<const v4u*>(tok + sub * SUB + 2 * SUB);   // the buffer is padded
-    r.h0 = hp[0]; r.h1 = hp[1];
     return r;
   };
   // the point where a pair's ids are needed: whole 16-byte registers, so the compiler
   // does not copy single ids out of a request early (it waits for the data wherever it
   // puts such a copy)
   auto arrive = [&](Pair v) {
-    asm volatile("" : "+v"(v.a0), "+v"(v.a1), "+v"(v.b0), "+v"(v.b1), "+v"(v.h0), "+v"(v.h1));
+    if constexpr (I16) asm volatile("" : "+v"(v.a), "+v"(v.b), "+v"(v.h));
+    else asm volatile("" : "+v"(v.a0), "+v"(v.a1), "+v"(v.b0), "+v"(v.b1), "+v"(v.h0), "+v"(v.h1));
     return v;
   };
   // Prologue: seeds and filter into LDS through registers, four 16-byte pieces per thread
@@ -951,6 +968,29 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
       m.v[4] = fs_premix(hi.x); m.v[5] = fs_premix(hi.y); m.v[6] = fs_premix(hi.z); m.v[7] = fs_premix(hi.w);
       asm volatile("" : "+v"(m.v[0]), "+v"(m.v[1]), "+v"(m.v[2]), "+v"(m.v[3]),
                         "+v"(m.v[4]), "+v"(m.v[5]), "+v"(m.v[6]), "+v"(m.v[7]));
+      return m;
+    };
+    // I16: fs_premix is a 24-bit multiply, and an SDWA word select on its operand takes the id out
+    // of its dword: one instruction per id, as with 32-bit ids (the multiplier in a register: an
+    // SDWA operand cannot be a literal)
+    uint32_t mul24 = FS_TOKEN_MUL24;
+    if constexpr (I16) asm volatile("" : "+v"(mul24));
+    auto premix_lo = [&](uint32_t two) {
+      uint32_t r;
+      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD"
+          : "=v"(r) : "v"(two), "v"(mul24));
+      return r;
+    };
+    auto premix_hi = [&](uint32_t two) {
+      uint32_t r;
+      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD"
+          : "=v"(r) : "v"(two), "v"(mul24));
+      return r;
+    };
+    auto premix8h = [&](const v4u& x) {
+      M8 m;
+      m.v[0] = premix_lo(x.x); m.v[1] = premix_hi(x.x); m.v[2] = premix_lo(x.y); m.v[3] = premix_hi(x.y);
+      m.v[4] = premix_lo(x.z); m.v[5] = premix_hi(x.z); m.v[6] = premix_lo(x.w); m.v[7] = premix_hi(x.w);
       return m;
     };
     // one sub-tile: m = the lane's own premixed ids, halo[h] = premixed id h of the lane behind
@@ -1064,11 +1104,28 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
     // rounds; a wave that has to empty its queue in mid-range does so by itself)
     const uint32_t flush_req = (diag >> 12) ? (diag >> 12) : coop ? kRecQueue - 128 : kRecFlush;
     const uint32_t flush_at = flush_req < kRecQueue - 128 ? flush_req : kRecQueue - 128;
+    // (I16: two pairs are requested ahead -- the pair after next when this one has arrived; the
+    // last two steps read the range's current sub-tiles again)
     Pair nx = request(s0);
+    Pair nx2 = nx;
+    if constexpr (I16) {
+      // (the first pair's three loads go out before the second's, as they do in the loop: the
+      // wait for a pair is then "all but the last three loads" on every path into the loop --
+      // with the two requests interleaved it came out as "all but one", one pair in flight)
+      asm volatile("" ::: "memory");
+      nx2 = request(s0 + 2 < s1 ? s0 + 2 : s0);
+    }
     for (uint32_t j = s0; j < s1; j += 2) {
       const Pair v = arrive(nx);
-      nx = request(j + 2 < s1 ? j + 2 : j);
-      const M8 ma = premix8(v.a0, v.a1), mb = premix8(v.b0, v.b1);
+      M8 ma, mb;
+      if constexpr (I16) {
+        nx = nx2;
+        nx2 = request(j + 4 < s1 ? j + 4 : j);
+        ma = premix8h(v.a); mb = premix8h(v.b);
+      } else {
+        nx = request(j + 2 < s1 ? j + 2 : j);
+        ma = premix8(v.a0, v.a1); mb = premix8(v.b0, v.b1);
+      }
       uint32_t halo[8];
       // A's halo: the first ids of the lane behind, lane 63: lane 0's first ids of B -- one
       // DPP rotation of the wave per id (no LDS), lane 0 offering its B ids
@@ -1081,12 +1138,17 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
         // B's halo: lane 63 takes the ids behind B (the same in every lane): a DPP shift of
         // the wave, the lane without a source keeps `old`
         auto hv = [&](int h) {
-          return h == 0 ? v.h0.x : h == 1 ? v.h0.y : h == 2 ? v.h0.z : h == 3 ? v.h0.w
-               : h == 4 ? v.h1.x : h == 5 ? v.h1.y : h == 6 ? v.h1.z : v.h1.w;
+          if constexpr (I16) {
+            const uint32_t two = h < 2 ? v.h.x : h < 4 ? v.h.y : h < 6 ? v.h.z : v.h.w;
+            return h & 1 ? premix_hi(two) : premix_lo(two);
+          } else {
+            return fs_premix(h == 0 ? v.h0.x : h == 1 ? v.h0.y : h == 2 ? v.h0.z : h == 3 ? v.h0.w
+                           : h == 4 ? v.h1.x : h == 5 ? v.h1.y : h == 6 ? v.h1.z : v.h1.w);
+          }
         };
 #pragma unroll
         for (int h = 0; h < (int)HALO; ++h)
-          halo[h] = (uint32_t)__builtin_amdgcn_update_dpp((int)fs_premix(hv(h)), (int)mb.v[h], 0x130, 0xF, 0xF, false);   // wave_shl:1
+          halo[h] = (uint32_t)__builtin_amdgcn_update_dpp((int)hv(h), (int)mb.v[h], 0x130, 0xF, 0xF, false);   // wave_shl:1
         scan(mb, halo, j + 1);
       }
       // ONE place where the queue is worked off (the rounds are a lot of code: a second copy
@@ -1329,7 +1391,7 @@ static int rows_filter_log2(const fs_index* ix) {
 template <int N>
 int launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t n_sub, uint32_t waves, uint32_t blocks,
                      const fsdev::RangeOut& out, const fsdev::RowSync& sy,
-                     const fsdev::RowFinal& fin, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+                     const fsdev::RowFinal& fin, bool ids16, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
   unsigned long long* dbg = nullptr;
   if (ix->sw.diag & 2) {               // timeline stamps, read back by fs_debug_stamps
     FS_TRY(ix->cur->w_dbg.reserve((size_t)blocks * waves * 20));
@@ -1354,11 +1416,18 @@ int launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t n_sub, uint32_t waves,
   };
   (void)nt;
   auto kern = k_scan_rows<N, 0, false, false, false, true>;
-  if (!c->has_str) {
+  if (!c->has_str && !ids16) {
     if (inl) kern = lw14 ? pick(k_scan_rows<N, 0, false, true, false, true>, k_scan_rows<N, K, false, true, false, true>)
                          : pick(k_scan_rows<N, 0, false, false, false, true>, k_scan_rows<N, K, false, false, false, true>);
     else kern = lw14 ? pick(k_scan_rows<N, 0, false, true, false, false>, k_scan_rows<N, K, false, true, false, false>)
                      : pick(k_scan_rows<N, 0, false, false, false, false>, k_scan_rows<N, K, false, false, false, false>);
+  }
+  if (ids16) {                         // the 16-bit id stream (fs_plan::ids16): the same instances over CorpusDev::tok16
+    if (c->has_str || !c->dev().tok16) { fs_set_error("k_scan_rows: the 16-bit id stream without a 16-bit copy"); return FS_E_DEVICE; }
+    if (inl) kern = lw14 ? pick(k_scan_rows<N, 0, false, true, false, true, true>, k_scan_rows<N, K, false, true, false, true, true>)
+                         : pick(k_scan_rows<N, 0, false, false, false, true, true>, k_scan_rows<N, K, false, false, false, true, true>);
+    else kern = lw14 ? pick(k_scan_rows<N, 0, false, true, false, false, true>, k_scan_rows<N, K, false, true, false, false, true>)
+                     : pick(k_scan_rows<N, 0, false, false, false, false, true>, k_scan_rows<N, K, false, false, false, false, true>);
   }
   StrFast strf{nullptr, nullptr, 0, 0, nullptr};
   if (c->has_str) {                    // (fs_scan_rows_shape has checked that the path applies)
@@ -1440,7 +1509,7 @@ void fs_scan_rows_lds(const fs_index* ix, int* filter_log2_words, uint32_t* seed
 
 // tokens -> output records: one launch of fs_scan_rows_blocks() workgroups of `waves` wave ranges
 int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blocks, uint32_t rcap, fs_row* d_rows,
-                        int wire, uint32_t caprow, fs_status* host_st, hipStream_t s,
+                        int wire, uint32_t caprow, bool ids16, fs_status* host_st, hipStream_t s,
                         hipEvent_t e0, hipEvent_t e1, uint64_t* count_out, hipEvent_t done,
                         bool* done_attached) {
   fs_index::Lane& ln = *ix->cur;
@@ -1466,13 +1535,13 @@ int fs_launch_scan_rows(fs_index* ix, fs_corpus* c, uint32_t waves, uint32_t blo
   const fsdev::RowFinal fin{reinterpret_cast<uint8_t*>(d_rows), rcap, ln.d_status.p, host_st, count_out, true,
                             (ix->sw.diag & 512) != 0};
   switch (ix->cfg.window_size) {
-    case 2: FS_TRY(launch_scan_rows<2>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 3: FS_TRY(launch_scan_rows<3>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 4: FS_TRY(launch_scan_rows<4>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 5: FS_TRY(launch_scan_rows<5>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 6: FS_TRY(launch_scan_rows<6>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 7: FS_TRY(launch_scan_rows<7>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
-    case 8: FS_TRY(launch_scan_rows<8>(ix, c, n_sub, waves, blocks, out, sy, fin, s, e0, e1)); break;
+    case 2: FS_TRY(launch_scan_rows<2>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 3: FS_TRY(launch_scan_rows<3>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 4: FS_TRY(launch_scan_rows<4>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 5: FS_TRY(launch_scan_rows<5>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 6: FS_TRY(launch_scan_rows<6>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 7: FS_TRY(launch_scan_rows<7>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
+    case 8: FS_TRY(launch_scan_rows<8>(ix, c, n_sub, waves, blocks, out, sy, fin, ids16, s, e0, e1)); break;
     default: fs_set_error("k_scan_rows covers n = 2..8"); return FS_E_UNSUPPORTED;
   }
   if (sy.rinfo) {

@@ -364,6 +364,14 @@ class ScriptIndex(object):
         _lib.check(_lib.load().fs_index_scan_shape(self._h, corpus._h, C.byref(out)), "fs_index_scan_shape")
         return out.as_dict()
 
+    def scan_ids16(self, corpus):
+        """Diagnostics: whether a search of `corpus` streams the 16-bit copy of its ids through
+        k_scan_rows (fs_scan_shape.ids16: every vector id below 2^16, no string ids of the batch's
+        own, FS_SCAN_IDS16 not 0) instead of the 32-bit ids."""
+        out = abi.FsScanShape()
+        _lib.check(_lib.load().fs_index_scan_shape(self._h, corpus._h, C.byref(out)), "fs_index_scan_shape")
+        return bool(out.ids16)
+
     def stream_floor(self, corpus, reps=20):
         """Diagnostics: ms of a kernel that only reads `corpus`' ids in k_scan_rows' launch
         shape (fs_stream_floor)."""

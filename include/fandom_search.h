@@ -1471,7 +1471,11 @@ typedef struct fs_scan_shape {
   uint32_t host_wire8;         /* 1: an FS_ROWS_HOST search brings 8-byte wire records over
                                   and expands them on the host (exact pipeline, scripts below
                                   2^18 tokens); 0: it does not                                 */
-  uint32_t reserved[3];        /* 0                                                            */
+  uint32_t ids16;              /* 1: k_scan_rows streams the corpus' 16-bit copy of the ids
+                                  (every vector id of the batch below 2^16, no string ids of its
+                                  own, FS_SCAN_IDS16 not 0), two pairs of sub-tiles in flight
+                                  per wave; 0: the 32-bit ids                                  */
+  uint32_t reserved[2];        /* 0                                                            */
 } fs_scan_shape;               /* 48 bytes                                                     */
 int fs_index_scan_shape(fs_index* ix, fs_corpus* c, fs_scan_shape* out);
 
