@@ -30,6 +30,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_lines", "fs_lines_rows", "fs_lines_times",
            "fs_fragments", "fs_fragments_rows", "fs_fragments_times",
            "fs_digest", "fs_digest_rows", "fs_digest_times",
+           "fs_intervals", "fs_intervals_rows", "fs_intervals_times",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
            "fs_sources", "fs_sources_times",
            "fs_matrix", "fs_matrix_rows", "fs_matrix_times",
@@ -49,7 +50,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "transitions", "sources", "matrix",
+TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "transitions", "sources", "matrix",
          "clusters", "groups")
 
 
@@ -234,6 +235,14 @@ def load():
     L.fs_digest_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                  C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    L.fs_intervals.restype = C.c_int
+    L.fs_intervals.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                               u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                               C.c_uint32, C.c_void_p, C.c_void_p]
+    L.fs_intervals_rows.restype = C.c_int
+    L.fs_intervals_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                    C.c_uint32, C.c_void_p, C.c_void_p]
     L.fs_transitions.restype = C.c_int
     L.fs_transitions.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                  u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

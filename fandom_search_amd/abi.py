@@ -204,6 +204,25 @@ FS_DIGEST_MAX_BYTES = 1 << 30
 # fs_digest_times: three passes and their total in ms, then two counts
 DIGEST_MS_NAMES = ("coverage", "rounds", "works", "total", "rounds_enqueued", "tiles_read")
 
+# fs_interval_unit: 64 bytes; fs_interval_replicate: 16 bytes
+INTERVAL_UNIT_DTYPE = np.dtype([("works", np.uint32), ("works_low", np.uint32),
+                                ("works_median", np.uint32), ("works_high", np.uint32),
+                                ("ppm", np.uint32), ("ppm_low", np.uint32),
+                                ("ppm_median", np.uint32), ("ppm_high", np.uint32),
+                                ("rank", np.uint32), ("next", np.uint32), ("ahead", np.uint32),
+                                ("tied", np.uint32), ("behind", np.uint32),
+                                ("reserved", np.uint32), ("mean_milli", np.uint64)])
+assert INTERVAL_UNIT_DTYPE.itemsize == 64
+INTERVAL_REPLICATE_DTYPE = np.dtype([("resampled_works", np.uint32),
+                                     ("resampled_active", np.uint32),
+                                     ("units_quoted", np.uint32), ("reserved", np.uint32)])
+assert INTERVAL_REPLICATE_DTYPE.itemsize == 16
+FS_INTERVALS_MAX_REPLICATES = 4096
+FS_INTERVALS_MAX_WORKS = 1 << 28
+FS_INTERVALS_MAX_BYTES = 1 << 30
+INTERVALS_MS_NAMES = ("incidence", "multiplicities", "product", "statistics", "neighbours",
+                      "total")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

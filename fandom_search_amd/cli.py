@@ -22,7 +22,8 @@ with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignmen
 completely each is quoted (fandom_search_amd/lines.py), and `fragments`, which lists the
 phrases the works quote word for word, each with the works quoting it in full
 (fandom_search_amd/fragments.py), and `digest`, which picks the fewest works that together show
-everything the works quote (fandom_search_amd/digest.py).  The
+everything the works quote (fandom_search_amd/digest.py), and `intervals`, which resamples the
+works to say how sure the works-per-stretch counts are (fandom_search_amd/intervals.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -414,10 +415,10 @@ def full_parser():
 
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
-    behind it the commands added since (`lines`, `fragments`, `digest`)."""
+    behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -484,6 +485,34 @@ def ao3_parser():
                               'script words any work quotes, 1 to 100, default 100'),
                     _own('--min-gain', default=1, type=int,
                          help='stop when no work adds this many new words, default 1')])
+
+    _analysis(subparsers, 'intervals',
+              'says how sure the works-per-stretch counts are: a Poisson bootstrap '
+              'over the fan works, per quoted region, script word, scene or character '
+              'the interval and median of its works over the replicates, its rank, and '
+              'in how many replicates it stays ahead of the next unit; per replicate the '
+              'works drawn',
+              'prefix of the two csv files, PREFIX-intervals.csv and '
+              'PREFIX-intervals-replicates.csv (default: the input name without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0,
+                '--min-words and --min-works must be at least 1, --max-gap at least 0'),
+               (lambda a: not 1 <= a.replicates <= 4096, '--replicates must be from 1 to 4096'),
+               (lambda a: not 50 <= a.level <= 99, '--level must be from 50 to 99'),
+               (lambda a: not 0 <= a.seed < 1 << 64, '--seed must be from 0 to 2^64 - 1')],
+              middle=[_own('--by', default='region',
+                           choices=('region', 'word', 'scene', 'character'),
+                           help='the units: the quoted regions of `quotes` (default), '
+                                'every script word inside one, the scenes or the '
+                                'characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --by region or word: fewest different works whose '
+                              'passages cover every word of a region, default 1'),
+                    _own('--replicates', default=1000, type=int,
+                         help='resamples of the works, 1 to 4096, default 1000'),
+                    _own('--seed', default=0, type=int,
+                         help='seed of the multiplicities, 0 to 2^64 - 1, default 0'),
+                    _own('--level', default=95, type=int,
+                         help='the interval as a whole percentage, 50 to 99, default 95')])
     return parser
 
 

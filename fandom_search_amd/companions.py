@@ -123,6 +123,24 @@ def units_of(labels, work, fan, orig, comb, n_works, n_script, by, min_words, ma
     return unit_of, about
 
 
+def word_units_of(labels, work, fan, orig, comb, n_works, n_script, min_words, max_gap, min_works,
+                  device):
+    """(unit_of[n_script], about) of `intervals --by word`: every script word inside a region of
+    `quotes` is a unit of its own, numbered in script order; its character, scene and text are
+    the word's own, those of a bridged word no record names unknown."""
+    words, _ = quotes.find_quotes(work, fan, orig, comb, n_works, n_script, min_words, max_gap,
+                                  min_works, device)
+    at = np.nonzero(abi.as_u32(words['region']) != abi.FS_NONE)[0]
+    unit_of = np.full(n_script, abi.FS_NONE, dtype=np.uint32)
+    unit_of[at] = np.arange(len(at), dtype=np.uint32)
+    unknown = (UNKNOWN_WORD, '', '')
+    about = []
+    for o in at.tolist():
+        word, char, scene = labels.get(o, unknown)
+        about.append((o, o, char, scene, word))
+    return unit_of, about
+
+
 def _tables(labels, names, work, fan, orig, comb, n_script, by, min_words, max_gap, min_works,
             min_both, min_share, device):
     if by not in BY:

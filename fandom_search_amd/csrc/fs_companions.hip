@@ -23,16 +23,13 @@
 // M is stored as fs_tiles.h stores the coverage matrix, [tile of 64 units][k][64] with k over
 // the 64-bit words of the active works, so tile_counts runs on it through a CoverArgs whose cov,
 // nk and n_tiles describe M.  Rows past n_units are zero and are never kept (min_both >= 1).
-#include "fs_tiles.h"
+// k_comp_units_ok and k_comp_incidence live in fs_incidence.h, which fs_intervals.hip shares.
+#include "fs_incidence.h"
 
 namespace {
 
-struct CompArgs {
-  CoverArgs r;                  // the records: heads, act, work_of, n_active (cov unused)
-  CoverArgs m;                  // M: cov, nk = ceil(n_active / 64), n_tiles and n_chunks of units,
-                                // covered = works(u)
-  const uint32_t* unit_of;      // [n_script]
-  uint32_t n_units, min_both, min_share;
+struct CompArgs : IncArgs {     // r, m, unit_of, n_units: fs_incidence.h
+  uint32_t min_both, min_share;
   uint32_t* partners;           // [m.n_tiles * 64]
   unsigned long long* best;     // [m.n_tiles * 64] both << 32 | (0xFFFFFFFF - partner)
   uint32_t* cnt;                // [m.n_tiles * 64][n_chunks] kept pairs of a row in a chunk
@@ -43,64 +40,11 @@ struct CompArgs {
   fs_companion* pairs;
 };
 
-// one lane per script word
-__global__ __launch_bounds__(kRunBlock) void k_comp_units_ok(const uint32_t* unit_of,
-                                                             uint32_t n_script, uint32_t n_units,
-                                                             uint32_t* bad_out) {
-  const uint64_t o = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  bool bad = false;
-  if (o < n_script) {
-    const uint32_t u = unit_of[o];
-    bad = u != FS_NONE && u >= n_units;
-  }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(bad_out, 1u);
-}
-
 // one lane per unit: a unit nobody quotes (no records, or no work with a passage)
 __global__ __launch_bounds__(kRunBlock) void k_comp_units_none(fs_companion_unit* units,
                                                                uint32_t n_units) {
   const uint64_t u = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   if (u < n_units) reinterpret_cast<uint4*>(units)[u] = make_uint4(0u, 0u, FS_NONE, 0u);
-}
-
-// A lane per run (after CoverJob::number found nothing: every work and word is inside, and
-// k_comp_units_ok: every unit is a row of M); the wave's kept runs are then taken in turn by
-// the whole wave.
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_comp_incidence(Src src, CompArgs a,
-                                                              const uint32_t* flag) {
-  const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63;
-  bool kept = false;
-  uint32_t o0 = 0, o1 = 0, ai = 0;
-  if (r < a.r.n_runs) {
-    const uint32_t h = a.r.heads[r], e = a.r.heads[r + 1];
-    if (e - h >= a.r.min_words) {
-      const uint4 k = src.key(h);
-      o0 = k.z;
-      o1 = src.key((uint64_t)e - 1).z;                       // o0 <= o1: a run steps forward
-      if (k.x < a.r.n_works && flag[k.x] && o1 < a.r.n_script && o0 <= o1) {
-        kept = true;
-        ai = a.r.act[k.x];
-      }
-    }
-  }
-  uint64_t todo = __ballot(kept);
-  while (todo) {
-    const int from = __builtin_ctzll(todo);
-    todo &= todo - 1;
-    const uint32_t b0 = (uint32_t)__shfl((int)o0, from), b1 = (uint32_t)__shfl((int)o1, from);
-    const uint32_t bi = (uint32_t)__shfl((int)ai, from);
-    if (bi >= a.r.n_active) continue;                        // (never: act numbers the flagged works)
-    const unsigned long long bit = 1ull << (bi & 63);
-    const size_t k = bi >> 6;
-    for (uint64_t o = (uint64_t)b0 + lane; o <= b1; o += 64) {
-      const uint32_t u = a.unit_of[o];
-      if (u >= a.n_units) continue;                          // none
-      if (o != b0 && a.unit_of[o - 1] == u) continue;        // the lane at the unit's first word did it
-      atomicOr(&a.m.cov[((size_t)(u / kTile) * a.m.nk + k) * kTile + u % kTile], bit);
-    }
-  }
 }
 
 __device__ inline bool comp_keep(const CompArgs& a, uint32_t both, uint32_t wa, uint32_t wb) {

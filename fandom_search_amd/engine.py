@@ -682,6 +682,26 @@ class ScriptIndex(object):
                          out_ptrs, "pick or work buffer too small")
         return tuple(got) + (int(total.value),)
 
+    def intervals_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
+                         max_gap=0, replicates=1000, seed=0, level=95, out_ptrs=None):
+        """`intervals` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident unit map of the script's words (fs_intervals_rows): per unit its works
+        with the bootstrap's order statistics and its standing against the next unit, per
+        replicate its totals.  Without `out_ptrs`: (abi.INTERVAL_UNIT_DTYPE[n_units],
+        abi.INTERVAL_REPLICATE_DTYPE[replicates]) on the host.  With `out_ptrs` = device
+        addresses (units, replicates): they are written and () comes back.  Buffers torch has
+        only just produced go in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_intervals_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                       C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                       int(max_gap), int(replicates), int(seed), int(level),
+                                       C.c_void_p(fixed[0]), C.c_void_p(fixed[1]))
+        return _rows_call("fs_intervals_rows", call,
+                          [(n_units, abi.INTERVAL_UNIT_DTYPE),
+                           (replicates, abi.INTERVAL_REPLICATE_DTYPE)], [], [], out_ptrs, "")
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

@@ -1047,6 +1047,99 @@ int fs_digest_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t
  * the gain pass read in them (0 unless FS_DIGEST_COUNT=1).  tools/digest_bench.py. */
 int fs_digest_times(double* ms);
 
+/* `ao3.py intervals`: how sure the works-per-unit counts are, a Poisson bootstrap over the fan
+ * works.  Records, passages, active works (N of them, numbered in work order), the coverage
+ * C_w, unit_of[n_script], M_u and works(u) as for fs_companions.  n_works is every work of the
+ * file, active or not.  For replicate b (0-based, b < replicates) and work w (its work number)
+ *     z = ((b << 32) | w) + seed * 0x9E3779B97F4A7C15                  (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31);  h = z >> 32
+ *     m(b, w) = the number of k in 0..12 with h >= T[k],
+ *     T[k] = floor(2^32 * sum_{i <= k} e^-1 / i!), the Poisson(1) distribution function:
+ *     1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777,
+ *     4294923276, 4294962463, 4294966817, 4294967252, 4294967292, 4294967295
+ * so a multiplicity is at most 13 and a pure function of (seed, b, w).  Per replicate:
+ * N_b = the sum of m(b, w) over all n_works works, A_b the same over the active works,
+ * c_b(u) = the sum of m(b, w) over M_u, ppm_b(u) = c_b(u) * 1000000 / max(1, N_b) (64 bits,
+ * rounded down), Q_b = the units with c_b(u) > 0.  Per unit, with s the c_b(u) in ascending
+ * order and t = replicates * (100 - level) / 200 (rounded down): low = s[t], high =
+ * s[replicates - 1 - t], median = s[(replicates - 1) / 2]; the same three over the ppm_b(u),
+ * sorted on their own.  The observed order is works(u) descending, then u ascending; next is the
+ * unit behind u in it.  Every output is an integer. */
+typedef struct fs_interval_unit {
+  uint32_t works;            /* |M_u|                                                     */
+  uint32_t works_low;        /* s[t]                                                      */
+  uint32_t works_median;     /* s[(replicates - 1) / 2]                                   */
+  uint32_t works_high;       /* s[replicates - 1 - t]                                     */
+  uint32_t ppm;              /* works * 1000000 / max(1, n_works)                         */
+  uint32_t ppm_low;          /* the three order statistics of ppm_b(u)                    */
+  uint32_t ppm_median;
+  uint32_t ppm_high;
+  uint32_t rank;             /* 1 + the units with more works                             */
+  uint32_t next;             /* the unit behind this one in the observed order;
+                                0xFFFFFFFF for the last, whose three counts are 0         */
+  uint32_t ahead;            /* replicates with c_b(u) >  c_b(next)                       */
+  uint32_t tied;             /*                        ==                                 */
+  uint32_t behind;           /*                        <       ; the three sum to
+                                replicates                                                */
+  uint32_t reserved;         /* 0                                                         */
+  uint64_t mean_milli;       /* (the sum of c_b(u) over b) * 1000 / replicates            */
+} fs_interval_unit;          /* 64 bytes                                                  */
+
+typedef struct fs_interval_replicate {
+  uint32_t resampled_works;  /* N_b                                                       */
+  uint32_t resampled_active; /* A_b                                                       */
+  uint32_t units_quoted;     /* Q_b                                                       */
+  uint32_t reserved;         /* 0                                                         */
+} fs_interval_replicate;     /* 16 bytes                                                  */
+
+#define FS_INTERVALS_MAX_REPLICATES 4096u
+#define FS_INTERVALS_MAX_WORKS (1u << 28)   /* n_works up to this: 13 * n_works fits 32 bits */
+/* Counted: the incidence matrix (ceil(n_units / 64) * 64 * ceil(N / 64) * 8 bytes), the
+ * multiplicity bytes (replicates padded to a multiple of 16, times N padded to a multiple of
+ * 64) and the counts c_b(u) (4 bytes per padded unit and padded replicate).  Their sum may be
+ * up to this. */
+#define FS_INTERVALS_MAX_BYTES (1u << 30)
+
+/* Host columns and the host unit map in; units[n_units] and reps[replicates] out, on HIP device
+ * `device`.  Both entry points: FS_E_INVALID for null arguments, min_words == 0, replicates
+ * outside 1..FS_INTERVALS_MAX_REPLICATES, level outside 50..99, records out of (work, fan_ix)
+ * order, a work >= n_works, an orig_ix >= n_script or a unit_of entry that is neither below
+ * n_units nor 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT,
+ * n_works > FS_INTERVALS_MAX_WORKS or tables above FS_INTERVALS_MAX_BYTES (the message states
+ * the three).  Without an active work every unit has works 0, rank 1, next = the unit behind it
+ * and tied = replicates.
+ * The passes are separate launches: incidence (fs_companions' own), multiplicities, the product
+ * counts[u][b] = sum over w of m(b, w) * M[u][w] on the matrix cores
+ * (v_mfma_i32_16x16x64_i8: a 64-bit word of M is one K = 64 step), the order statistics (a
+ * workgroup per unit sorts its counts in LDS), and the neighbours (the host sorts works(u)
+ * between the two).  Switches of the environment, read once per call; the output is the same
+ * wherever they stand:
+ *   FS_INTERVALS_MFMA       1 (default): the product by MFMA; 0: a plain integer kernel, a lane
+ *                           per (unit, replicate) that walks the set bits of the unit's row
+ *   FS_INTERVALS_KSPLIT     the workgroups that share the words of a product tile and add
+ *                           their parts; default: 1 from 512 product workgroups on, more
+ *                           below, at least 8 words each
+ *   FS_INTERVALS_MAX_BYTES  a lower bound than the macro's, for tests */
+int fs_intervals(int device, const uint32_t* work, const uint32_t* fan_ix,
+                 const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                 const uint32_t* unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+                 uint32_t replicates, uint64_t seed, uint32_t level, fs_interval_unit* units,
+                 fs_interval_replicate* reps);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (16-byte aligned), on the index's device
+ * and stream; returns when they are written. */
+int fs_intervals_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                      const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                      uint32_t max_gap, uint32_t replicates, uint64_t seed, uint32_t level,
+                      fs_interval_unit* d_units, fs_interval_replicate* d_reps);
+/* HIP-event milliseconds of the last fs_intervals / fs_intervals_rows call on this thread:
+ * incidence (with the row popcounts), multiplicities (with N_b and A_b), product, statistics
+ * (with Q_b), neighbours (with the host's sort of works(u)), and the total of the five; 0 for a
+ * pass that did not run.  tools/intervals_bench.py. */
+int fs_intervals_times(double* ms);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
