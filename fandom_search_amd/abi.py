@@ -223,6 +223,19 @@ FS_INTERVALS_MAX_BYTES = 1 << 30
 INTERVALS_MS_NAMES = ("incidence", "multiplicities", "product", "statistics", "neighbours",
                       "total")
 
+# fs_contrast_unit: 32 bytes; fs_contrast_perm: 16 bytes
+CONTRAST_UNIT_DTYPE = np.dtype([("a_works", np.uint32), ("b_works", np.uint32),
+                                ("ge", np.uint32), ("adj_ge", np.uint32),
+                                ("statistic", np.uint64), ("d", np.int64)])
+assert CONTRAST_UNIT_DTYPE.itemsize == 32
+CONTRAST_PERM_DTYPE = np.dtype([("max_statistic", np.uint64), ("a_active", np.uint32),
+                                ("max_unit", np.uint32)])
+assert CONTRAST_PERM_DTYPE.itemsize == 16
+FS_CONTRAST_MAX_PERMUTATIONS = 4096
+FS_CONTRAST_MAX_WORKS = 1 << 20
+FS_CONTRAST_MAX_BYTES = 1 << 30
+CONTRAST_MS_NAMES = ("incidence", "selection", "product", "sweeps", "total")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

@@ -23,7 +23,9 @@ completely each is quoted (fandom_search_amd/lines.py), and `fragments`, which l
 phrases the works quote word for word, each with the works quoting it in full
 (fandom_search_amd/fragments.py), and `digest`, which picks the fewest works that together show
 everything the works quote (fandom_search_amd/digest.py), and `intervals`, which resamples the
-works to say how sure the works-per-stretch counts are (fandom_search_amd/intervals.py).  The
+works to say how sure the works-per-stretch counts are (fandom_search_amd/intervals.py), and
+`contrast`, which says what one group of works quotes more than another and which of those
+differences survive a look at every unit at once (fandom_search_amd/contrast.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -415,10 +417,11 @@ def full_parser():
 
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
-    behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`)."""
+    behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
+    `contrast`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, contrast or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -513,6 +516,48 @@ def ao3_parser():
                          help='seed of the multiplicities, 0 to 2^64 - 1, default 0'),
                     _own('--level', default=95, type=int,
                          help='the interval as a whole percentage, 50 to 99, default 95')])
+
+    _analysis(subparsers, 'contrast',
+              'says what one group of fan works quotes more than another: two sides taken '
+              'from the metadata csv, per quoted region, script word, scene or character the '
+              'share of either side quoting it, how often a random relabelling of the works '
+              'differs as much, and how often the largest difference over all units does '
+              '(a permutation test with the max-statistic correction)',
+              'prefix of the three csv files, PREFIX-contrast.csv, PREFIX-contrast-sides.csv '
+              'and PREFIX-contrast-permutations.csv (default: the input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_quoting < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-works and --min-quoting must be at least 1, --max-gap at '
+                'least 0'),
+               (lambda a: not 1 <= a.permutations <= 4096,
+                '--permutations must be from 1 to 4096'),
+               (lambda a: not 0 <= a.seed < 1 << 64, '--seed must be from 0 to 2^64 - 1')],
+              first=[_own('meta', action='store',
+                          help='filename for the metadata csv (FILENAME, TITLE, AUTHOR, '
+                               'SUMMARY, NOTES, PUBLICATION_DATE, LANGUAGE, TAGS)'),
+                     _own('--a', action='append', required=True, metavar='KEY',
+                          help='a key of side A; may be given several times'),
+                     _own('--b', action='append', default=None, metavar='KEY',
+                          help='a key of side B; may be given several times; default: side B '
+                               'is every work that does not match --a'),
+                     _own('--by', default='year',
+                          help='what the keys are: year, month, author, language, tag or '
+                               'tag:<Category>; default year')],
+              middle=[_own('--unit', default='region',
+                           choices=('region', 'word', 'scene', 'character'),
+                           help='the units: the quoted regions of `quotes` (default), '
+                                'every script word inside one, the scenes or the '
+                                'characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --unit region or word: fewest different works whose '
+                              'passages cover every word of a region, default 1'),
+                    _own('--min-quoting', default=5, type=int,
+                         help='fewest works of both sides together quoting a unit of the '
+                              'family the adjustment covers, default 5'),
+                    _own('--permutations', default=1000, type=int,
+                         help='relabellings of the works, 1 to 4096, default 1000'),
+                    _own('--seed', default=0, type=int,
+                         help='seed of the relabellings, 0 to 2^64 - 1, default 0')])
     return parser
 
 

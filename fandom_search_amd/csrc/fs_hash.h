@@ -196,3 +196,14 @@ FS_HDC int fs_share_block_start(int n, int r) {
   // the longer runs first: 7 = 4 + 3, 9 = 5 + 4, 11 = 4 + 4 + 3
   return b == 2 ? (n + 1) / 2 : (r == 1 ? (n + 2) / 3 : (n + 2) / 3 + (n + 1) / 3);
 }
+
+// The draw of a fan work in replicate or permutation r (fs_intervals.hip, fs_contrast.hip;
+// include/fandom_search.h): the upper half of a splitmix64 step over ((r << 32) | w) + term,
+// term = seed * 0x9E3779B97F4A7C15.  A pure function of (seed, r, w).
+FS_HD uint32_t fs_work_hash(uint64_t term, uint32_t r, uint32_t w) {
+  uint64_t z = (((uint64_t)r << 32) | w) + term;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z = z ^ (z >> 31);
+  return (uint32_t)(z >> 32);
+}

@@ -68,11 +68,7 @@ struct IntArgs : IncArgs {
 
 // m(b, w): include/fandom_search.h
 __host__ __device__ inline uint32_t int_mult(uint64_t term, uint32_t b, uint32_t w) {
-  uint64_t z = (((uint64_t)b << 32) | w) + term;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  const uint32_t h = (uint32_t)(z >> 32);
+  const uint32_t h = fs_work_hash(term, b, w);
   return (h >= 1580030168u) + (h >= 3160060337u) + (h >= 3950075421u) + (h >= 4213413783u) +
          (h >= 4279248373u) + (h >= 4292415291u) + (h >= 4294609777u) + (h >= 4294923276u) +
          (h >= 4294962463u) + (h >= 4294966817u) + (h >= 4294967252u) + (h >= 4294967292u) +

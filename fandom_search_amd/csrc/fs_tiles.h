@@ -86,7 +86,8 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_cover(Src src, CoverArgs a,
 }
 
 // a workgroup of 64 lanes per tile: lane r sums row r (adjacent lanes, adjacent addresses)
-__global__ __launch_bounds__(kTile) void k_pairs_covered(CoverArgs a) {
+// (fs_contrast.hip takes its counts from the product and does not launch it)
+[[maybe_unused]] __global__ __launch_bounds__(kTile) void k_pairs_covered(CoverArgs a) {
   const unsigned long long* t = a.cov + (size_t)blockIdx.x * a.nk * kTile + threadIdx.x;
   uint32_t c = 0;
   for (uint32_t k = 0; k < a.nk; ++k) c += (uint32_t)__popcll(t[(size_t)k * kTile]);

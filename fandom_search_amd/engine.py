@@ -702,6 +702,29 @@ class ScriptIndex(object):
                           [(n_units, abi.INTERVAL_UNIT_DTYPE),
                            (replicates, abi.INTERVAL_REPLICATE_DTYPE)], [], [], out_ptrs, "")
 
+    def contrast_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, side_ptr,
+                        min_words=6, max_gap=0, min_quoting=5, permutations=1000, seed=0,
+                        key_bits=32, out_ptrs=None):
+        """`contrast` over device-resident fs_row records sorted by (work, fan_ix), a
+        device-resident unit map of the script's words and device-resident side bytes, one per
+        work: 0 out, 1 side A, 2 side B (fs_contrast_rows): per unit its works on either side,
+        its statistic and in how many relabellings it, and the largest statistic of any unit,
+        is reached; per permutation that largest statistic.  Without `out_ptrs`:
+        (abi.CONTRAST_UNIT_DTYPE[n_units], abi.CONTRAST_PERM_DTYPE[permutations]) on the host.
+        With `out_ptrs` = device addresses (units, permutations): they are written and () comes
+        back.  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_contrast_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                      C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                      int(max_gap), C.c_void_p(side_ptr), int(min_quoting),
+                                      int(permutations), int(seed), int(key_bits),
+                                      C.c_void_p(fixed[0]), C.c_void_p(fixed[1]))
+        return _rows_call("fs_contrast_rows", call,
+                          [(n_units, abi.CONTRAST_UNIT_DTYPE),
+                           (permutations, abi.CONTRAST_PERM_DTYPE)], [], [], out_ptrs, "")
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

@@ -1140,6 +1140,105 @@ int fs_intervals_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint3
  * pass that did not run.  tools/intervals_bench.py. */
 int fs_intervals_times(double* ms);
 
+/* `ao3.py contrast`: what one set of fan works quotes more than another, a permutation test of
+ * every unit at once with the max-statistic correction.  Records, passages, active works, the
+ * coverage, unit_of[n_script] and the works quoting a unit as for fs_intervals.  n_works is
+ * every work of the file, active or not.  side[n_works] is a byte per work: 0 out, 1 side A,
+ * 2 side B.  The pool is the works of side A or B, N = NA + NB of them, active or not.
+ * Observed, per unit u: a(u) and b(u) the active works of A and of B quoting u, t = a + b,
+ *     D(u)   = a(u) * N - t(u) * NA                      (signed; = a * NB - b * NA)
+ *     den(u) = isqrt((t(u) * (N - t(u))) << 20)          (the exact floor of the square root)
+ *     X(d,u) = (|d| << 20) / den(u), 0 when den(u) = 0;  X(u) = X(D(u), u)
+ * Permutation r (0-based, r < permutations) draws a side A of its own: with h(r, w) the hash of
+ * fs_intervals with r in place of the replicate,
+ *     z = ((r << 32) | w) + seed * 0x9E3779B97F4A7C15                  (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31);  h = z >> 32
+ *     key(r, w) = h >> (32 - key_bits), 0 when key_bits = 0
+ * side A of r is the NA pool works smallest in (key(r, w), w): exactly NA works, ties on the key
+ * to the smaller work number (key_bits = 0: the first NA pool works in every permutation).
+ * a_r(u) = the active works of that set quoting u, D_r(u) = a_r(u) * N - t(u) * NA.
+ *     GE(u)      = the permutations r with |D_r(u)| >= |D(u)|
+ * The family is the units with t(u) >= min_quoting.
+ *     MX_r       = the maximum over the family of X(D_r(u), u); 0 with an empty family
+ *     MAX_UNIT_r = the first family unit attaining MX_r; 0xFFFFFFFF with an empty family
+ *     ADJ_GE(u)  = the permutations r with MX_r >= X(u) for a family unit, 0xFFFFFFFF otherwise
+ * Every output is an integer. */
+typedef struct fs_contrast_unit {
+  uint32_t a_works;          /* a(u)                                                      */
+  uint32_t b_works;          /* b(u)                                                      */
+  uint32_t ge;               /* GE(u)                                                     */
+  uint32_t adj_ge;           /* ADJ_GE(u); 0xFFFFFFFF outside the family                  */
+  uint64_t statistic;        /* X(u)                                                      */
+  int64_t d;                 /* D(u)                                                      */
+} fs_contrast_unit;          /* 32 bytes                                                  */
+
+typedef struct fs_contrast_perm {
+  uint64_t max_statistic;    /* MX_r                                                      */
+  uint32_t a_active;         /* the active works drawn into side A                        */
+  uint32_t max_unit;         /* MAX_UNIT_r                                                */
+} fs_contrast_perm;          /* 16 bytes                                                  */
+
+#define FS_CONTRAST_MAX_PERMUTATIONS 4096u
+/* n_works up to this, so that every intermediate fits 64 bits: a count is below 2^20 and N at
+ * most 2^20, so |D| <= 2^40 and |D| << 20 <= 2^60; t * (N - t) <= 2^38 and, shifted, 2^58. */
+#define FS_CONTRAST_MAX_WORKS (1u << 20)
+/* Counted: the incidence matrix (ceil(n_units / 64) * 64 * ceil(active works / 64) * 8 bytes),
+ * the labels (permutations + 2 rows, padded to a multiple of 64, of ceil(active works / 64) * 8
+ * bytes) and the counts (4 bytes per padded unit and padded row of the labels).  Their sum may
+ * be up to this. */
+#define FS_CONTRAST_MAX_BYTES (1u << 30)
+
+/* Host columns, the host unit map and the host side bytes in; units[n_units] and
+ * perms[permutations] out, on HIP device `device`; a_counts is null or
+ * [n_units][permutations], a_r(u), the null distribution itself.  Both entry points:
+ * FS_E_INVALID for null arguments, min_words == 0, min_quoting == 0, permutations outside
+ * 1..FS_CONTRAST_MAX_PERMUTATIONS, key_bits > 32, a side byte above 2, records out of (work,
+ * fan_ix) order, a work >= n_works, an orig_ix >= n_script or a unit_of entry that is neither
+ * below n_units nor 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script >
+ * FS_WORKS_MAX_SCRIPT, n_works > FS_CONTRAST_MAX_WORKS or tables above FS_CONTRAST_MAX_BYTES
+ * (the message states the three).  No records, no active work, an empty side and an empty pool
+ * follow the definitions: every count is 0, so D = 0, GE = permutations, X = 0 and nobody is in
+ * the family; without units only perms is written.
+ * The passes are separate launches and no workgroup waits on another: incidence (fs_companions'
+ * own); selection, a workgroup per permutation: a radix select of the NA-th smallest key over
+ * 12 + 12 + 8 bits with histograms in LDS, the hash made again in every pass, the works at the
+ * boundary key taken in ascending work number, then the labels of the active works as bits of
+ * a matrix L in the layout of M (tiles of 64 permutations, k-major), its last two rows the
+ * observed side A and the pool; product, counts[u][r] = sum over k of popc(M[u][k] & L[r][k]),
+ * a workgroup per (tile of units, tile of rows of L); the sweeps: a wave per unit for a, b, D,
+ * den (a double square root corrected to the exact floor), X, GE and an atomic max into MX_r,
+ * then MAX_UNIT_r by an atomic min among the units attaining MX_r together with ADJ_GE(u)
+ * against MX in LDS.  Switches of the environment, read once per call; the output is the same
+ * wherever they stand:
+ *   FS_CONTRAST_PRECHECK   1 (default): a lane reads MX_r first and leaves out an atomic that
+ *                          cannot win (MX_r only rises, and every value it takes is a true
+ *                          statistic); 0: every atomic is issued.  For the bench
+ *   FS_CONTRAST_MAX_BYTES  a lower bound than the macro's, for tests */
+int fs_contrast(int device, const uint32_t* work, const uint32_t* fan_ix,
+                const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                const uint32_t* unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+                const uint8_t* side, uint32_t min_quoting, uint32_t permutations, uint64_t seed,
+                uint32_t key_bits, fs_contrast_unit* units, fs_contrast_perm* perms,
+                uint32_t* a_counts);
+/* The same over device-resident fs_row records (16-byte aligned), a device-resident unit map of
+ * the index's n_script entries and device-resident side bytes into device buffers (16-byte
+ * aligned), on the index's device and stream; returns when they are written. */
+int fs_contrast_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                     const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                     uint32_t max_gap, const uint8_t* d_side, uint32_t min_quoting,
+                     uint32_t permutations, uint64_t seed, uint32_t key_bits,
+                     fs_contrast_unit* d_units, fs_contrast_perm* d_perms);
+/* HIP-event milliseconds of the last fs_contrast / fs_contrast_rows call on this thread:
+ * incidence (with the check of the side bytes, the run heads and the numbering of the active
+ * works, the host's wait for them included), selection (with the labels), product, sweeps, and
+ * the total of the four; 0 for a pass that did not run.  tools/contrast_bench.py. */
+int fs_contrast_times(double* ms);
+/* The exact floor of the square root of x, as the sweeps compute den(u): a double square root
+ * and its correction.  No device is touched. */
+uint64_t fs_contrast_isqrt(uint64_t x);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
