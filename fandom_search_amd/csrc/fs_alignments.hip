@@ -137,8 +137,8 @@ __device__ inline u64 peak_key(uint32_t best, uint32_t i) {
 
 // kPlace false: the order check, and the segment heads of this workgroup's 256 records into
 // cnt; true: the heads to their places, cnt holding the scan
-template <class Src, bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_al_heads(Src src, AlArgs a) {
+template <bool kPlace>
+__global__ __launch_bounds__(kBlock) void k_al_heads(RowsSrc src, AlArgs a) {
   __shared__ uint32_t s_w[kBlock / 64];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool head = false, bad = false;
@@ -186,8 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_al_bin(AlArgs a) {
 
 // a lane per segment of 1 .. small records: the recurrence as it stands.  The lane reads back
 // only what it wrote itself.
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_al_chain_lane(Src src, AlArgs a) {
+__global__ __launch_bounds__(kBlock) void k_al_chain_lane(RowsSrc src, AlArgs a) {
   const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
   if (k >= a.n_seg) return;
   const uint32_t b = a.heads[k], e = a.heads[k + 1];
@@ -236,8 +235,7 @@ __device__ inline u64 lane_u64(u64 v, uint32_t s) {                 // s wave-un
 }
 
 // a wave (= a workgroup) per listed segment
-template <class Src>
-__global__ __launch_bounds__(64) void k_al_chain_wave(Src src, AlArgs a) {
+__global__ __launch_bounds__(64) void k_al_chain_wave(RowsSrc src, AlArgs a) {
   const uint32_t lane = threadIdx.x;
   const uint32_t k = a.list[blockIdx.x];
   const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.heads[k]);
@@ -439,10 +437,10 @@ int al_check(uint64_t n_rows, uint32_t min_words, uint32_t reach, uint32_t match
 
 // *n_out and *n_path set; d_out and d_path written unless FS_E_CAPACITY (all on `s`, finished
 // on return)
-template <class Src>
-int al_run(const Src& src, uint32_t n, uint32_t min_words, uint32_t reach, uint32_t match,
+int al_run(const fs_row* d_rows, uint32_t n, uint32_t min_words, uint32_t reach, uint32_t match,
            uint32_t gap, fs_alignment* d_out, uint64_t cap, uint64_t* n_out, uint32_t* d_path,
            uint64_t path_cap, uint64_t* n_path, hipStream_t s) {
+  const RowsSrc src{d_rows};
   AlScratch k;
   AlArgs a{};
   Clock<6> clk;
@@ -466,7 +464,7 @@ int al_run(const Src& src, uint32_t n, uint32_t min_words, uint32_t reach, uint3
   FS_TRY(clk.mark(0, s));
 
   // the segments
-  hipLaunchKernelGGL((k_al_heads<Src, false>), dim3(rec_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_al_heads<false>), dim3(rec_blocks), blk, 0, s, src, a);
   hipLaunchKernelGGL(k_al_scan, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.cnt, rec_blocks,
                      a.status + kStSegs);
   FS_HIP(hipGetLastError());
@@ -485,7 +483,7 @@ int al_run(const Src& src, uint32_t n, uint32_t min_words, uint32_t reach, uint3
   a.heads = k.heads.p;
   a.bcnt = k.bcnt.p;
   a.list = k.list.p;
-  hipLaunchKernelGGL((k_al_heads<Src, true>), dim3(rec_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_al_heads<true>), dim3(rec_blocks), blk, 0, s, src, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(1, s));
 
@@ -521,8 +519,8 @@ int al_run(const Src& src, uint32_t n, uint32_t min_words, uint32_t reach, uint3
   FS_HIP(hipMemsetAsync(a.size, 0, nn * sizeof(uint32_t), s));
   FS_HIP(hipMemsetAsync(a.peak, 0, nn * sizeof(u64), s));
   if (a.small)
-    hipLaunchKernelGGL(k_al_chain_lane<Src>, dim3(seg_blocks), blk, 0, s, src, a);
-  if (n_wave) hipLaunchKernelGGL(k_al_chain_wave<Src>, dim3(n_wave), dim3(64), 0, s, src, a);
+    hipLaunchKernelGGL(k_al_chain_lane, dim3(seg_blocks), blk, 0, s, src, a);
+  if (n_wave) hipLaunchKernelGGL(k_al_chain_wave, dim3(n_wave), dim3(64), 0, s, src, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(3, s));
 
@@ -573,14 +571,14 @@ extern "C" int fs_alignments(int device, const uint32_t* work, const uint32_t* f
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_alignment> d_out;
   DBuf<uint32_t> d_path;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, nullptr, comb));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n, nullptr, comb));
   const uint64_t most = n_rows / min_words;                  // alignments never outnumber this
   FS_TRY(d_out.reserve(cap < most ? cap : most));
   FS_TRY(d_path.reserve(path_cap < n_rows ? path_cap : n_rows));   // nor path records the records
-  const int rc = al_run(cols.src(), n, min_words, reach, match, gap, d_out.p, cap, n_out, d_path.p,
+  const int rc = al_run(rows.p, n, min_words, reach, match, gap, d_out.p, cap, n_out, d_path.p,
                         path_cap, n_path, nullptr);
   if (rc != FS_OK) return rc;
   if (*n_out) FS_TRY(copy_out(out, d_out, *n_out));
@@ -607,8 +605,8 @@ extern "C" int fs_alignments_rows(fs_index* ix, const fs_row* d_rows, uint64_t n
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  return al_run(RowsSrc{d_rows}, (uint32_t)n_rows, min_words, reach, match, gap, d_out, cap, n_out,
-                d_path, path_cap, n_path, ix->stream);
+  return al_run(d_rows, (uint32_t)n_rows, min_words, reach, match, gap, d_out, cap, n_out, d_path,
+                path_cap, n_path, ix->stream);
 }
 
 extern "C" int fs_alignments_times(double* ms) {

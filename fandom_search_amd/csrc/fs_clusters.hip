@@ -342,11 +342,9 @@ struct ClustersJob {
   ClusterArgs a{};
 
   // d_works written, a.n_listed set (all on `s`, finished on return)
-  template <class Src>
-  int families(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-               uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
-               uint32_t min_shared, uint32_t min_jaccard, uint32_t min_size, uint32_t common_pct,
-               fs_cluster_work* d_works, hipStream_t s) {
+  int families(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+               uint32_t min_words, uint32_t max_gap, uint32_t min_shared, uint32_t min_jaccard,
+               uint32_t min_size, uint32_t common_pct, fs_cluster_work* d_works, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.n = n;
     a.n_works = n_works;
@@ -359,7 +357,7 @@ struct ClustersJob {
     a.common_pct = common_pct;
     a.works = d_works;
     const dim3 work_grid((n_works + kRunBlock - 1) / kRunBlock), blk(kRunBlock);
-    if (n) FS_TRY(cj.number(src, d_rows, cols, a, max_gap, s));
+    if (n) FS_TRY(cj.number(d_rows, a, max_gap, s));
     if (!a.n_active) {
       if (n_works) hipLaunchKernelGGL(k_clusters_works, work_grid, blk, 0, s, a, nullptr);
       FS_HIP(hipGetLastError());
@@ -409,7 +407,7 @@ struct ClustersJob {
     a.members = members.p;
     const dim3 row_grid((uint32_t)((rows + kRunBlock - 1) / kRunBlock));
     FS_TRY(clk.mark(0, s));
-    cj.cover(src, a, s);
+    cj.cover(d_rows, a, s);
     hipLaunchKernelGGL(k_clusters_init, row_grid, blk, 0, s, a);
     FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_clusters_links, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
@@ -496,14 +494,7 @@ int clusters_check(uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_
     fs_set_error("min_jaccard and common_pct are percentages: at most 100");
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: clusters take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: clusters take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("clusters", n_rows, n_script));
   *n_clusters = 0;
   return FS_OK;
 }
@@ -529,15 +520,14 @@ extern "C" int fs_clusters(int device, const uint32_t* work, const uint32_t* fan
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_cluster_work> d_works;
   DBuf<fs_cluster> d_clusters;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_works.reserve(n_works));
-  const ColsSrc src = cols.src();
   ClustersJob job;
-  FS_TRY(job.families(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_shared,
-                      min_jaccard, min_size, common_pct, d_works.p, nullptr));
+  FS_TRY(job.families(rows.p, n, n_works, n_script, min_words, max_gap, min_shared, min_jaccard,
+                      min_size, common_pct, d_works.p, nullptr));
   if (n_works) FS_TRY(copy_out(works, d_works, n_works));
   *n_clusters = job.a.n_listed;
   if (job.a.n_listed > cap) return FS_E_CAPACITY;
@@ -570,11 +560,9 @@ extern "C" int fs_clusters_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_r
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   ClustersJob job;
-  FS_TRY(job.families(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                      min_words, max_gap, min_shared, min_jaccard, min_size, common_pct, d_works,
-                      ix->stream));
+  FS_TRY(job.families(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, min_words, max_gap,
+                      min_shared, min_jaccard, min_size, common_pct, d_works, ix->stream));
   *n_clusters = job.a.n_listed;
   if (job.a.n_listed > cap) return FS_E_CAPACITY;
   return job.write(d_clusters, ix->stream);

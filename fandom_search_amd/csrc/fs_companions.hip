@@ -200,11 +200,9 @@ struct CompJob {
   }
 
   // d_units written, n_pairs set (all on `s`, finished on return)
-  template <class Src>
-  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-            uint32_t n_works, uint32_t n_script, const uint32_t* d_unit_of, uint32_t n_units,
-            uint32_t min_words, uint32_t max_gap, uint32_t min_both, uint32_t min_share,
-            fs_companion_unit* d_units, hipStream_t s) {
+  int count(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+            const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+            uint32_t min_both, uint32_t min_share, fs_companion_unit* d_units, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.r.n = n;
     a.r.n_works = n_works;
@@ -225,7 +223,7 @@ struct CompJob {
                          dim3(kRunBlock), 0, s, d_unit_of, n_script, n_units, bad.p);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-    const int rc = cj.number(src, d_rows, cols, a.r, max_gap, s);
+    const int rc = cj.number(d_rows, a.r, max_gap, s);
     FS_HIP(hipStreamSynchronize(s));
     if (rc != FS_OK) return rc;
     if (bad_units) {
@@ -279,8 +277,8 @@ struct CompJob {
     FS_TRY(clk.mark(0, s));
     hipLaunchKernelGGL(k_pairs_list, dim3((n_works + kRunBlock - 1) / kRunBlock), blk, 0, s, a.r,
                        cj.flag.p);
-    hipLaunchKernelGGL(k_comp_incidence<Src>, dim3((a.r.n_runs + kRunBlock - 1) / kRunBlock), blk,
-                       0, s, src, a, cj.flag.p);
+    hipLaunchKernelGGL(k_comp_incidence, dim3((a.r.n_runs + kRunBlock - 1) / kRunBlock), blk, 0,
+                       s, RowsSrc{d_rows}, a, cj.flag.p);
     hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
     FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_comp_tiles<0>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
@@ -333,14 +331,7 @@ int comp_check(uint64_t n_rows, uint32_t n_script, const void* unit_of, uint32_t
     fs_set_error("min_share %u: a whole percentage, 0 to 100", min_share);
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: companions take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: companions take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("companions", n_rows, n_script));
   *n_pairs = 0;
   return FS_OK;
 }
@@ -366,17 +357,16 @@ extern "C" int fs_companions(int device, const uint32_t* work, const uint32_t* f
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_unit_of;
   DBuf<fs_companion_unit> d_units;
   DBuf<fs_companion> d_pairs;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n_script, nullptr));
   FS_TRY(d_units.reserve(n_units));
-  const ColsSrc src = cols.src();
   CompJob job;
-  FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
-                   max_gap, min_both, min_share, d_units.p, nullptr));
+  FS_TRY(job.count(rows.p, n, n_works, n_script, d_unit_of.p, n_units, min_words, max_gap,
+                   min_both, min_share, d_units.p, nullptr));
   FS_TRY(copy_out(units, d_units, n_units));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
@@ -412,11 +402,9 @@ extern "C" int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   CompJob job;
-  FS_TRY(job.count(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                   d_unit_of, n_units, min_words, max_gap, min_both, min_share, d_units,
-                   ix->stream));
+  FS_TRY(job.count(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, d_unit_of, n_units,
+                   min_words, max_gap, min_both, min_share, d_units, ix->stream));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
   return job.write(d_pairs, ix->stream);

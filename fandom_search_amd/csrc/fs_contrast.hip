@@ -285,11 +285,10 @@ struct ConJob {
 
   // d_units and d_perms written, and h_counts (host, [n_units][permutations]) unless null (all
   // on `s`, finished on return)
-  template <class Src>
-  int run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n, uint32_t n_works,
-          uint32_t n_script, const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
-          uint32_t max_gap, const uint8_t* d_side, uint32_t min_quoting, uint32_t permutations,
-          uint64_t seed, uint32_t key_bits, fs_contrast_unit* d_units, fs_contrast_perm* d_perms,
+  int run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+          const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+          const uint8_t* d_side, uint32_t min_quoting, uint32_t permutations, uint64_t seed,
+          uint32_t key_bits, fs_contrast_unit* d_units, fs_contrast_perm* d_perms,
           uint32_t* h_counts, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     const uint64_t max_bytes =
@@ -326,7 +325,7 @@ struct ConJob {
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(st, tally.p, sizeof st, hipMemcpyDeviceToHost, s));
     int rc = FS_OK;
-    if (n) rc = cj.number(src, d_rows, cols, a.r, max_gap, s);
+    if (n) rc = cj.number(d_rows, a.r, max_gap, s);
     FS_HIP(hipStreamSynchronize(s));
     if (st[0]) {
       fs_set_error("a side byte above 2 (0 out, 1 side A, 2 side B)");
@@ -383,8 +382,8 @@ struct ConJob {
       hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
                          cj.flag.p);
       if (n_units)
-        hipLaunchKernelGGL(k_comp_incidence<Src>, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0,
-                           s, src, a, cj.flag.p);
+        hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
+                           RowsSrc{d_rows}, a, cj.flag.p);
     }
     FS_TRY(clk.mark(1, s));
     if (some) hipLaunchKernelGGL(k_con_select, dim3(a.R), dim3(kSel), 0, s, a);
@@ -461,21 +460,20 @@ extern "C" int fs_contrast(int device, const uint32_t* work, const uint32_t* fan
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_unit_of;
   DBuf<uint8_t> d_side;
   DBuf<fs_contrast_unit> d_units;
   DBuf<fs_contrast_perm> d_perms;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n && n_units ? n_script : 0, nullptr));
   FS_TRY(d_side.upload(side, n_works, nullptr));
   FS_TRY(d_units.reserve(n_units));
   FS_TRY(d_perms.reserve(permutations));
-  const ColsSrc src = cols.src();
   ConJob job;
-  FS_TRY(job.run(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
-                 max_gap, d_side.p, min_quoting, permutations, seed, key_bits, d_units.p,
-                 d_perms.p, a_counts, nullptr));
+  FS_TRY(job.run(rows.p, n, n_works, n_script, d_unit_of.p, n_units, min_words, max_gap, d_side.p,
+                 min_quoting, permutations, seed, key_bits, d_units.p, d_perms.p, a_counts,
+                 nullptr));
   if (n_units) FS_TRY(copy_out(units, d_units, n_units));
   FS_TRY(copy_out(perms, d_perms, permutations));
   FS_HIP(hipDeviceSynchronize());
@@ -506,11 +504,10 @@ extern "C" int fs_contrast_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_r
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   ConJob job;
-  return job.run(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                 d_unit_of, n_units, min_words, max_gap, d_side, min_quoting, permutations, seed,
-                 key_bits, d_units, d_perms, nullptr, ix->stream);
+  return job.run(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, d_unit_of, n_units,
+                 min_words, max_gap, d_side, min_quoting, permutations, seed, key_bits, d_units,
+                 d_perms, nullptr, ix->stream);
 }
 
 extern "C" int fs_contrast_times(double* ms) {

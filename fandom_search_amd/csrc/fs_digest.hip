@@ -498,10 +498,9 @@ struct DigestJob {
   uint32_t n_picks = 0, total = 0;
 
   // a.n_active, n_picks, total and the picks on the device set (all on `s`, finished on return)
-  template <class Src>
-  int rounds(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-             uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
-             uint32_t max_picks, uint32_t cover, uint32_t min_gain, hipStream_t s) {
+  int rounds(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+             uint32_t min_words, uint32_t max_gap, uint32_t max_picks, uint32_t cover,
+             uint32_t min_gain, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.n = n;
     a.n_works = n_works;
@@ -517,7 +516,7 @@ struct DigestJob {
     if (!batch) batch = kBatch;
     const uint64_t max_bytes = FS_DIGEST_MAX_BYTES;
     if (!n) return FS_OK;
-    FS_TRY(cj.number(src, d_rows, cols, a, max_gap, s));
+    FS_TRY(cj.number(d_rows, a, max_gap, s));
     if (!a.n_active) return FS_OK;
     a.seed = a.lazy && a.n_tiles > env_u32("FS_DIGEST_SEED_TILES", kSeedTiles, 0xFFFFFFFFu);
     const size_t rows = (size_t)a.n_tiles * kTile;
@@ -563,7 +562,7 @@ struct DigestJob {
     a.picks = picks.p;
     a.pick_cap = most;
     FS_TRY(clk.mark(0, s));
-    cj.cover(src, a, s);
+    cj.cover(d_rows, a, s);
     hipLaunchKernelGGL(k_digest_union, dim3(a.n_tiles), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_digest_total, dim3(1), dim3(kApply), 0, s, a);
     hipLaunchKernelGGL(k_digest_init, dim3(a.n_tiles), dim3(kTile), 0, s, a);
@@ -673,13 +672,12 @@ extern "C" int fs_digest(int device, const uint32_t* work, const uint32_t* fan_i
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_digest_work> d_works;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
-  const ColsSrc src = cols.src();
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   DigestJob job;
-  FS_TRY(job.rounds(src, nullptr, src, n, n_works, n_script, min_words, max_gap, max_picks, cover,
-                    min_gain, nullptr));
+  FS_TRY(job.rounds(rows.p, n, n_works, n_script, min_words, max_gap, max_picks, cover, min_gain,
+                    nullptr));
   *n_picks = job.n_picks;
   *n_active = job.a.n_active;
   *total_words = job.total;
@@ -717,10 +715,9 @@ extern "C" int fs_digest_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
   }
   if (!n_rows) return FS_OK;
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   DigestJob job;
-  FS_TRY(job.rounds(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                    min_words, max_gap, max_picks, cover, min_gain, ix->stream));
+  FS_TRY(job.rounds(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, min_words, max_gap,
+                    max_picks, cover, min_gain, ix->stream));
   *n_picks = job.n_picks;
   *n_active = job.a.n_active;
   *total_words = job.total;

@@ -345,10 +345,9 @@ struct FragJob {
   uint32_t dedup = 1;
 
   // a.n_active and n_frags set (all on `s`, finished on return)
-  template <class Src>
-  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-            uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
-            uint32_t min_works, uint32_t min_length, uint32_t max_words, hipStream_t s) {
+  int count(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+            uint32_t min_words, uint32_t max_gap, uint32_t min_works, uint32_t min_length,
+            uint32_t max_words, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.n = n;
     a.n_works = n_works;
@@ -362,7 +361,7 @@ struct FragJob {
     const uint32_t bits = env_u32("FS_FRAGMENTS_HASH_BITS", 32u, 32u);
     a.hash_mask = bits >= 32 ? ~0u : (1u << bits) - 1;
     if (!n) return FS_OK;
-    FS_TRY(cj.number(src, d_rows, cols, a, max_gap, s));
+    FS_TRY(cj.number(d_rows, a, max_gap, s));
     if (!a.n_active) return FS_OK;
     // rows d0 .. d1: no interval is longer than the script
     a.d0 = min_length - 1;
@@ -430,7 +429,7 @@ struct FragJob {
     const dim3 blk(kRunBlock);
     const dim3 list_grid(blocks_of(a.list_cap, kRunBlock));
     FS_TRY(clk.mark(0, s));
-    cj.cover(src, a, s);
+    cj.cover(d_rows, a, s);
     hipLaunchKernelGGL(k_frag_runs, dim3((uint32_t)run_blocks), blk, 0, s, a);
     FS_TRY(clk.mark(1, s));
     if (dedup) {
@@ -520,14 +519,13 @@ extern "C" int fs_fragments(int device, const uint32_t* work, const uint32_t* fa
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_fragment> d_frags;
   DBuf<fs_fragment_work> d_works;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
-  const ColsSrc src = cols.src();
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FragJob job;
-  FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_works,
-                   min_length, max_words, nullptr));
+  FS_TRY(job.count(rows.p, n, n_works, n_script, min_words, max_gap, min_works, min_length,
+                   max_words, nullptr));
   *n_frags = job.n_frags;
   *n_active = job.a.n_active;
   if (job.n_frags > frags_cap || job.a.n_active > works_cap) return FS_E_CAPACITY;
@@ -565,10 +563,9 @@ extern "C" int fs_fragments_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_
   }
   if (!n_rows) return FS_OK;
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   FragJob job;
-  FS_TRY(job.count(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                   min_words, max_gap, min_works, min_length, max_words, ix->stream));
+  FS_TRY(job.count(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, min_words, max_gap,
+                   min_works, min_length, max_words, ix->stream));
   *n_frags = job.n_frags;
   *n_active = job.a.n_active;
   if (job.n_frags > frags_cap || job.a.n_active > works_cap) return FS_E_CAPACITY;

@@ -44,14 +44,6 @@ enum { G_WORKS, G_PWORKS, G_WORDS, G_EXACT, G_PASSAGES, G_PASSAGE_WORDS, G_LONGE
        G_PEAK, G_PEAK_FIRST, G_TOP, G_TOP_WORDS, G_CELLS, G_ROWS };
 constexpr uint32_t kWorkStats = 5;          // records, exact, passages, records in them, longest
 
-// the exact flag of a record: from its distance, or the column the caller passed with the others
-struct ExactCols : ColsSrc {
-  const uint8_t* ex;
-};
-
-__device__ inline bool exact_of(const RowsSrc& src, uint64_t i) { return src.comb(i) <= 0.0; }
-__device__ inline bool exact_of(const ExactCols& src, uint64_t i) { return src.ex[i] != 0; }
-
 struct GroupsArgs {
   uint32_t n, n_works, n_script, nk, n_groups, n_labels, n_runs, min_words, min_works;
   uint32_t seg_k, nkp, nkb;     // lanes of a unit over the 64-bit words: segment, padded, blocks
@@ -118,8 +110,7 @@ __device__ inline uint32_t seg_prefix(uint32_t v, uint32_t seg, uint32_t lane) {
   return inc - v;
 }
 
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_groups_records(Src src, GroupsArgs a) {
+__global__ __launch_bounds__(kBlock) void k_groups_records(RowsSrc src, GroupsArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool valid = i < a.n, ex = false;
@@ -129,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_groups_records(Src src, GroupsArgs a
     if (k.x >= a.n_works || k.z >= a.n_script) valid = false;
   }
   if (__ballot(i < a.n && !valid) && lane == 0) atomicOr(&a.status[0], 1u);
-  if (valid) ex = exact_of(src, i);
+  if (valid) ex = src.comb(i) <= 0.0;
   int first;
   unsigned long long kf;
   for (uint64_t todo = __ballot(valid); todo;) {
@@ -160,8 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_groups_records(Src src, GroupsArgs a
 }
 
 // one lane per run
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_groups_runs(Src src, GroupsArgs a) {
+__global__ __launch_bounds__(kBlock) void k_groups_runs(RowsSrc src, GroupsArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool keep = false;
@@ -587,11 +577,10 @@ struct GroupsJob {
 
   // d_groups written, n_cells and n_words set (all on `s`, finished on return); n > 0 and
   // n_groups > 0
-  template <class Src>
-  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, const GroupsPlan& plan,
-            uint32_t n, uint32_t n_works, uint32_t n_script, uint32_t n_groups,
-            const uint32_t* label_of_host, uint32_t n_labels, uint32_t min_words,
-            uint32_t max_gap, uint32_t min_works, fs_group* d_groups, hipStream_t s) {
+  int count(const fs_row* d_rows, const GroupsPlan& plan, uint32_t n, uint32_t n_works,
+            uint32_t n_script, uint32_t n_groups, const uint32_t* label_of_host, uint32_t n_labels,
+            uint32_t min_words, uint32_t max_gap, uint32_t min_works, fs_group* d_groups,
+            hipStream_t s) {
     a.n = n;
     a.n_works = n_works;
     a.n_script = n_script;
@@ -609,8 +598,7 @@ struct GroupsJob {
     a.n_units = (uint32_t)plan.units.size();
     a.n_split = (uint32_t)plan.split_group.size();
     a.groups = reinterpret_cast<uint32_t*>(d_groups);
-    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &runs,
-                        &a.heads, &a.n_runs));
+    FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &runs, &a.heads, &a.n_runs));
     if (!n_works || !n_script) return invalid();
     if (!fits((uint64_t)a.n_units * a.nkp) || !fits((uint64_t)a.n_units * n_labels) ||
         !fits((uint64_t)n_groups * a.nlp)) {
@@ -674,8 +662,9 @@ struct GroupsJob {
     a.status = status.p;
     const dim3 blk(kBlock);
     FS_TRY(mark(0, s));
-    hipLaunchKernelGGL(k_groups_records<Src>, grid(n), blk, 0, s, src, a);
-    hipLaunchKernelGGL(k_groups_runs<Src>, grid(a.n_runs), blk, 0, s, src, a);
+    const RowsSrc src{d_rows};
+    hipLaunchKernelGGL(k_groups_records, grid(n), blk, 0, s, src, a);
+    hipLaunchKernelGGL(k_groups_runs, grid(a.n_runs), blk, 0, s, src, a);
     FS_TRY(mark(1, s));
     if (a.n_units) {
       hipLaunchKernelGGL(k_groups_stats, grid(a.n_units), blk, 0, s, a);
@@ -774,18 +763,16 @@ extern "C" int fs_groups(int device, const uint32_t* work, const uint32_t* fan_i
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
-  DBuf<uint8_t> d_exact;
+  DBuf<fs_row> rows;
   DBuf<fs_group> d_groups;
   DBuf<fs_group_cell> d_cells;
   DBuf<fs_group_word> d_words;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
-  FS_TRY(d_exact.upload(exact, n, nullptr));
+  // the exact flags travel as comb: 0.0 where set, 1.0 where not
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n, nullptr, nullptr, exact));
   FS_TRY(d_groups.reserve(n_groups));
-  const ExactCols src{cols.src(), d_exact.p};
   GroupsJob job;
-  FS_TRY(job.count(src, nullptr, src, plan, n, n_works, n_script, n_groups, label_of, n_labels,
-                   min_words, max_gap, min_works, d_groups.p, nullptr));
+  FS_TRY(job.count(rows.p, plan, n, n_works, n_script, n_groups, label_of, n_labels, min_words,
+                   max_gap, min_works, d_groups.p, nullptr));
   FS_TRY(copy_out(groups, d_groups, n_groups));
   *n_cells = job.n_cells;
   *n_words = job.n_words;
@@ -840,10 +827,9 @@ extern "C" int fs_groups_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
     FS_HIP(hipStreamSynchronize(ix->stream));
     return FS_OK;
   }
-  const RowsSrc src{d_rows};
   GroupsJob job;
-  FS_TRY(job.count(src, d_rows, ColsSrc{}, plan, (uint32_t)n_rows, n_works, n_script, n_groups,
-                   label_of, n_labels, min_words, max_gap, min_works, d_groups, ix->stream));
+  FS_TRY(job.count(d_rows, plan, (uint32_t)n_rows, n_works, n_script, n_groups, label_of, n_labels,
+                   min_words, max_gap, min_works, d_groups, ix->stream));
   *n_cells = job.n_cells;
   *n_words = job.n_words;
   if (job.n_cells > cap_cells || job.n_words > cap_words) return FS_E_CAPACITY;

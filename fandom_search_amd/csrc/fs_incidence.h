@@ -35,8 +35,7 @@ __global__ __launch_bounds__(kRunBlock) void k_comp_units_ok(const uint32_t* uni
 // A lane per run (after CoverJob::number found nothing: every work and word is inside, and
 // k_comp_units_ok: every unit is a row of M); the wave's kept runs are then taken in turn by
 // the whole wave.
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_comp_incidence(Src src, IncArgs a,
+__global__ __launch_bounds__(kRunBlock) void k_comp_incidence(RowsSrc src, IncArgs a,
                                                               const uint32_t* flag) {
   const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;

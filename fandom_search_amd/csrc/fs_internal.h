@@ -546,10 +546,23 @@ int fs_launch_blk_work(const uint64_t* work_off, uint32_t n_works, uint32_t n_bl
 // (d_heads[k] = first record of run k, d_heads[n_runs] = n; FS_E_INVALID when out of order);
 // the scratch behind d_heads lives until fs_runs_free.  Synchronises `s`.
 struct fs_runs;
-int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d_fan,
-                 const uint32_t* d_orig, uint32_t n, uint32_t min_words, uint32_t max_gap,
+int fs_runs_find(const fs_row* d_rows, uint32_t n, uint32_t min_words, uint32_t max_gap,
                  hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs);
+// the same over three key columns, for fs_readings.hip, whose records are not fs_row records
+int fs_runs_find_cols(const uint32_t* d_work, const uint32_t* d_fan, const uint32_t* d_orig,
+                      uint32_t n, uint32_t min_words, uint32_t max_gap, hipStream_t s,
+                      fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs);
 void fs_runs_free(fs_runs* r);
+
+// fs_passages.hip: what every entry point over host columns starts with.  The n records of the
+// caller's columns into `rows` as fs_row{work, fan_ix, orig_ix, 0, dist, comb}: the columns
+// uploaded on the null stream in the order work, fan, orig, dist, comb (exact), then packed by
+// one kernel, the doubles bit for bit.  A null dist or comb is 0.0 in every record; `exact`
+// (fs_groups: a byte per record) stands in for comb as exact ? 0.0 : 1.0.  The column staging is
+// freed on return, which waits for the kernel: `rows` is all the device holds afterwards.
+int fs_host_rows(DBuf<fs_row>& rows, const uint32_t* work, const uint32_t* fan,
+                 const uint32_t* orig, size_t n, const double* dist = nullptr,
+                 const double* comb = nullptr, const uint8_t* exact = nullptr);
 
 void fs_host_pool_free(struct fs_host_pool* p);
 int fs_launch_levtab(fs_index* ix, fs_corpus* c, hipStream_t s);

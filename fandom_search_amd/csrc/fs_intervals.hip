@@ -344,11 +344,10 @@ struct IntJob {
   IntArgs a{};
 
   // d_units and d_reps written (all on `s`, finished on return)
-  template <class Src>
-  int run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n, uint32_t n_works,
-          uint32_t n_script, const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
-          uint32_t max_gap, uint32_t replicates, uint64_t seed, uint32_t level,
-          fs_interval_unit* d_units, fs_interval_replicate* d_reps, hipStream_t s) {
+  int run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+          const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+          uint32_t replicates, uint64_t seed, uint32_t level, fs_interval_unit* d_units,
+          fs_interval_replicate* d_reps, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     const uint32_t mfma = env_u32("FS_INTERVALS_MFMA", 1u, 1u);
     const uint64_t max_bytes =
@@ -382,7 +381,7 @@ struct IntJob {
                            d_unit_of, n_script, n_units, bad.p);
       FS_HIP(hipGetLastError());
       FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-      const int rc = cj.number(src, d_rows, cols, a.r, max_gap, s);
+      const int rc = cj.number(d_rows, a.r, max_gap, s);
       FS_HIP(hipStreamSynchronize(s));
       if (rc != FS_OK) return rc;
       if (bad_units) {
@@ -432,8 +431,8 @@ struct IntJob {
     if (some) {
       hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
                          cj.flag.p);
-      hipLaunchKernelGGL(k_comp_incidence<Src>, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                         src, a, cj.flag.p);
+      hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
+                         RowsSrc{d_rows}, a, cj.flag.p);
       hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
     }
     FS_TRY(clk.mark(1, s));
@@ -552,18 +551,17 @@ extern "C" int fs_intervals(int device, const uint32_t* work, const uint32_t* fa
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_unit_of;
   DBuf<fs_interval_unit> d_units;
   DBuf<fs_interval_replicate> d_reps;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n && n_units ? n_script : 0, nullptr));
   FS_TRY(d_units.reserve(n_units));
   FS_TRY(d_reps.reserve(replicates));
-  const ColsSrc src = cols.src();
   IntJob job;
-  FS_TRY(job.run(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
-                 max_gap, replicates, seed, level, d_units.p, d_reps.p, nullptr));
+  FS_TRY(job.run(rows.p, n, n_works, n_script, d_unit_of.p, n_units, min_words, max_gap, replicates,
+                 seed, level, d_units.p, d_reps.p, nullptr));
   if (n_units) FS_TRY(copy_out(units, d_units, n_units));
   FS_TRY(copy_out(reps, d_reps, replicates));
   FS_HIP(hipDeviceSynchronize());
@@ -593,11 +591,9 @@ extern "C" int fs_intervals_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   IntJob job;
-  return job.run(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                 d_unit_of, n_units, min_words, max_gap, replicates, seed, level, d_units, d_reps,
-                 ix->stream);
+  return job.run(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, d_unit_of, n_units,
+                 min_words, max_gap, replicates, seed, level, d_units, d_reps, ix->stream);
 }
 
 extern "C" int fs_intervals_times(double* ms) {

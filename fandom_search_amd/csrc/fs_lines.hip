@@ -94,8 +94,7 @@ __global__ __launch_bounds__(kRunBlock) void k_lines_init(fs_line* lines, uint32
 // A lane per run (after CoverJob::number found nothing: every work and word is inside, and
 // k_lines_check: line_of is the line of every word); the wave's kept runs are then taken in
 // turn by the whole wave.
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_lines_tables(Src src, LinesArgs a,
+__global__ __launch_bounds__(kRunBlock) void k_lines_tables(RowsSrc src, LinesArgs a,
                                                             const uint32_t* flag) {
   const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
@@ -306,11 +305,9 @@ struct LinesJob {
   }
 
   // a.r.n_active and n_cells set, the tables built (all on `s`, finished on return)
-  template <class Src>
-  int tables(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-             uint32_t n_works, uint32_t n_script, const uint32_t* d_line_first, uint32_t n_lines,
-             uint32_t min_words, uint32_t max_gap, uint32_t most, fs_line* d_lines,
-             hipStream_t s) {
+  int tables(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+             const uint32_t* d_line_first, uint32_t n_lines, uint32_t min_words, uint32_t max_gap,
+             uint32_t most, fs_line* d_lines, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.r.n = n;
     a.r.n_works = n_works;
@@ -338,7 +335,7 @@ struct LinesJob {
                          d_line_first, n_lines, n_script, line_of.p);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(&bad_lines, bad.p, sizeof bad_lines, hipMemcpyDeviceToHost, s));
-    const int rc = cj.number(src, d_rows, cols, a.r, max_gap, s);
+    const int rc = cj.number(d_rows, a.r, max_gap, s);
     FS_HIP(hipStreamSynchronize(s));
     if (rc != FS_OK) return rc;
     if (bad_lines) {
@@ -392,8 +389,8 @@ struct LinesJob {
                        cj.flag.p);
     hipLaunchKernelGGL(k_lines_init, dim3(blocks_of(n_lines, kRunBlock)), blk, 0, s, d_lines,
                        n_lines);
-    hipLaunchKernelGGL(k_lines_tables<Src>, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s, src,
-                       a, cj.flag.p);
+    hipLaunchKernelGGL(k_lines_tables, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
+                       RowsSrc{d_rows}, a, cj.flag.p);
     hipLaunchKernelGGL(k_lines_popc, dim3(blocks_of(n_lines, kRunBlock / 64)), blk, 0, s, a);
     hipLaunchKernelGGL(k_pairs_scan<unsigned long long>, dim3(1), dim3(kScanBlock), 0, s, cnt.p,
                        (uint64_t)n_lines, off.p, total.p);
@@ -477,18 +474,17 @@ extern "C" int fs_lines(int device, const uint32_t* work, const uint32_t* fan_ix
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_line_first;
   DBuf<fs_line> d_lines;
   DBuf<fs_line_work> d_works;
   DBuf<fs_line_cell> d_cells;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_line_first.upload(line_first, (size_t)n_lines + 1, nullptr));
   FS_TRY(d_lines.reserve(n_lines));
-  const ColsSrc src = cols.src();
   LinesJob job;
-  FS_TRY(job.tables(src, nullptr, src, n, n_works, n_script, d_line_first.p, n_lines, min_words,
-                    max_gap, most, d_lines.p, nullptr));
+  FS_TRY(job.tables(rows.p, n, n_works, n_script, d_line_first.p, n_lines, min_words, max_gap, most,
+                    d_lines.p, nullptr));
   *n_active = job.a.r.n_active;
   *n_cells = job.n_cells;
   const bool place = job.a.r.n_active <= works_cap && job.n_cells <= cells_cap;
@@ -529,10 +525,9 @@ extern "C" int fs_lines_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   LinesJob job;
-  FS_TRY(job.tables(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                    d_line_first, n_lines, min_words, max_gap, most, d_lines, ix->stream));
+  FS_TRY(job.tables(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, d_line_first,
+                    n_lines, min_words, max_gap, most, d_lines, ix->stream));
   *n_active = job.a.r.n_active;
   *n_cells = job.n_cells;
   const bool place = job.a.r.n_active <= works_cap && job.n_cells <= cells_cap;

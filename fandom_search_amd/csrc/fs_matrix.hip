@@ -98,8 +98,8 @@ __global__ __launch_bounds__(kScanBlock) void k_mx_scan(const uint32_t* in, uint
 
 // kPlace false: bounds, order and the run heads of this workgroup's 256 records into rcnt;
 // true (rcnt holding the scan): the work of every run, c(run, v) counted
-template <class Src, bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_mx_heads(Src src, MxArgs a) {
+template <bool kPlace>
+__global__ __launch_bounds__(kBlock) void k_mx_heads(RowsSrc src, MxArgs a) {
   __shared__ uint32_t s_w[kBlock / 64];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool head = false, bad = false, unsorted = false;
@@ -383,10 +383,10 @@ struct MxScratch {
 
 // d_starts (when not null) and d_out written, *n_spans and *n_kept set; d_out untouched on
 // FS_E_CAPACITY (all on `s`, finished on return)
-template <class Src>
-int mx_run(const Src& src, uint32_t n, uint32_t n_works, uint32_t n_script, uint32_t ngram,
+int mx_run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script, uint32_t ngram,
            uint32_t* d_starts, fs_matrix_ngram* d_out, uint64_t cap, uint64_t* n_spans,
            uint64_t* n_kept, hipStream_t s) {
+  const RowsSrc src{d_rows};
   for (double& t : t_ms) t = 0.0;
   if (!n_works || !n_script) {
     fs_set_error("a work >= n_works or a script index >= n_script");
@@ -413,7 +413,7 @@ int mx_run(const Src& src, uint32_t n, uint32_t n_works, uint32_t n_script, uint
   a.rcnt = k.rcnt.p;
   FS_HIP(hipMemsetAsync(a.status, 0, kStWords * sizeof(uint32_t), s));
   FS_TRY(clk.mark(0, s));
-  hipLaunchKernelGGL((k_mx_heads<Src, false>), dim3(rec_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_mx_heads<false>), dim3(rec_blocks), blk, 0, s, src, a);
   hipLaunchKernelGGL(k_mx_scan, dim3(1), dim3(kScanBlock), 0, s, a.rcnt, a.rcnt, rec_blocks,
                      a.status + kStRuns);
   FS_HIP(hipGetLastError());
@@ -454,7 +454,7 @@ int mx_run(const Src& src, uint32_t n, uint32_t n_works, uint32_t n_script, uint
   FS_HIP(hipMemsetAsync(a.cv, 0, a.slots * sizeof(uint32_t), s));
   FS_HIP(hipMemsetAsync(a.rcur, 0, (2 * nr + 1) * sizeof(uint32_t), s));       // and rspan
   FS_HIP(hipMemsetAsync(a.diff, 0, ((size_t)n_script + 1) * sizeof(uint32_t), s));
-  hipLaunchKernelGGL((k_mx_heads<Src, true>), dim3(rec_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_mx_heads<true>), dim3(rec_blocks), blk, 0, s, src, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(1, s));
 
@@ -536,15 +536,15 @@ extern "C" int fs_matrix(int device, const uint32_t* work, const uint32_t* fan_i
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_starts;
   DBuf<fs_matrix_ngram> d_out;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_starts.reserve(n_script));
   const uint64_t most = n_rows / ngram + 1;                  // n-grams never outnumber this
   FS_TRY(d_out.reserve(cap < most ? cap : most));
-  const int rc = mx_run(cols.src(), n, n_works, n_script, ngram, d_starts.p, d_out.p, cap,
-                        n_spans, n_kept, nullptr);
+  const int rc = mx_run(rows.p, n, n_works, n_script, ngram, d_starts.p, d_out.p, cap, n_spans,
+                        n_kept, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
   if (starts && n_script) FS_TRY(copy_out(starts, d_starts, n_script));
   if (rc == FS_OK && *n_kept) FS_TRY(copy_out(out, d_out, *n_kept));
@@ -576,8 +576,7 @@ extern "C" int fs_matrix_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
     for (double& t : t_ms) t = 0.0;
     return FS_OK;
   }
-  const RowsSrc src{d_rows};
-  return mx_run(src, (uint32_t)n_rows, n_works, n_script, ngram, d_starts, d_out, cap, n_spans,
+  return mx_run(d_rows, (uint32_t)n_rows, n_works, n_script, ngram, d_starts, d_out, cap, n_spans,
                 n_kept, ix->stream);
 }
 

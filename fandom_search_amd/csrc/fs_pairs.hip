@@ -202,10 +202,9 @@ struct PairsJob {
   uint64_t n_pairs = 0;
 
   // d_works written, n_pairs set (all on `s`, finished on return)
-  template <class Src>
-  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-            uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
-            uint32_t min_shared, fs_pair_work* d_works, hipStream_t s) {
+  int count(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+            uint32_t min_words, uint32_t max_gap, uint32_t min_shared, fs_pair_work* d_works,
+            hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
     a.n = n;
     a.n_works = n_works;
@@ -215,7 +214,7 @@ struct PairsJob {
     a.min_shared = min_shared;
     a.works = d_works;
     const dim3 work_grid((n_works + kRunBlock - 1) / kRunBlock), blk(kRunBlock);
-    if (n) FS_TRY(cj.number(src, d_rows, cols, a, max_gap, s));
+    if (n) FS_TRY(cj.number(d_rows, a, max_gap, s));
     if (!a.n_active) {
       if (n_works) hipLaunchKernelGGL(k_pairs_works, work_grid, blk, 0, s, a, nullptr);
       FS_HIP(hipGetLastError());
@@ -252,7 +251,7 @@ struct PairsJob {
     a.any = any.p;
     a.total = total.p;
     FS_TRY(clk.mark(0, s));
-    cj.cover(src, a, s);
+    cj.cover(d_rows, a, s);
     FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_pairs_tiles<0>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_pairs_scan<unsigned long long>, dim3(1), dim3(kScanBlock), 0, s, cnt.p,
@@ -299,14 +298,7 @@ int pairs_check(uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t m
     fs_set_error("min_words and min_shared must be at least 1");
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: pairs take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: pairs take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("pairs", n_rows, n_script));
   *n_pairs = 0;
   return FS_OK;
 }
@@ -331,15 +323,14 @@ extern "C" int fs_pairs(int device, const uint32_t* work, const uint32_t* fan_ix
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_pair_work> d_works;
   DBuf<fs_pair> d_pairs;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_works.reserve(n_works));
-  const ColsSrc src = cols.src();
   PairsJob job;
-  FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_shared,
-                   d_works.p, nullptr));
+  FS_TRY(job.count(rows.p, n, n_works, n_script, min_words, max_gap, min_shared, d_works.p,
+                   nullptr));
   if (n_works) FS_TRY(copy_out(works, d_works, n_works));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
@@ -373,10 +364,9 @@ extern "C" int fs_pairs_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   PairsJob job;
-  FS_TRY(job.count(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                   min_words, max_gap, min_shared, d_works, ix->stream));
+  FS_TRY(job.count(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, min_words, max_gap,
+                   min_shared, d_works, ix->stream));
   *n_pairs = job.n_pairs;
   if (job.n_pairs > cap) return FS_E_CAPACITY;
   return job.write(d_pairs, ix->stream);

@@ -54,6 +54,15 @@ __device__ inline void tile_prefix(const uint64_t* __restrict__ mask, uint64_t n
   __syncthreads();
 }
 
+// the three key columns of records that never were fs_row records (fs_readings.hip)
+struct KeyCols {
+  const uint32_t* work;
+  const uint32_t* fan;
+  const uint32_t* orig;
+  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
+};
+
+// Src: RowsSrc or KeyCols (the one kernel compiled for both)
 template <class Src>
 __global__ __launch_bounds__(kBlock) void k_pass_heads(Src src, uint32_t n, int64_t g1,
                                                        uint64_t* __restrict__ mask,
@@ -159,8 +168,7 @@ __device__ inline double lane_value(double v, uint32_t t) {
 }
 
 // records [b, e) by one lane, eight loads in flight ahead of their adds
-template <class Src>
-__device__ inline Acc lane_walk(const Src& src, uint64_t b, uint64_t e) {
+__device__ inline Acc lane_walk(const RowsSrc& src, uint64_t b, uint64_t e) {
   Acc a = acc_init();
   uint64_t i = b;
   for (; i + 8 <= e; i += 8) {
@@ -179,8 +187,7 @@ __device__ inline Acc lane_walk(const Src& src, uint64_t b, uint64_t e) {
 
 // records [b, e) (wave-uniform bounds) by the whole wave: 64 records per load, the next 64
 // requested before the current ones are added; every lane adds all of them in record order
-template <class Src>
-__device__ inline Acc wave_walk(const Src& src, uint64_t b, uint64_t e, uint32_t lane) {
+__device__ inline Acc wave_walk(const RowsSrc& src, uint64_t b, uint64_t e, uint32_t lane) {
   Acc a = acc_init();
   double2 cur = b + lane < e ? src.val(b + lane) : make_double2(0.0, 0.0);
   for (uint64_t c = b; c < e; c += 64) {
@@ -193,8 +200,8 @@ __device__ inline Acc wave_walk(const Src& src, uint64_t b, uint64_t e, uint32_t
   return a;
 }
 
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_pass_reduce(Src src, const uint32_t* __restrict__ heads,
+__global__ __launch_bounds__(kBlock) void k_pass_reduce(RowsSrc src,
+                                                        const uint32_t* __restrict__ heads,
                                                         uint32_t n_runs,
                                                         const uint64_t* __restrict__ mask,
                                                         const uint32_t* __restrict__ off,
@@ -287,13 +294,25 @@ int pass_count(const Src& src, uint32_t n, uint32_t min_words, uint32_t max_gap,
   return FS_OK;
 }
 
-// the w.n_kept passages into d_out (queued on s)
-template <class Src>
-int pass_write(const Src& src, PassWork& w, fs_passage* d_out, hipStream_t s) {
-  if (!w.n_kept) return FS_OK;
-  hipLaunchKernelGGL(k_pass_reduce<Src>, dim3(tiles(w.n_runs)), dim3(kBlock), 0, s, src, w.heads.p,
-                     w.n_runs, w.mask2.p, w.cnt2.p, d_out);
-  FS_HIP(hipGetLastError());
+// Both entry points behind their checks: the kept passages of n records on `s`, into `out`
+// on the host (by way of a device buffer of the call's own) or into d_out on the device.
+int pass_run(const fs_row* d_rows, uint32_t n, uint32_t min_words, uint32_t max_gap,
+             fs_passage* out, fs_passage* d_out, uint64_t cap, uint64_t* n_out, hipStream_t s) {
+  PassWork w;
+  FS_TRY(pass_count(RowsSrc{d_rows}, n, min_words, max_gap, w, s));
+  *n_out = w.n_kept;
+  if (w.n_kept > cap) return FS_E_CAPACITY;
+  DBuf<fs_passage> d_own;
+  if (out) {
+    FS_TRY(d_own.reserve(w.n_kept));
+    d_out = d_own.p;
+  }
+  if (w.n_kept) {
+    hipLaunchKernelGGL(k_pass_reduce, dim3(tiles(w.n_runs)), dim3(kBlock), 0, s, RowsSrc{d_rows},
+                       w.heads.p, w.n_runs, w.mask2.p, w.cnt2.p, d_out);
+    FS_HIP(hipGetLastError());
+    if (out) FS_TRY(copy_out(out, d_own, w.n_kept));
+  }
   return FS_OK;
 }
 
@@ -320,19 +339,19 @@ int pass_check(uint64_t n_rows, uint32_t min_words, const void* out, uint64_t ca
 
 }  // namespace
 
-// The runs of records sorted by (work, fan_ix), exactly as the passages join them, for
-// fs_works.hip (declared in fs_internal.h): rows, or the three key columns when d_rows is null.
+// The runs of records sorted by (work, fan_ix), exactly as the passages join them, for the
+// other command units (declared in fs_internal.h).
 struct fs_runs {
   PassWork w;
 };
 
-int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d_fan,
-                 const uint32_t* d_orig, uint32_t n, uint32_t min_words, uint32_t max_gap,
-                 hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
+namespace {
+
+template <class Src>
+int runs_find(const Src& src, uint32_t n, uint32_t min_words, uint32_t max_gap, hipStream_t s,
+              fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
   fs_runs* r = new fs_runs;
-  const int rc = d_rows ? pass_count(RowsSrc{d_rows}, n, min_words, max_gap, r->w, s)
-                        : pass_count(ColsSrc{d_work, d_fan, d_orig}, n, min_words, max_gap, r->w,
-                                     s);
+  const int rc = pass_count(src, n, min_words, max_gap, r->w, s);
   if (rc != FS_OK) {
     delete r;
     return rc;
@@ -343,7 +362,71 @@ int fs_runs_find(const fs_row* d_rows, const uint32_t* d_work, const uint32_t* d
   return FS_OK;
 }
 
+// a record per thread; the doubles travel as their bits
+__global__ __launch_bounds__(kBlock) void k_rows_pack(const uint32_t* __restrict__ work,
+                                                      const uint32_t* __restrict__ fan,
+                                                      const uint32_t* __restrict__ orig,
+                                                      const uint2* __restrict__ dist,
+                                                      const uint2* __restrict__ comb,
+                                                      const uint8_t* __restrict__ exact, uint32_t n,
+                                                      fs_row* __restrict__ rows) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint2 d = dist ? dist[i] : make_uint2(0u, 0u);
+  uint2 c = comb ? comb[i] : make_uint2(0u, 0u);
+  if (exact) c.y = exact[i] ? 0u : 0x3FF00000u;              // 0.0 : 1.0
+  uint4* o = reinterpret_cast<uint4*>(rows + i);
+  o[0] = make_uint4(work[i], fan[i], orig[i], 0u);
+  o[1] = make_uint4(d.x, d.y, c.x, c.y);
+}
+
+}  // namespace
+
+int fs_runs_find(const fs_row* d_rows, uint32_t n, uint32_t min_words, uint32_t max_gap,
+                 hipStream_t s, fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
+  return runs_find(RowsSrc{d_rows}, n, min_words, max_gap, s, runs, d_heads, n_runs);
+}
+
+int fs_runs_find_cols(const uint32_t* d_work, const uint32_t* d_fan, const uint32_t* d_orig,
+                      uint32_t n, uint32_t min_words, uint32_t max_gap, hipStream_t s,
+                      fs_runs** runs, const uint32_t** d_heads, uint32_t* n_runs) {
+  return runs_find(KeyCols{d_work, d_fan, d_orig}, n, min_words, max_gap, s, runs, d_heads,
+                   n_runs);
+}
+
 void fs_runs_free(fs_runs* r) { delete r; }
+
+int fs_host_rows(DBuf<fs_row>& rows, const uint32_t* work, const uint32_t* fan,
+                 const uint32_t* orig, size_t n, const double* dist, const double* comb,
+                 const uint8_t* exact) {
+  // one staging buffer: the 8-byte columns first, then the 4-byte ones, then the flags
+  const size_t nd = dist ? n : 0, nc = comb ? n : 0, ne = exact ? n : 0;
+  DBuf<unsigned char> stage;
+  FS_TRY(stage.reserve((nd + nc) * sizeof(double) + 3 * n * sizeof(uint32_t) + ne));
+  double* d_dist = reinterpret_cast<double*>(stage.p);
+  double* d_comb = d_dist + nd;
+  uint32_t* d_work = reinterpret_cast<uint32_t*>(d_comb + nc);
+  uint32_t *d_fan = d_work + n, *d_orig = d_fan + n;
+  uint8_t* d_exact = reinterpret_cast<uint8_t*>(d_orig + n);
+  const auto up = [](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, nullptr) : hipSuccess;
+  };
+  FS_HIP(up(d_work, work, n * sizeof(uint32_t)));
+  FS_HIP(up(d_fan, fan, n * sizeof(uint32_t)));
+  FS_HIP(up(d_orig, orig, n * sizeof(uint32_t)));
+  FS_HIP(up(d_dist, dist, nd * sizeof(double)));
+  FS_HIP(up(d_comb, comb, nc * sizeof(double)));
+  FS_HIP(up(d_exact, exact, ne));
+  FS_TRY(rows.reserve(n));
+  if (n) {
+    hipLaunchKernelGGL(k_rows_pack, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, nullptr, d_work,
+                       d_fan, d_orig, nd ? reinterpret_cast<const uint2*>(d_dist) : nullptr,
+                       nc ? reinterpret_cast<const uint2*>(d_comb) : nullptr,
+                       ne ? d_exact : nullptr, (uint32_t)n, rows.p);
+    FS_HIP(hipGetLastError());
+  }
+  return FS_OK;                     // `stage` is freed here, behind the kernel that reads it
+}
 
 extern "C" int fs_passages(int device, const uint32_t* work, const uint32_t* fan_ix,
                            const uint32_t* orig_ix, const double* dist, const double* comb,
@@ -357,18 +440,9 @@ extern "C" int fs_passages(int device, const uint32_t* work, const uint32_t* fan
     return FS_E_INVALID;
   }
   FS_ENTER(device);
-  const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, dist, comb));
-  const ColsSrc src = cols.src();
-  PassWork w;
-  FS_TRY(pass_count(src, n, min_words, max_gap, w, nullptr));
-  *n_out = w.n_kept;
-  if (w.n_kept > cap) return FS_E_CAPACITY;
-  DBuf<fs_passage> d_out;
-  FS_TRY(d_out.reserve(w.n_kept));
-  FS_TRY(pass_write(src, w, d_out.p, nullptr));
-  if (w.n_kept) FS_TRY(copy_out(out, d_out, w.n_kept));
+  DBuf<fs_row> rows;
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n_rows, dist, comb));
+  FS_TRY(pass_run(rows.p, (uint32_t)n_rows, min_words, max_gap, out, nullptr, cap, n_out, nullptr));
   FS_HIP(hipDeviceSynchronize());
   return FS_OK;
 }
@@ -388,12 +462,8 @@ extern "C" int fs_passages_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_r
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
-  PassWork w;
-  FS_TRY(pass_count(src, (uint32_t)n_rows, min_words, max_gap, w, ix->stream));
-  *n_out = w.n_kept;
-  if (w.n_kept > cap) return FS_E_CAPACITY;
-  FS_TRY(pass_write(src, w, d_out, ix->stream));
+  FS_TRY(pass_run(d_rows, (uint32_t)n_rows, min_words, max_gap, nullptr, d_out, cap, n_out,
+                  ix->stream));
   FS_HIP(hipStreamSynchronize(ix->stream));
   return FS_OK;
 }

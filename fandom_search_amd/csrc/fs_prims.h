@@ -1,7 +1,9 @@
 // fs_prims.h -- what the command units (fs_passages.hip ... fs_companions.hip, fs_matches.hip,
 // fs_tiles.h) share: wave reductions and scans, workgroup scans and ranks, the one-workgroup
-// chunked scan, the two views of the match records, and the host's pass clock and environment
-// bounds.  A command unit takes its scans, ranks, wave reductions and record views from here.
+// chunked scan, the view of the match records, and the host's pass clock, environment bounds
+// and record limits.  A command unit takes its scans, ranks and wave reductions from here and
+// reads its records through RowsSrc: fs_row records in device memory, whether a search left
+// them there or fs_host_rows (fs_internal.h) packed them from the columns a caller passed.
 // Everything is integer arithmetic: no schedule changes a result.  (The search path keeps its
 // own DPP versions in fs_device.h.)
 #pragma once
@@ -167,7 +169,7 @@ __device__ inline void scan_array(const In* in, uint64_t n, Out* out, T* total) 
   if (threadIdx.x == 0) *total = sum;
 }
 
-// ---- the match records: fs_row records, or the columns a caller passed ----
+// ---- the match records ----
 
 // the key half {work, fan_ix, orig_ix, lev} and the value half {dist, comb}, one 16-byte load
 // each (rows are 16-byte aligned, 32 bytes apart)
@@ -176,18 +178,6 @@ struct RowsSrc {
   __device__ uint4 key(uint64_t i) const { return reinterpret_cast<const uint4*>(rows + i)[0]; }
   __device__ double2 val(uint64_t i) const { return reinterpret_cast<const double2*>(rows + i)[1]; }
   __device__ double comb(uint64_t i) const { return rows[i].comb; }
-};
-
-// dist and cmb are null where a command has no such column
-struct ColsSrc {
-  const uint32_t* work;
-  const uint32_t* fan;
-  const uint32_t* orig;
-  const double* dist = nullptr;
-  const double* cmb = nullptr;
-  __device__ uint4 key(uint64_t i) const { return make_uint4(work[i], fan[i], orig[i], 0); }
-  __device__ double2 val(uint64_t i) const { return make_double2(dist[i], cmb[i]); }
-  __device__ double comb(uint64_t i) const { return cmb[i]; }
 };
 
 // ---- host (internal linkage: the library exports none of these) ----
@@ -231,24 +221,7 @@ struct Clock {
   }
 };
 
-// ---- what the entry points over host columns share ----
-
-// the record columns of a host entry point on the device: uploaded on the null stream in the
-// order work, fan, orig, dist, comb, the last two only where the command passes them
-struct HostCols {
-  DBuf<uint32_t> work, fan, orig;
-  DBuf<double> dist, comb;
-  int upload(const uint32_t* h_work, const uint32_t* h_fan, const uint32_t* h_orig, size_t n,
-             const double* h_dist = nullptr, const double* h_comb = nullptr) {
-    FS_TRY(work.upload(h_work, n, nullptr));
-    FS_TRY(fan.upload(h_fan, n, nullptr));
-    FS_TRY(orig.upload(h_orig, n, nullptr));
-    if (h_dist) FS_TRY(dist.upload(h_dist, n, nullptr));
-    if (h_comb) FS_TRY(comb.upload(h_comb, n, nullptr));
-    return FS_OK;
-  }
-  ColsSrc src() const { return ColsSrc{work.p, fan.p, orig.p, dist.p, comb.p}; }
-};
+// ---- what the entry points share ----
 
 // the first n records of a device buffer to the host, when the device is done with them
 template <class T>

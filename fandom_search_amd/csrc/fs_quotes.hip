@@ -67,8 +67,7 @@ struct QuotesArgs {
 };
 
 // one lane per run
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_quotes_runs(Src src, QuotesArgs a) {
+__global__ __launch_bounds__(kRunBlock) void k_quotes_runs(RowsSrc src, QuotesArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   bool bad = false;
@@ -112,8 +111,8 @@ __device__ inline uint32_t run_from(const QuotesArgs& a, uint64_t i) {
 
 // What a kept run covers, as an inclusive range of bits: script words (kLevel 0), or the ids of
 // the regions its span intersects (kLevel 1: contiguous; none when lo > hi).
-template <class Src, int kLevel>
-__device__ inline bool run_range(const Src& src, const QuotesArgs& a, uint32_t r, int64_t* lo,
+template <int kLevel>
+__device__ inline bool run_range(const RowsSrc& src, const QuotesArgs& a, uint32_t r, int64_t* lo,
                                  int64_t* hi) {
   const uint32_t h = a.heads[r], e = a.heads[r + 1];
   if (e - h < a.min_words) return false;
@@ -132,12 +131,12 @@ __device__ inline bool run_range(const Src& src, const QuotesArgs& a, uint32_t r
 
 // The ranges of runs [rs, re) into the bitmap `bm` (LDS or a global merge area), a word of bits
 // at a time, one lane per run; every bit found clear adds 1 to its counter cnt[bit * stride].
-template <class Src, int kLevel>
-__device__ inline void mark_runs(const Src& src, const QuotesArgs& a, uint32_t rs, uint32_t re,
+template <int kLevel>
+__device__ inline void mark_runs(const RowsSrc& src, const QuotesArgs& a, uint32_t rs, uint32_t re,
                                  uint32_t* bm, uint32_t* cnt, uint32_t stride) {
   for (uint64_t r = (uint64_t)rs + threadIdx.x; r < re; r += kWave) {
     int64_t lo, hi;
-    if (!run_range<Src, kLevel>(src, a, (uint32_t)r, &lo, &hi)) continue;
+    if (!run_range<kLevel>(src, a, (uint32_t)r, &lo, &hi)) continue;
     const uint32_t k0 = (uint32_t)(lo >> 5), k1 = (uint32_t)(hi >> 5);
     for (uint32_t k = k0; k <= k1; ++k) {
       uint32_t m = 0xFFFFFFFFu;
@@ -150,12 +149,12 @@ __device__ inline void mark_runs(const Src& src, const QuotesArgs& a, uint32_t r
 }
 
 // the bitmap words those runs touched, cleared again
-template <class Src, int kLevel>
-__device__ inline void unmark_runs(const Src& src, const QuotesArgs& a, uint32_t rs, uint32_t re,
-                                   uint32_t* bm) {
+template <int kLevel>
+__device__ inline void unmark_runs(const RowsSrc& src, const QuotesArgs& a, uint32_t rs,
+                                   uint32_t re, uint32_t* bm) {
   for (uint64_t r = (uint64_t)rs + threadIdx.x; r < re; r += kWave) {
     int64_t lo, hi;
-    if (!run_range<Src, kLevel>(src, a, (uint32_t)r, &lo, &hi)) continue;
+    if (!run_range<kLevel>(src, a, (uint32_t)r, &lo, &hi)) continue;
     for (uint32_t k = (uint32_t)(lo >> 5); k <= (uint32_t)(hi >> 5); ++k) bm[k] = 0;
   }
 }
@@ -163,9 +162,9 @@ __device__ inline void unmark_runs(const Src& src, const QuotesArgs& a, uint32_t
 // Records [b, e) (wave-uniform) into the LDS bitmap `bm`: n_words and n_exact of their script
 // words by atomics.  kFirst: a bit found clear adds 1 to the word's n_works (a work of one
 // wave); otherwise the bitmap is merged afterwards.  *bad |= an orig_ix outside the script.
-template <class Src, bool kFirst>
-__device__ inline void add_records(const Src& src, const QuotesArgs& a, uint32_t* bm, uint64_t b,
-                                   uint64_t e, bool* bad) {
+template <bool kFirst>
+__device__ inline void add_records(const RowsSrc& src, const QuotesArgs& a, uint32_t* bm,
+                                   uint64_t b, uint64_t e, bool* bad) {
   uint32_t* __restrict__ cnt = reinterpret_cast<uint32_t*>(a.words);
   for (uint64_t c = b; c < e; c += kDepth * kWave) {
     uint32_t os[kDepth];
@@ -198,8 +197,8 @@ __device__ inline void add_records(const Src& src, const QuotesArgs& a, uint32_t
 extern __shared__ uint32_t s_quotes[];
 
 // a wave per slice of records: the parts of large works inside it
-template <class Src, int kLevel>
-__global__ __launch_bounds__(kWave) void k_quotes_slices(Src src, QuotesArgs a) {
+template <int kLevel>
+__global__ __launch_bounds__(kWave) void k_quotes_slices(RowsSrc src, QuotesArgs a) {
   const uint32_t lane = threadIdx.x;
   if (kLevel == 0) {
     for (uint32_t k = lane; k < a.bw; k += kWave) s_quotes[k] = 0;
@@ -219,7 +218,7 @@ __global__ __launch_bounds__(kWave) void k_quotes_slices(Src src, QuotesArgs a) 
     const uint32_t rs = run_from(a, b), re = run_from(a, e);   // runs whose head is in [b, e)
     if (kLevel == 0) {
       uint32_t* __restrict__ g = a.area + (size_t)(ws / a.slice) * 2 * a.bw;
-      add_records<Src, false>(src, a, s_quotes, b, e, &bad);
+      add_records<false>(src, a, s_quotes, b, e, &bad);
       __syncthreads();
       uint32_t* __restrict__ cnt = reinterpret_cast<uint32_t*>(a.words);
       for (uint32_t k = lane; k < a.bw; k += kWave) {
@@ -229,10 +228,10 @@ __global__ __launch_bounds__(kWave) void k_quotes_slices(Src src, QuotesArgs a) 
         for (uint32_t nb = v & ~atomicOr(&g[k], v); nb; nb &= nb - 1)
           atomicAdd(&cnt[(size_t)(k * 32 + (uint32_t)__builtin_ctz(nb)) * kWordU32 + kWNWorks], 1u);
       }
-      mark_runs<Src, 0>(src, a, rs, re, g + a.bw, cnt + kWNPassageWorks, kWordU32);
+      mark_runs<0>(src, a, rs, re, g + a.bw, cnt + kWNPassageWorks, kWordU32);
       __syncthreads();
     } else {
-      mark_runs<Src, 1>(src, a, rs, re, a.rarea + (size_t)(ws / a.slice) * a.rbw,
+      mark_runs<1>(src, a, rs, re, a.rarea + (size_t)(ws / a.slice) * a.rbw,
                         reinterpret_cast<uint32_t*>(a.regions) + kRNWorks, kRegionU32);
     }
   }
@@ -240,8 +239,8 @@ __global__ __launch_bounds__(kWave) void k_quotes_slices(Src src, QuotesArgs a) 
 }
 
 // a wave per a.per_wave works
-template <class Src, int kLevel>
-__global__ __launch_bounds__(kWave) void k_quotes_each(Src src, QuotesArgs a) {
+template <int kLevel>
+__global__ __launch_bounds__(kWave) void k_quotes_each(RowsSrc src, QuotesArgs a) {
   const uint32_t lane = threadIdx.x;
   const uint32_t lds_words = kLevel ? a.rbw : 2 * a.bw;
   for (uint32_t k = lane; k < lds_words; k += kWave) s_quotes[k] = 0;
@@ -254,11 +253,11 @@ __global__ __launch_bounds__(kWave) void k_quotes_each(Src src, QuotesArgs a) {
     if (nw == 0 || nw > a.slice) continue;           // none, or k_quotes_slices' work
     const uint32_t rs = run_from(a, ws), re = run_from(a, we);
     if (kLevel == 0) {
-      add_records<Src, true>(src, a, s_quotes, ws, we, &bad);
-      mark_runs<Src, 0>(src, a, rs, re, s_quotes + a.bw,
+      add_records<true>(src, a, s_quotes, ws, we, &bad);
+      mark_runs<0>(src, a, rs, re, s_quotes + a.bw,
                         reinterpret_cast<uint32_t*>(a.words) + kWNPassageWorks, kWordU32);
     } else {
-      mark_runs<Src, 1>(src, a, rs, re, s_quotes,
+      mark_runs<1>(src, a, rs, re, s_quotes,
                         reinterpret_cast<uint32_t*>(a.regions) + kRNWorks, kRegionU32);
     }
     if (w + 1 == w1) break;
@@ -268,9 +267,9 @@ __global__ __launch_bounds__(kWave) void k_quotes_each(Src src, QuotesArgs a) {
         const uint32_t o = src.key(i).z;
         if (o < a.n_script) s_quotes[o >> 5] = 0;
       }
-      unmark_runs<Src, 0>(src, a, rs, re, s_quotes + a.bw);
+      unmark_runs<0>(src, a, rs, re, s_quotes + a.bw);
     } else {
-      unmark_runs<Src, 1>(src, a, rs, re, s_quotes);
+      unmark_runs<1>(src, a, rs, re, s_quotes);
     }
     __syncthreads();
   }
@@ -454,14 +453,7 @@ int quotes_check(uint64_t n_rows, uint32_t n_script, uint32_t min_words, uint32_
     fs_set_error("min_words and min_works must be at least 1");
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: quotes take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: quotes take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("quotes", n_rows, n_script));
   *n_regions = 0;
   *done = n_rows == 0;
   return FS_OK;
@@ -485,12 +477,11 @@ int lds_allow(K kernel, size_t lds) {
 }
 
 // d_words written and *n_regions set; d_regions too unless FS_E_CAPACITY (all on `s`, finished
-// on return).  The records are `src`: d_rows, or the columns `cols`.
-template <class Src>
-int quotes_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-               uint32_t n_works, uint32_t n_script, uint32_t min_words, uint32_t max_gap,
-               uint32_t min_works, fs_quote_word* d_words, fs_quote_region* d_regions,
-               uint64_t cap, uint64_t* n_regions, hipStream_t s) {
+// on return).
+int quotes_run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+               uint32_t min_words, uint32_t max_gap, uint32_t min_works, fs_quote_word* d_words,
+               fs_quote_region* d_regions, uint64_t cap, uint64_t* n_regions, hipStream_t s) {
+  const RowsSrc src{d_rows};
   if (!n) {
     if (n_script)
       hipLaunchKernelGGL(k_quotes_none, dim3((n_script + kRunBlock - 1) / kRunBlock),
@@ -516,8 +507,7 @@ int quotes_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32
   while (a.slice < 2 * (size_t)a.bw + a.bw / 2 + 1) a.slice *= 2;
   const uint32_t tiles = (uint32_t)(((uint64_t)n + a.slice - 1) / a.slice);
 
-  FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &k.runs,
-                      &a.heads, &a.n_runs));
+  FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &k.runs, &a.heads, &a.n_runs));
   if (!n_works || !n_script) return quotes_invalid();
 
   FS_TRY(k.wstart.reserve(n_works));
@@ -547,13 +537,13 @@ int quotes_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32
   a.regions = d_regions;
 
   const size_t lds_slices = (size_t)a.bw * sizeof(uint32_t), lds_each = 2 * lds_slices;
-  FS_TRY(lds_allow(&k_quotes_slices<Src, 0>, lds_slices));
-  FS_TRY(lds_allow(&k_quotes_each<Src, 0>, lds_each));
+  FS_TRY(lds_allow(&k_quotes_slices<0>, lds_slices));
+  FS_TRY(lds_allow(&k_quotes_each<0>, lds_each));
   const uint32_t each_blocks = (n_works + a.per_wave - 1) / a.per_wave;
-  hipLaunchKernelGGL(k_quotes_runs<Src>, dim3((a.n_runs + kRunBlock - 1) / kRunBlock),
+  hipLaunchKernelGGL(k_quotes_runs, dim3((a.n_runs + kRunBlock - 1) / kRunBlock),
                      dim3(kRunBlock), 0, s, src, a);
-  hipLaunchKernelGGL((k_quotes_slices<Src, 0>), dim3(tiles), dim3(kWave), lds_slices, s, src, a);
-  hipLaunchKernelGGL((k_quotes_each<Src, 0>), dim3(each_blocks), dim3(kWave), lds_each, s, src, a);
+  hipLaunchKernelGGL((k_quotes_slices<0>), dim3(tiles), dim3(kWave), lds_slices, s, src, a);
+  hipLaunchKernelGGL((k_quotes_each<0>), dim3(each_blocks), dim3(kWave), lds_each, s, src, a);
   hipLaunchKernelGGL(k_quotes_scan, dim3(1), dim3(kScanBlock), 0, s, a);
   FS_HIP(hipGetLastError());
   uint32_t st[2];
@@ -570,13 +560,13 @@ int quotes_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32
   FS_HIP(hipMemsetAsync(k.rarea.p, 0, (size_t)tiles * a.rbw * sizeof(uint32_t), s));
   a.rarea = k.rarea.p;
   const size_t lds_regions = (size_t)a.rbw * sizeof(uint32_t);
-  FS_TRY(lds_allow(&k_quotes_each<Src, 1>, lds_regions));
+  FS_TRY(lds_allow(&k_quotes_each<1>, lds_regions));
   hipLaunchKernelGGL(k_quotes_fill, dim3((n_script + kRunBlock - 1) / kRunBlock), dim3(kRunBlock),
                      0, s, a);
   hipLaunchKernelGGL(k_quotes_reduce, dim3((a.n_regions + kRunBlock - 1) / kRunBlock),
                      dim3(kRunBlock), 0, s, a);
-  hipLaunchKernelGGL((k_quotes_slices<Src, 1>), dim3(tiles), dim3(kWave), 0, s, src, a);
-  hipLaunchKernelGGL((k_quotes_each<Src, 1>), dim3(each_blocks), dim3(kWave), lds_regions, s, src,
+  hipLaunchKernelGGL((k_quotes_slices<1>), dim3(tiles), dim3(kWave), 0, s, src, a);
+  hipLaunchKernelGGL((k_quotes_each<1>), dim3(each_blocks), dim3(kWave), lds_regions, s, src,
                      a);
   FS_HIP(hipGetLastError());
   FS_HIP(hipStreamSynchronize(s));
@@ -608,15 +598,14 @@ extern "C" int fs_quotes(int device, const uint32_t* work, const uint32_t* fan_i
   // regions never outnumber half the script's words (a word apart at least) nor the records
   uint64_t most = ((uint64_t)n_script + 1) / 2;
   if (most > n_rows) most = n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_quote_word> d_words;
   DBuf<fs_quote_region> d_regions;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, nullptr, comb));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n, nullptr, comb));
   FS_TRY(d_words.reserve(n_script));
   FS_TRY(d_regions.reserve(cap < most ? cap : most));
-  const ColsSrc src = cols.src();
-  const int rc = quotes_run(src, nullptr, src, n, n_works, n_script, min_words, max_gap, min_works,
-                            d_words.p, d_regions.p, cap, n_regions, nullptr);
+  const int rc = quotes_run(rows.p, n, n_works, n_script, min_words, max_gap, min_works, d_words.p,
+                            d_regions.p, cap, n_regions, nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
   FS_TRY(copy_out(words, d_words, n_script));
   if (rc == FS_OK && *n_regions) FS_TRY(copy_out(regions, d_regions, *n_regions));
@@ -646,7 +635,6 @@ extern "C" int fs_quotes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_row
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
-  return quotes_run(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                    min_words, max_gap, min_works, d_words, d_regions, cap, n_regions, ix->stream);
+  return quotes_run(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, min_words, max_gap,
+                    min_works, d_words, d_regions, cap, n_regions, ix->stream);
 }

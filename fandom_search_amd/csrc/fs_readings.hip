@@ -360,15 +360,17 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   if (!n_works || !n_script || !n_spell) return invalid();
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
-  DBuf<uint32_t> d_spell, d_status;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  // raw columns, not fs_row records: the passes below read one column each
+  DBuf<uint32_t> d_work, d_fan, d_orig, d_spell, d_status;
+  FS_TRY(d_work.upload(work, n, nullptr));
+  FS_TRY(d_fan.upload(fan_ix, n, nullptr));
+  FS_TRY(d_orig.upload(orig_ix, n, nullptr));
   FS_TRY(d_spell.upload(spell, n, nullptr));
   FS_TRY(d_status.reserve(4));
   FS_HIP(hipMemsetAsync(d_status.p, 0, 4 * sizeof(uint32_t), nullptr));
   RdArgs a{};
-  a.work = cols.work.p;
-  a.orig = cols.orig.p;
+  a.work = d_work.p;
+  a.orig = d_orig.p;
   a.spell = d_spell.p;
   a.n = n;
   a.n_works = n_works;
@@ -382,8 +384,8 @@ extern "C" int fs_readings(int device, const uint32_t* work, const uint32_t* fan
   hipLaunchKernelGGL(k_rd_check, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, nullptr, a);
   FS_HIP(hipGetLastError());
   RunsGuard runs;
-  FS_TRY(fs_runs_find(nullptr, cols.work.p, cols.fan.p, cols.orig.p, n, min_words, max_gap, nullptr, &runs.r,
-                      &a.heads, &a.n_runs));
+  FS_TRY(fs_runs_find_cols(d_work.p, d_fan.p, d_orig.p, n, min_words, max_gap, nullptr, &runs.r,
+                           &a.heads, &a.n_runs));
   uint32_t st[2];
   FS_HIP(hipMemcpy(st, d_status.p, sizeof st, hipMemcpyDeviceToHost));
   if (st[0]) return invalid();

@@ -69,8 +69,7 @@ struct RtArgs {
   fs_retelling_passage* passages;
 };
 
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_rt_check(Src src, RtArgs a) {
+__global__ __launch_bounds__(kBlock) void k_rt_check(RowsSrc src, RtArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const bool bad = i < a.n && src.key(i).x >= a.n_works;
   if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.status[kStBad], 1u);
@@ -85,8 +84,8 @@ __global__ __launch_bounds__(kScanBlock) void k_rt_scan(const uint32_t* in, uint
 
 // kPlace false: kept runs of this workgroup's 256 runs into cnt; true: the kept runs to their
 // places, cnt holding the scan
-template <class Src, bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_rt_kept(Src src, RtArgs a) {
+template <bool kPlace>
+__global__ __launch_bounds__(kBlock) void k_rt_kept(RowsSrc src, RtArgs a) {
   __shared__ uint32_t s_w[kBlock / 64];
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   uint32_t b = 0, e = 0;
@@ -326,13 +325,13 @@ int rt_invalid() {
 }
 
 // d_out written and *n_passages set; d_passages too unless FS_E_CAPACITY (all on `s`, finished
-// on return).  The records are `src`: d_rows, or the columns `cols`.
-template <class Src>
-int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n, uint32_t n_works,
-           uint32_t min_words, uint32_t max_gap, fs_retelling* d_out,
-           fs_retelling_passage* d_passages, uint64_t cap, uint64_t* n_passages, hipStream_t s) {
+// on return).
+int rt_run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t min_words, uint32_t max_gap,
+           fs_retelling* d_out, fs_retelling_passage* d_passages, uint64_t cap,
+           uint64_t* n_passages, hipStream_t s) {
   for (double& t : t_ms) t = 0.0;
   if (n && !n_works) return rt_invalid();
+  const RowsSrc src{d_rows};
   const dim3 blk(kBlock), work_grid(blocks_of(n_works, kBlock));
   const auto none = [&]() -> int {
     if (n_works) hipLaunchKernelGGL(k_rt_none, work_grid, blk, 0, s, d_out, n_works);
@@ -358,10 +357,9 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   FS_HIP(hipMemsetAsync(k.status.p, 0, kStWords * sizeof(uint32_t), s));
   a.status = k.status.p;
   FS_TRY(clk.mark(0, s));
-  hipLaunchKernelGGL((k_rt_check<Src>), dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
+  hipLaunchKernelGGL(k_rt_check, dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
   FS_HIP(hipGetLastError());
-  FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &k.runs,
-                      &a.heads, &a.n_runs));
+  FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &k.runs, &a.heads, &a.n_runs));
   uint32_t st[kStWords];
   FS_HIP(hipMemcpyAsync(st, k.status.p, sizeof st, hipMemcpyDeviceToHost, s));
   FS_HIP(hipStreamSynchronize(s));
@@ -371,7 +369,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   const uint32_t run_blocks = blocks_of(a.n_runs, kBlock);
   FS_TRY(k.cnt.reserve(run_blocks));
   a.cnt = k.cnt.p;
-  hipLaunchKernelGGL((k_rt_kept<Src, false>), dim3(run_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_rt_kept<false>), dim3(run_blocks), blk, 0, s, src, a);
   hipLaunchKernelGGL(k_rt_scan, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.cnt, run_blocks,
                      a.status + kStTotal);
   FS_HIP(hipGetLastError());
@@ -404,7 +402,7 @@ int rt_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n
   a.bcnt = k.bcnt.p;
   a.list = k.list.p;
   FS_HIP(hipMemsetAsync(a.cpos, 0, np * sizeof(uint32_t), s));
-  hipLaunchKernelGGL((k_rt_kept<Src, true>), dim3(run_blocks), blk, 0, s, src, a);
+  hipLaunchKernelGGL((k_rt_kept<true>), dim3(run_blocks), blk, 0, s, src, a);
   hipLaunchKernelGGL(k_rt_offsets, dim3(blocks_of((uint64_t)n_works + 1, kBlock)), blk, 0, s, a);
   FS_HIP(hipGetLastError());
   FS_TRY(clk.mark(1, s));
@@ -468,16 +466,15 @@ extern "C" int fs_retellings(int device, const uint32_t* work, const uint32_t* f
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<fs_retelling> d_out;
   DBuf<fs_retelling_passage> d_pass;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_out.reserve(n_works));
   const uint64_t most = n_rows / min_words;                  // passages never outnumber this
   FS_TRY(d_pass.reserve(cap < most ? cap : most));
-  const ColsSrc src = cols.src();
-  const int rc = rt_run(src, nullptr, src, n, n_works, min_words, max_gap, d_out.p, d_pass.p, cap,
-                        n_passages, nullptr);
+  const int rc = rt_run(rows.p, n, n_works, min_words, max_gap, d_out.p, d_pass.p, cap, n_passages,
+                        nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
   if (n_works) FS_TRY(copy_out(out, d_out, n_works));
   if (rc == FS_OK && *n_passages) FS_TRY(copy_out(passages, d_pass, *n_passages));
@@ -500,9 +497,8 @@ extern "C" int fs_retellings_rows(fs_index* ix, const fs_row* d_rows, uint64_t n
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
-  return rt_run(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, min_words, max_gap, d_out,
-                d_passages, cap, n_passages, ix->stream);
+  return rt_run(d_rows, (uint32_t)n_rows, n_works, min_words, max_gap, d_out, d_passages, cap,
+                n_passages, ix->stream);
 }
 
 extern "C" int fs_retellings_times(double* ms) {

@@ -48,6 +48,8 @@ constexpr uint32_t kMaxK = FS_SOURCES_MAX_FILES;
 constexpr uint32_t kMaxPairs = kMaxK * (kMaxK - 1) / 2;
 constexpr uint32_t kGroups = 1024;          // workgroups of a pass that keeps figures in LDS
 constexpr uint32_t kCols = 9;               // passage columns
+// what the FS_SOURCES_MAX_BYTES refusal counts (include/fandom_search.h); a record of the file
+// at hand is an fs_row of 32 bytes, with its 28 bytes of columns beside it while it is packed
 constexpr uint64_t kRecordBytes = 28, kWorkBytes = 12, kPassageBytes = 160, kRowBytes = 56;
 
 static_assert(sizeof(fs_source_cols) == 40 && sizeof(fs_source_passage) == 80 &&
@@ -94,10 +96,10 @@ __host__ __device__ inline uint32_t pair_ix(uint32_t a, uint32_t b, uint32_t K) 
   return a * (2 * K - a - 1) / 2 + (b - a - 1);
 }
 
-__global__ __launch_bounds__(kBlock) void k_src_check(ColsSrc src, uint32_t n, uint32_t n_works,
+__global__ __launch_bounds__(kBlock) void k_src_check(RowsSrc src, uint32_t n, uint32_t n_works,
                                                       uint32_t* status) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  const bool bad = i < n && src.work[i] >= n_works;
+  const bool bad = i < n && src.key(i).x >= n_works;
   if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&status[kStBadRecord], 1u);
 }
 
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(kScanBlock) void k_src_scan(uint32_t* v, uint32_t n
 // kPlace false: the kept runs of this workgroup's 256 runs into cnt; true: those runs to their
 // places as columns [kCols][m] at `cols`, cnt holding the scan
 template <bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_src_seq(ColsSrc src, const uint32_t* heads,
+__global__ __launch_bounds__(kBlock) void k_src_seq(RowsSrc src, const uint32_t* heads,
                                                     uint32_t n_runs, uint32_t min_words,
                                                     uint32_t script, uint32_t* cnt, uint32_t* cols,
                                                     uint32_t m) {
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_src_seq(ColsSrc src, const uint32_t*
     if (p >= m) return;                               // (never: the counts placed m)
     const uint4 x = src.key(b), y = src.key(e - 1);
     uint32_t exact = 0;
-    for (uint32_t i = b; i < e; ++i) exact += src.cmb[i] <= 0.0 ? 1u : 0u;
+    for (uint32_t i = b; i < e; ++i) exact += src.comb(i) <= 0.0 ? 1u : 0u;
     cols[p] = script;
     cols[(size_t)m + p] = x.x;
     cols[(size_t)2 * m + p] = x.y;
@@ -486,8 +488,8 @@ extern "C" int fs_sources(int device, const fs_source_cols* files, uint32_t n_fi
   SrcArgs a{};
   a.K = K;
   a.n_works = n_works;
-  DBuf<uint32_t> status, d_work, d_fan, d_orig, cnt;
-  DBuf<double> d_comb;
+  DBuf<uint32_t> status, cnt;
+  DBuf<fs_row> rows;
   std::vector<DBuf<uint32_t>> part(K);
   FS_TRY(status.reserve(kStWords));
   FS_TRY(clk.mark(0, st));
@@ -497,12 +499,9 @@ extern "C" int fs_sources(int device, const fs_source_cols* files, uint32_t n_fi
     const uint32_t n = (uint32_t)files[s].n;
     a.off[s + 1] = a.off[s];
     if (!n) continue;
-    FS_TRY(d_work.upload(files[s].work, n, st));
-    FS_TRY(d_fan.upload(files[s].fan_ix, n, st));
-    FS_TRY(d_orig.upload(files[s].orig_ix, n, st));
-    FS_TRY(d_comb.upload(files[s].comb, n, st));
-    ColsSrc src{d_work.p, d_fan.p, d_orig.p};
-    src.cmb = d_comb.p;
+    FS_TRY(fs_host_rows(rows, files[s].work, files[s].fan_ix, files[s].orig_ix, n, nullptr,
+                        files[s].comb));
+    const RowsSrc src{rows.p};
     FS_HIP(hipMemsetAsync(status.p, 0, kStWords * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_src_check, dim3(blocks_of(n, kBlock)), blk, 0, st, src, n, n_works,
                        status.p);
@@ -510,8 +509,7 @@ extern "C" int fs_sources(int device, const fs_source_cols* files, uint32_t n_fi
     RunsHold runs;
     const uint32_t* heads = nullptr;
     uint32_t n_runs = 0;
-    const int rc = fs_runs_find(nullptr, d_work.p, d_fan.p, d_orig.p, n, min_words, max_gap, st,
-                                &runs.r, &heads, &n_runs);
+    const int rc = fs_runs_find(rows.p, n, min_words, max_gap, st, &runs.r, &heads, &n_runs);
     if (rc != FS_OK) {
       if (rc == FS_E_INVALID) fs_set_error("file %u: records are not sorted by (work, fan_ix)", s);
       return rc;
@@ -544,7 +542,7 @@ extern "C" int fs_sources(int device, const fs_source_cols* files, uint32_t n_fi
     hipLaunchKernelGGL(k_src_seq<true>, dim3(run_blocks), blk, 0, st, src, heads, n_runs,
                        min_words, s, cnt.p, part[s].p, m);
     FS_HIP(hipGetLastError());
-    FS_HIP(hipStreamSynchronize(st));                   // the columns go before the next upload
+    FS_HIP(hipStreamSynchronize(st));                   // the records go before the next file's
   }
   const uint64_t P = a.off[K];
   a.P = P;

@@ -35,8 +35,7 @@ struct CoverArgs {
   uint32_t* status;             // [0] invalid input, [1] active works
 };
 
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_check(Src src, CoverArgs a) {
+__global__ __launch_bounds__(kRunBlock) void k_pairs_check(RowsSrc src, CoverArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   bool bad = false;
   if (i < a.n) {
@@ -47,8 +46,7 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_check(Src src, CoverArgs a)
 }
 
 // one lane per run (after k_pairs_check found nothing: every work and word is inside)
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_flag(Src src, CoverArgs a) {
+__global__ __launch_bounds__(kRunBlock) void k_pairs_flag(RowsSrc src, CoverArgs a) {
   const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   if (r >= a.n_runs) return;
   const uint32_t h = a.heads[r], e = a.heads[r + 1];
@@ -70,8 +68,7 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_list(CoverArgs a, const uin
   if (w < a.n_works && flag[w]) a.work_of[a.act[w]] = (uint32_t)w;
 }
 
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_pairs_cover(Src src, CoverArgs a,
+__global__ __launch_bounds__(kRunBlock) void k_pairs_cover(RowsSrc src, CoverArgs a,
                                                            const uint32_t* flag) {
   const uint64_t r = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   if (r >= a.n_runs) return;
@@ -154,11 +151,8 @@ struct CoverJob {
   // a.n_runs, a.act (the numbers; the flags stay in flag.p), a.status, a.n_active, a.n_tiles
   // and a.n_chunks set.  a.n, a.n_works, a.n_script, a.nk and a.min_words are the caller's;
   // a.n > 0.  Finished on return.
-  template <class Src>
-  int number(const Src& src, const fs_row* d_rows, const ColsSrc& cols, CoverArgs& a,
-             uint32_t max_gap, hipStream_t s) {
-    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, a.n, a.min_words, max_gap, s,
-                        &runs, &a.heads, &a.n_runs));
+  int number(const fs_row* d_rows, CoverArgs& a, uint32_t max_gap, hipStream_t s) {
+    FS_TRY(fs_runs_find(d_rows, a.n, a.min_words, max_gap, s, &runs, &a.heads, &a.n_runs));
     if (!a.n_works || !a.n_script) return invalid();
     FS_TRY(flag.reserve(a.n_works));
     FS_TRY(act.reserve(a.n_works));
@@ -167,11 +161,11 @@ struct CoverJob {
     FS_HIP(hipMemsetAsync(status.p, 0, 4 * sizeof(uint32_t), s));
     a.act = flag.p;                                  // k_pairs_flag writes the flags
     a.status = status.p;
+    const RowsSrc src{d_rows};
     const dim3 blk(kRunBlock);
-    hipLaunchKernelGGL(k_pairs_check<Src>, dim3((a.n + kRunBlock - 1) / kRunBlock), blk, 0, s,
-                       src, a);
-    hipLaunchKernelGGL(k_pairs_flag<Src>, dim3((a.n_runs + kRunBlock - 1) / kRunBlock), blk, 0, s,
-                       src, a);
+    hipLaunchKernelGGL(k_pairs_check, dim3((a.n + kRunBlock - 1) / kRunBlock), blk, 0, s, src, a);
+    hipLaunchKernelGGL(k_pairs_flag, dim3((a.n_runs + kRunBlock - 1) / kRunBlock), blk, 0, s, src,
+                       a);
     hipLaunchKernelGGL(k_pairs_scan<uint32_t>, dim3(1), dim3(kScanBlock), 0, s, flag.p,
                        (uint64_t)a.n_works, act.p, status.p + 1);
     FS_HIP(hipGetLastError());
@@ -201,13 +195,12 @@ struct CoverJob {
   }
 
   // the works of the active numbers, the matrix, the row popcounts (launched, not waited for)
-  template <class Src>
-  void cover(const Src& src, const CoverArgs& a, hipStream_t s) {
+  void cover(const fs_row* d_rows, const CoverArgs& a, hipStream_t s) {
     const dim3 blk(kRunBlock);
     hipLaunchKernelGGL(k_pairs_list, dim3((a.n_works + kRunBlock - 1) / kRunBlock), blk, 0, s, a,
                        flag.p);
-    hipLaunchKernelGGL(k_pairs_cover<Src>, dim3((a.n_runs + kRunBlock - 1) / kRunBlock), blk, 0, s,
-                       src, a, flag.p);
+    hipLaunchKernelGGL(k_pairs_cover, dim3((a.n_runs + kRunBlock - 1) / kRunBlock), blk, 0, s,
+                       RowsSrc{d_rows}, a, flag.p);
     hipLaunchKernelGGL(k_pairs_covered, dim3(a.n_tiles), dim3(kTile), 0, s, a);
   }
 

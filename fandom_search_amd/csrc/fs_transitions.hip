@@ -87,8 +87,7 @@ struct TrArgs {
   fs_transition* cells;
 };
 
-template <class Src>
-__global__ __launch_bounds__(kBlock) void k_tr_check(Src src, TrArgs a) {
+__global__ __launch_bounds__(kBlock) void k_tr_check(RowsSrc src, TrArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool bad = false;
   if (i < a.n) {
@@ -123,8 +122,8 @@ __global__ __launch_bounds__(kScanBlock) void k_tr_scan(const uint32_t* in, uint
 // kPlace false: the kept runs with a unit of this workgroup's 256 runs into cnt; true: those
 // runs to their places, cnt holding the scan.  (Every orig_ix is below n_script here:
 // k_tr_check found nothing.)
-template <class Src, bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_tr_seq(Src src, TrArgs a) {
+template <bool kPlace>
+__global__ __launch_bounds__(kBlock) void k_tr_seq(RowsSrc src, TrArgs a) {
   __shared__ uint32_t s_w[kBlock / 64];
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   uint32_t b = 0, e = 0, u = FS_NONE;
@@ -339,15 +338,13 @@ struct TrJob {
     return FS_OK;
   }
 
-  // d_units written, n_cells set (all on `s`, finished on return).  The records are `src`:
-  // d_rows, or the columns `cols`.
-  template <class Src>
-  int count(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n,
-            uint32_t n_works, uint32_t n_script, const uint32_t* d_unit_of, uint32_t n_units,
-            uint32_t min_words, uint32_t max_gap, uint32_t within, uint32_t min_steps,
-            uint32_t min_step_works, uint32_t min_share, fs_transition_unit* d_units,
-            hipStream_t s) {
+  // d_units written, n_cells set (all on `s`, finished on return)
+  int count(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+            const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+            uint32_t within, uint32_t min_steps, uint32_t min_step_works, uint32_t min_share,
+            fs_transition_unit* d_units, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
+    const RowsSrc src{d_rows};
     a.n = n;
     a.n_works = n_works;
     a.n_script = n_script;
@@ -369,11 +366,10 @@ struct TrJob {
     FS_HIP(hipMemsetAsync(status.p, 0, kStWords * sizeof(uint32_t), s));
     a.status = status.p;
     FS_TRY(clk.mark(0, s));
-    hipLaunchKernelGGL((k_tr_check<Src>), dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
+    hipLaunchKernelGGL(k_tr_check, dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
     hipLaunchKernelGGL(k_tr_units_ok, dim3(blocks_of(n_script, kBlock)), blk, 0, s, a);
     FS_HIP(hipGetLastError());
-    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &runs,
-                        &a.heads, &a.n_runs));
+    FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &runs, &a.heads, &a.n_runs));
     uint32_t st[kStWords];
     FS_HIP(hipMemcpyAsync(st, status.p, sizeof st, hipMemcpyDeviceToHost, s));
     FS_HIP(hipStreamSynchronize(s));
@@ -390,7 +386,7 @@ struct TrJob {
     const uint32_t run_blocks = blocks_of(a.n_runs, kBlock);
     FS_TRY(cnt.reserve(run_blocks));
     a.cnt = cnt.p;
-    if (run_blocks) hipLaunchKernelGGL((k_tr_seq<Src, false>), dim3(run_blocks), blk, 0, s, src, a);
+    if (run_blocks) hipLaunchKernelGGL((k_tr_seq<false>), dim3(run_blocks), blk, 0, s, src, a);
     hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.cnt, run_blocks,
                        (unsigned long long*)nullptr, a.status + kStSeq);
     FS_HIP(hipGetLastError());
@@ -406,7 +402,7 @@ struct TrJob {
     a.of = seq.p + 3 * m;
     a.ol = seq.p + 4 * m;
     a.unit = seq.p + 5 * m;
-    hipLaunchKernelGGL((k_tr_seq<Src, true>), dim3(run_blocks), blk, 0, s, src, a);
+    hipLaunchKernelGGL((k_tr_seq<true>), dim3(run_blocks), blk, 0, s, src, a);
     FS_HIP(hipGetLastError());
     FS_TRY(clk.mark(1, s));
 
@@ -504,14 +500,7 @@ int tr_check(uint64_t n_rows, uint32_t n_script, const void* unit_of, uint32_t n
     fs_set_error("min_share %u: a whole percentage, 0 to 100", min_share);
     return FS_E_INVALID;
   }
-  if (n_rows >= (1ull << 32)) {
-    fs_set_error("%llu records: transitions take fewer than 2^32", (unsigned long long)n_rows);
-    return FS_E_UNSUPPORTED;
-  }
-  if (n_script > FS_WORKS_MAX_SCRIPT) {
-    fs_set_error("n_script %u: transitions take up to %u", n_script, FS_WORKS_MAX_SCRIPT);
-    return FS_E_UNSUPPORTED;
-  }
+  FS_TRY(record_limits("transitions", n_rows, n_script));
   *n_cells = 0;
   return FS_OK;
 }
@@ -539,17 +528,16 @@ extern "C" int fs_transitions(int device, const uint32_t* work, const uint32_t* 
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_unit_of;
   DBuf<fs_transition_unit> d_units;
   DBuf<fs_transition> d_cells;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n));
   FS_TRY(d_unit_of.upload(unit_of, n_script, nullptr));
   FS_TRY(d_units.reserve(n_units));
-  const ColsSrc src = cols.src();
   TrJob job;
-  FS_TRY(job.count(src, nullptr, src, n, n_works, n_script, d_unit_of.p, n_units, min_words,
-                   max_gap, within, min_steps, min_step_works, min_share, d_units.p, nullptr));
+  FS_TRY(job.count(rows.p, n, n_works, n_script, d_unit_of.p, n_units, min_words, max_gap, within,
+                   min_steps, min_step_works, min_share, d_units.p, nullptr));
   FS_TRY(copy_out(units, d_units, n_units));
   *n_cells = job.n_cells;
   if (job.n_cells > cap) {
@@ -589,11 +577,10 @@ extern "C" int fs_transitions_rows(fs_index* ix, const fs_row* d_rows, uint64_t 
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
   TrJob job;
-  FS_TRY(job.count(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script,
-                   d_unit_of, n_units, min_words, max_gap, within, min_steps, min_step_works,
-                   min_share, d_units, ix->stream));
+  FS_TRY(job.count(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, d_unit_of, n_units,
+                   min_words, max_gap, within, min_steps, min_step_works, min_share, d_units,
+                   ix->stream));
   *n_cells = job.n_cells;
   if (job.n_cells > cap) {
     fs_set_error("%llu cells need room", (unsigned long long)job.n_cells);

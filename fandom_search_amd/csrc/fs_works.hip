@@ -48,8 +48,7 @@ struct WorksArgs {
 };
 
 // one lane per run
-template <class Src>
-__global__ __launch_bounds__(kRunBlock) void k_works_runs(Src src, WorksArgs a,
+__global__ __launch_bounds__(kRunBlock) void k_works_runs(RowsSrc src, WorksArgs a,
                                                           const uint32_t* __restrict__ heads,
                                                           uint32_t n_runs) {
   const uint32_t lane = threadIdx.x & 63;
@@ -127,8 +126,7 @@ __device__ inline void lds_clear(uint32_t* mem, const WorksArgs& a) {
 // Records [b, e) (wave-uniform) into the wave's LDS.  Returns this lane's share of the
 // outputs: lane j < n_thr the records with comb <= thr[j]; *fresh += script words whose bit
 // these records set first (wave-uniform); *bad |= an orig_ix outside the script.
-template <class Src>
-__device__ inline uint32_t lds_add(const Src& src, const WorksArgs& a, const Lds& l, uint64_t b,
+__device__ inline uint32_t lds_add(const RowsSrc& src, const WorksArgs& a, const Lds& l, uint64_t b,
                                    uint64_t e, uint32_t* fresh, bool* bad) {
   const uint32_t lane = threadIdx.x;
   uint32_t acc = 0;
@@ -172,8 +170,7 @@ __device__ inline uint32_t lds_add(const Src& src, const WorksArgs& a, const Lds
 }
 
 // the bits records [b, e) set, cleared again: all of them when that is less work
-template <class Src>
-__device__ inline void lds_unset(const Src& src, const WorksArgs& a, const Lds& l, uint64_t b,
+__device__ inline void lds_unset(const RowsSrc& src, const WorksArgs& a, const Lds& l, uint64_t b,
                                  uint64_t e) {
   if (e - b >= a.bw) {
     for (uint32_t k = threadIdx.x; k < a.bw; k += kWave) l.bm[k] = 0;
@@ -188,8 +185,7 @@ __device__ inline void lds_unset(const Src& src, const WorksArgs& a, const Lds& 
 extern __shared__ uint32_t s_works[];
 
 // a wave per slice of records: the parts of large works inside it
-template <class Src>
-__global__ __launch_bounds__(kWave) void k_works_slices(Src src, WorksArgs a) {
+__global__ __launch_bounds__(kWave) void k_works_slices(RowsSrc src, WorksArgs a) {
   const Lds l = lds_of(s_works, a);
   const uint32_t lane = threadIdx.x;
   lds_clear(s_works, a);
@@ -230,8 +226,7 @@ __global__ __launch_bounds__(kWave) void k_works_slices(Src src, WorksArgs a) {
 }
 
 // a wave per a.per_wave works
-template <class Src>
-__global__ __launch_bounds__(kWave) void k_works_each(Src src, WorksArgs a) {
+__global__ __launch_bounds__(kWave) void k_works_each(RowsSrc src, WorksArgs a) {
   const Lds l = lds_of(s_works, a);
   const uint32_t lane = threadIdx.x;
   lds_clear(s_works, a);
@@ -394,13 +389,12 @@ int works_invalid() {
 }
 
 // d_out and d_counts written and *n_cells set; d_cells too unless FS_E_CAPACITY (all on `s`,
-// finished on return).  The records are `src`: d_rows, or the columns `cols`.
-template <class Src>
-int works_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_t n, uint32_t n_works,
-              uint32_t n_script, const uint32_t* group_of, uint32_t n_groups, uint32_t min_words,
-              uint32_t max_gap, const double* thresholds, uint32_t n_thr, fs_work* d_out,
-              uint32_t* d_counts, fs_work_cell* d_cells, uint64_t cap, uint64_t* n_cells,
-              hipStream_t s) {
+// finished on return).
+int works_run(const fs_row* d_rows, uint32_t n, uint32_t n_works, uint32_t n_script,
+              const uint32_t* group_of, uint32_t n_groups, uint32_t min_words, uint32_t max_gap,
+              const double* thresholds, uint32_t n_thr, fs_work* d_out, uint32_t* d_counts,
+              fs_work_cell* d_cells, uint64_t cap, uint64_t* n_cells, hipStream_t s) {
+  const RowsSrc src{d_rows};
   WorksScratch k;
   WorksArgs a{};
   a.n = n;
@@ -422,9 +416,7 @@ int works_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_
 
   const uint32_t* heads = nullptr;
   uint32_t n_runs = 0;
-  if (n)
-    FS_TRY(fs_runs_find(d_rows, cols.work, cols.fan, cols.orig, n, min_words, max_gap, s, &k.runs,
-                        &heads, &n_runs));
+  if (n) FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &k.runs, &heads, &n_runs));
   if (n && !n_works) return works_invalid();
   if (!n_works) return FS_OK;
 
@@ -457,7 +449,7 @@ int works_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_
   a.cells = d_cells;
 
   if (n_runs)
-    hipLaunchKernelGGL(k_works_runs<Src>, dim3((n_runs + kRunBlock - 1) / kRunBlock),
+    hipLaunchKernelGGL(k_works_runs, dim3((n_runs + kRunBlock - 1) / kRunBlock),
                        dim3(kRunBlock), 0, s, src, a, heads, n_runs);
   hipLaunchKernelGGL(k_works_scan<0>, dim3(1), dim3(kScanBlock), 0, s, a);
   FS_HIP(hipGetLastError());
@@ -469,13 +461,13 @@ int works_run(const Src& src, const fs_row* d_rows, const ColsSrc& cols, uint32_
   a.staged = k.staged.p;
 
   if (lds > 64 * 1024) {
-    FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_works_slices<Src>),
+    FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_works_slices),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_works_each<Src>),
+    FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_works_each),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  if (tiles) hipLaunchKernelGGL(k_works_slices<Src>, dim3(tiles), dim3(kWave), lds, s, src, a);
-  hipLaunchKernelGGL(k_works_each<Src>, dim3((n_works + a.per_wave - 1) / a.per_wave),
+  if (tiles) hipLaunchKernelGGL(k_works_slices, dim3(tiles), dim3(kWave), lds, s, src, a);
+  hipLaunchKernelGGL(k_works_each, dim3((n_works + a.per_wave - 1) / a.per_wave),
                      dim3(kWave), lds, s, src, a);
   hipLaunchKernelGGL(k_works_scan<1>, dim3(1), dim3(kScanBlock), 0, s, a);
   FS_HIP(hipGetLastError());
@@ -517,17 +509,16 @@ extern "C" int fs_works(int device, const uint32_t* work, const uint32_t* fan_ix
   }
   FS_ENTER(device);
   const uint32_t n = (uint32_t)n_rows;
-  HostCols cols;
+  DBuf<fs_row> rows;
   DBuf<uint32_t> d_counts;
   DBuf<fs_work> d_out;
   DBuf<fs_work_cell> d_cells;
-  FS_TRY(cols.upload(work, fan_ix, orig_ix, n, nullptr, comb));
+  FS_TRY(fs_host_rows(rows, work, fan_ix, orig_ix, n, nullptr, comb));
   FS_TRY(d_out.reserve(n_works));
   FS_TRY(d_counts.reserve((size_t)n_works * (n_thr + 1)));
   FS_TRY(d_cells.reserve(cap < n_rows ? cap : n_rows));       // a record makes at most one cell
-  const ColsSrc src = cols.src();
-  const int rc = works_run(src, nullptr, src, n, n_works, n_script, group_of, n_groups, min_words,
-                           max_gap, thresholds, n_thr, d_out.p, d_counts.p, d_cells.p, cap, n_cells,
+  const int rc = works_run(rows.p, n, n_works, n_script, group_of, n_groups, min_words, max_gap,
+                           thresholds, n_thr, d_out.p, d_counts.p, d_cells.p, cap, n_cells,
                            nullptr);
   if (rc != FS_OK && rc != FS_E_CAPACITY) return rc;
   if (n_works) {
@@ -562,8 +553,7 @@ extern "C" int fs_works_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows
     return FS_E_INVALID;
   }
   FS_ENTER(ix->device);
-  const RowsSrc src{d_rows};
-  return works_run(src, d_rows, ColsSrc{}, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, group_of,
-                   n_groups, min_words, max_gap, thresholds, n_thr, d_out, d_counts, d_cells, cap,
-                   n_cells, ix->stream);
+  return works_run(d_rows, (uint32_t)n_rows, n_works, (uint32_t)ix->n_script, group_of, n_groups,
+                   min_words, max_gap, thresholds, n_thr, d_out, d_counts, d_cells, cap, n_cells,
+                   ix->stream);
 }

@@ -281,16 +281,20 @@ typedef struct fs_passage {
   double   comb_sum, comb_max;
 } fs_passage;          /* 48 bytes                                             */
 
-/* Host columns in, `cap` host passages out, on HIP device `device`.  Both entry points:
+/* Host columns in, `cap` host passages out, on HIP device `device`.  Here and in every
+ * command below, the host form uploads its columns, packs them on the device into fs_row
+ * records (lev 0; a column the command does not take 0.0) and runs what its _rows form runs:
+ * it holds 32 bytes per record on the device, and the columns beside them only while it
+ * packs.  Both entry points:
  * FS_E_INVALID for min_words == 0 or records out of (work, fan_ix) order, FS_E_UNSUPPORTED
  * for n_rows >= 2^32, FS_E_CAPACITY with *n_out = passages required when cap is smaller,
  * FS_OK with *n_out = 0 and no device work for n_rows == 0. */
 int fs_passages(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
                 const double* dist, const double* comb, uint64_t n_rows, uint32_t min_words,
                 uint32_t max_gap, fs_passage* out, uint64_t cap, uint64_t* n_out);
-/* The same over device-resident fs_row records (16-byte aligned, e.g. straight after a
- * search) into a device buffer of `cap` passages, on the index's device and stream;
- * returns when they are written. */
+/* The same over fs_row records already on the device (16-byte aligned, e.g. straight after a
+ * search; lev is not read) into a device buffer of `cap` passages, on the index's device and
+ * stream; returns when they are written. */
 int fs_passages_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t min_words,
                      uint32_t max_gap, fs_passage* d_out, uint64_t cap, uint64_t* n_out);
 

@@ -294,6 +294,40 @@ def test_tables_above_the_cap_are_refused_before_anything_is_allocated():
     assert found[0]["covered"][0] == 4                     # the same columns, accepted
 
 
+# ---- host columns and device records are one path ---------------------------------------
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])            # around the pack kernel's workgroup
+def test_host_columns_equal_device_records_with_the_flags_in_comb(n, synth_base):
+    """fs_groups packs its columns into fs_row records on the device, the exact flag as comb:
+    the output equals, byte for byte, fs_groups_rows over the same records built on the host
+    with lev = 7 and comb = 0.0 / 1.0, and with the same flags spelt -0.0 / NaN."""
+    import torch
+    from fandom_search_amd.engine import ScriptIndex, torch_ready
+    script = synth.script_tokens(200)
+    ix = ScriptIndex(script, [synth_base["words"][int(t)] for t in script], synth_base["emb"],
+                     synth.lsh_normals(6))
+    sizes = [n - n // 2, n // 2] if n > 1 else [1]
+    work, fan, orig, exact = with_exact(records(sizes, len(script), seed=n), n)
+    assert 0 < exact.sum() < n or n == 1
+    mem = [[0, 1 + w] for w in range(len(sizes))]
+    m_off, m_grp = lists(mem)
+    label_of = scenes(len(script), 3)
+    args = (len(sizes), m_off, m_grp, 3, label_of, 3, 2, 1, 1)
+    host = groups.find_groups(work, fan, orig, exact, len(sizes), len(script), *args[1:])
+    assert host[0]["n_words"][0] == n and host[0]["n_exact"][0] == exact.sum()
+    for yes, no in ((0.0, 1.0), (-0.0, np.nan)):
+        rows = np.zeros(n, dtype=abi.ROW_DTYPE)
+        rows["work"], rows["fan_ix"], rows["orig_ix"], rows["lev"] = work, fan, orig, 7
+        rows["dist"] = np.nan
+        rows["comb"] = np.where(exact != 0, yes, no)
+        buf = torch.from_numpy(rows.view(np.uint8)).cuda()
+        torch_ready()
+        dev = ix.groups_device(buf.data_ptr(), n, *args)
+        for a, b in zip(host, dev):
+            assert a.tobytes() == b.tobytes()
+    ix.close()
+
+
 # ---- after a real search ---------------------------------------------------------------
 
 def test_device_rows_equal_host_columns_after_a_search(synth_base):

@@ -161,6 +161,38 @@ def test_capacity_then_success():
     assert_passages_equal(out, want)
 
 
+# ---- host columns and device records are one path ---------------------------------------
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])            # around the pack kernel's workgroup
+def test_host_columns_equal_device_records_with_another_lev(n, synth_base):
+    """fs_passages packs its columns into fs_row records on the device: the passages equal, byte
+    for byte, fs_passages_rows over the same records built on the host with lev = 7 (lev is not
+    read; NaN, -0.0 and 0.0 arrive as they left)."""
+    import torch
+    from fandom_search_amd.engine import ScriptIndex, torch_ready
+    script = synth.script_tokens(64)
+    ix = ScriptIndex(script, [synth_base["words"][int(t)] for t in script], synth_base["emb"],
+                     synth.lsh_normals(6))
+    cols = random_records(n, seed=n, nan=0.1)
+    for col in cols[3:]:                                     # NaN, -0.0 and 0.0 are among them
+        zeros = col[col == 0]
+        assert n == 1 or (np.isnan(col).any() and np.signbit(zeros).any()
+                          and not np.signbit(zeros).all())
+    rows = np.zeros(n, dtype=abi.ROW_DTYPE)
+    for name, col in zip(("work", "fan_ix", "orig_ix", "dist", "comb"), cols):
+        rows[name] = col
+    rows["lev"] = 7
+    assert rows["dist"].view(np.uint64).tolist() == cols[3].view(np.uint64).tolist()
+    buf = torch.from_numpy(rows.view(np.uint8)).cuda()
+    torch_ready()
+    for m, g in ((1, 0), (2, 1)):
+        host = passages.find_passages(*cols, min_words=m, max_gap=g)
+        dev = ix.passages_device(buf.data_ptr(), n, min_words=m, max_gap=g)
+        assert host.tobytes() == dev.tobytes()
+        assert len(host) > 0 or m > n
+    ix.close()
+
+
 # ---- after a real search ---------------------------------------------------------------
 
 def planted(work_idx, n_tokens, script, vocab_size=synth.VOCAB_SIZE):
