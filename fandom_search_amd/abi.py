@@ -236,6 +236,28 @@ FS_CONTRAST_MAX_WORKS = 1 << 20
 FS_CONTRAST_MAX_BYTES = 1 << 30
 CONTRAST_MS_NAMES = ("incidence", "selection", "product", "sweeps", "total")
 
+# fs_saturation_point: 64 bytes; fs_saturation_perm and fs_saturation_summary: 16 bytes
+SATURATION_POINT_DTYPE = np.dtype([("units_low", np.uint32), ("units_median", np.uint32),
+                                   ("units_high", np.uint32), ("units_min", np.uint32),
+                                   ("units_max", np.uint32), ("works_low", np.uint32),
+                                   ("works_median", np.uint32), ("works_high", np.uint32),
+                                   ("units_sum", np.uint64), ("works_sum", np.uint64),
+                                   ("reserved0", np.uint64), ("reserved1", np.uint64)])
+assert SATURATION_POINT_DTYPE.itemsize == 64
+SATURATION_PERM_DTYPE = np.dtype([("half_at", np.uint32), ("ninety_at", np.uint32),
+                                  ("all_at", np.uint32), ("reserved", np.uint32)])
+assert SATURATION_PERM_DTYPE.itemsize == 16
+SATURATION_SUMMARY_DTYPE = np.dtype([("n_active", np.uint32), ("units_quoted", np.uint32),
+                                     ("singletons", np.uint32), ("doubletons", np.uint32)])
+assert SATURATION_SUMMARY_DTYPE.itemsize == 16
+FS_SATURATION_MAX_PERMUTATIONS = 4096
+FS_SATURATION_MAX_POINTS = 1024
+FS_SATURATION_MAX_WORKS = 1 << 28
+FS_SATURATION_MAX_BYTES = 1 << 30
+# fs_saturation_times: six passes and their total in ms, then the product's source and its shares of k and of the orders
+SATURATION_MS_NAMES = ("incidence", "sizes", "times", "product", "curve", "points", "total",
+                       "table", "ksplit", "osplit")
+
 # fs_transition_unit: 40 bytes; fs_transition: 32 bytes
 TRANSITION_UNIT_DTYPE = np.dtype([("passages", np.uint32), ("works", np.uint32),
                                   ("starts", np.uint32), ("ends", np.uint32),

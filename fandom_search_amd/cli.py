@@ -25,7 +25,9 @@ phrases the works quote word for word, each with the works quoting it in full
 everything the works quote (fandom_search_amd/digest.py), and `intervals`, which resamples the
 works to say how sure the works-per-stretch counts are (fandom_search_amd/intervals.py), and
 `contrast`, which says what one group of works quotes more than another and which of those
-differences survive a look at every unit at once (fandom_search_amd/contrast.py).  The
+differences survive a look at every unit at once (fandom_search_amd/contrast.py), and
+`saturation`, which says how much of what fans quote a sample of the works would have shown
+(fandom_search_amd/saturation.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -418,10 +420,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`)."""
+    `contrast`, `saturation`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, contrast or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -558,6 +560,41 @@ def ao3_parser():
                          help='relabellings of the works, 1 to 4096, default 1000'),
                     _own('--seed', default=0, type=int,
                          help='seed of the relabellings, 0 to 2^64 - 1, default 0')])
+
+    _analysis(subparsers, 'saturation',
+              'says whether the sample of works is large enough: random orders of the fan '
+              'works, per point of the curve how many script words inside a quoted region, '
+              'regions, scenes or characters a sample of that share of the works has seen, '
+              'as an interval, median and mean over the orders beside the sample\'s size; '
+              'per order where it passes half, nine tenths and all of them; and the Chao2 '
+              'lower bound of what is still unseen',
+              'prefix of the three csv files, PREFIX-saturation.csv, '
+              'PREFIX-saturation-permutations.csv and PREFIX-saturation-summary.csv '
+              '(default: the input name without .csv)',
+              [(lambda a: a.min_words < 1 or a.min_works < 1 or a.max_gap < 0,
+                '--min-words and --min-works must be at least 1, --max-gap at least 0'),
+               (lambda a: not 1 <= a.permutations <= 4096,
+                '--permutations must be from 1 to 4096'),
+               (lambda a: not 1 <= a.points <= 1024, '--points must be from 1 to 1024'),
+               (lambda a: not 50 <= a.level <= 99, '--level must be from 50 to 99'),
+               (lambda a: not 0 <= a.seed < 1 << 64, '--seed must be from 0 to 2^64 - 1')],
+              middle=[_own('--by', default='word',
+                           choices=('region', 'word', 'scene', 'character'),
+                           help='the units: every script word inside a quoted region of '
+                                '`quotes` (default), the regions, the scenes or the '
+                                'characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --by region or word: fewest different works whose '
+                              'passages cover every word of a region, default 1'),
+                    _own('--permutations', default=1000, type=int,
+                         help='orders of the works, 1 to 4096, default 1000'),
+                    _own('--points', default=100, type=int,
+                         help='points of the curve, evenly spaced sample shares, 1 to 1024, '
+                              'default 100'),
+                    _own('--seed', default=0, type=int,
+                         help='seed of the orders, 0 to 2^64 - 1, default 0'),
+                    _own('--level', default=95, type=int,
+                         help='the interval as a whole percentage, 50 to 99, default 95')])
     return parser
 
 

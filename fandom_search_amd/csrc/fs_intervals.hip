@@ -21,8 +21,8 @@
 //   k_int_plain      FS_INTERVALS_MFMA=0: a lane per (unit, replicate) walks the set bits of the
 //                    unit's row; no matrix instruction.  For the tests and the bench's A/B
 //   k_int_stats      a workgroup per unit: its B counts and its B ppm values sorted in LDS (a
-//                    bitonic network over the next power of two), the three order statistics of
-//                    each and the sum
+//                    bitonic network over the next power of two, fs_sort.h), the three order
+//                    statistics of each and the sum
 //   k_int_quoted     Q_b: lanes over replicates, waves over units, one atomic add per workgroup
 //                    and replicate
 //   (host)           works(u) copied back, the observed order by a stable sort, rank and next up
@@ -34,6 +34,7 @@
 // 64 k + 16 g + j.  What is relied on: row = lane & 15 for A (the replicate), column =
 // lane & 15 for B (the unit), and the C/D map col = lane & 15, row = 4 * (lane >> 4) + reg.
 #include "fs_incidence.h"
+#include "fs_sort.h"
 
 #include <algorithm>
 #include <vector>
@@ -224,26 +225,7 @@ __global__ __launch_bounds__(kStat) void k_int_stats(IntArgs a) {
   }
   sum = wave_sum(sum);
   if ((tid & 63) == 0) s_w[tid >> 6] = sum;
-  for (uint32_t k = 2; k <= a.P; k <<= 1) {
-    for (uint32_t j = k >> 1; j; j >>= 1) {
-      __syncthreads();
-      for (uint32_t i = tid; i < a.P; i += kStat) {
-        const uint32_t o = i ^ j;
-        if (o <= i) continue;
-        const bool up = (i & k) == 0;
-        const uint32_t c0 = s_c[i], c1 = s_c[o], p0 = s_p[i], p1 = s_p[o];
-        if ((c0 > c1) == up && c0 != c1) {
-          s_c[i] = c1;
-          s_c[o] = c0;
-        }
-        if ((p0 > p1) == up && p0 != p1) {
-          s_p[i] = p1;
-          s_p[o] = p0;
-        }
-      }
-    }
-  }
-  __syncthreads();
+  block_sort_two<kStat>(s_c, s_p, a.P);
   if (tid) return;
   sum = 0;
   for (uint32_t w = 0; w < kStat / 64; ++w) sum += s_w[w];

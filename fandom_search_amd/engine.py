@@ -725,6 +725,34 @@ class ScriptIndex(object):
                           [(n_units, abi.CONTRAST_UNIT_DTYPE),
                            (permutations, abi.CONTRAST_PERM_DTYPE)], [], [], out_ptrs, "")
 
+    def saturation_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
+                          max_gap=0, permutations=1000, points=100, seed=0, level=95,
+                          first=False, out_ptrs=None):
+        """`saturation` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident unit map of the script's words (fs_saturation_rows): works(u), per point
+        of the curve the order statistics of the units seen and of the works sampled over the
+        orders, per order where it passes half, nine tenths and all of the quoted units, and the
+        summary's counts; with `first` also first(r, u), [n_units][permutations].  Without
+        `out_ptrs`: (uint32[n_units], abi.SATURATION_POINT_DTYPE[points],
+        abi.SATURATION_PERM_DTYPE[permutations], abi.SATURATION_SUMMARY_DTYPE[1]) on the host,
+        then the uint32 first times with `first`.  With `out_ptrs` = device addresses (works,
+        points, permutations, summary and, with `first`, the first times): they are written and
+        () comes back.  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_saturation_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                        C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                        int(max_gap), int(permutations), int(points), int(seed),
+                                        int(level), C.c_void_p(fixed[0]), C.c_void_p(fixed[1]),
+                                        C.c_void_p(fixed[2]), C.c_void_p(fixed[3]),
+                                        C.c_void_p(fixed[4]) if first else None)
+        fixed = [(n_units, np.uint32), (points, abi.SATURATION_POINT_DTYPE),
+                 (permutations, abi.SATURATION_PERM_DTYPE), (1, abi.SATURATION_SUMMARY_DTYPE)]
+        if first:
+            fixed.append((int(n_units) * int(permutations), np.uint32))
+        return _rows_call("fs_saturation_rows", call, fixed, [], [], out_ptrs, "")
+
     def transitions_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                            max_gap=0, within=abi.FS_NONE, min_steps=1, min_step_works=2,
                            min_share=0, out_ptrs=None, cap=None):

@@ -1243,6 +1243,134 @@ int fs_contrast_times(double* ms);
  * and its correction.  No device is touched. */
 uint64_t fs_contrast_isqrt(uint64_t x);
 
+/* `ao3.py saturation`: what a sample of the fan works would show, the accumulation (rarefaction)
+ * curve of the quoted units.  Records, passages, active works (numbered in work order), the
+ * coverage, unit_of[n_script] and works(u), the active works quoting unit u, as for
+ * fs_intervals.  n_works is every work of the file, active or not; a sample draws from all of
+ * them.  A unit is quoted when works(u) > 0; Q is their number.  In order r (0-based, r <
+ * permutations) work w (its work number) arrives at time h(r, w), the hash of fs_intervals with
+ * r in place of the replicate,
+ *     z = ((r << 32) | w) + seed * 0x9E3779B97F4A7C15                  (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31);  h = z >> 32
+ * a pure function of (seed, r, w).  Nothing is sorted or ranked: the sample at fraction f is the
+ * works with h < f * 2^32, each work in it independently with probability f, and the samples
+ * are nested as f grows.  Point c (1..points) has the threshold T_c = floor(c * 2^32 / points),
+ * so T_points = 2^32, and
+ *     bucket(h, points) = ((h + 1) * points + 2^32 - 1) >> 32          (64 bits)
+ * is the first point whose sample holds a work of time h.
+ *     first(r, u) = the smallest h(r, w) over the active works quoting u
+ *     n_r(c)      = the works, of all n_works, with h(r, w) < T_c
+ *     S_r(c)      = the quoted units with first(r, u) < T_c
+ * so n_r(points) = n_works and S_r(points) = Q in every order.  Per point, with s the S_r(c) in
+ * ascending order and t = permutations * (100 - level) / 200 (rounded down): low = s[t], high =
+ * s[permutations - 1 - t], median = s[(permutations - 1) / 2], min = s[0], max =
+ * s[permutations - 1] and the sum over r; the same three order statistics and the sum over the
+ * n_r(c).  Per order: half_at, the smallest c with 2 * S_r(c) >= Q; ninety_at, with 10 * S_r(c)
+ * >= 9 * Q; all_at, with S_r(c) == Q; all three 1 when Q = 0.  Every output is an integer. */
+typedef struct fs_saturation_point {
+  uint32_t units_low;        /* s[t] of S_r(c)                                            */
+  uint32_t units_median;     /* s[(permutations - 1) / 2]                                 */
+  uint32_t units_high;       /* s[permutations - 1 - t]                                   */
+  uint32_t units_min;        /* s[0]                                                      */
+  uint32_t units_max;        /* s[permutations - 1]                                       */
+  uint32_t works_low;        /* the three order statistics of n_r(c)                      */
+  uint32_t works_median;
+  uint32_t works_high;
+  uint64_t units_sum;        /* the sum of S_r(c) over r                                  */
+  uint64_t works_sum;        /* the sum of n_r(c) over r                                  */
+  uint64_t reserved0;        /* 0                                                         */
+  uint64_t reserved1;        /* 0                                                         */
+} fs_saturation_point;       /* 64 bytes                                                  */
+
+typedef struct fs_saturation_perm {
+  uint32_t half_at;          /* the smallest c with 2 * S_r(c) >= Q                       */
+  uint32_t ninety_at;        /*                     10 * S_r(c) >= 9 * Q                  */
+  uint32_t all_at;           /*                     S_r(c) == Q                           */
+  uint32_t reserved;         /* 0                                                         */
+} fs_saturation_perm;        /* 16 bytes                                                  */
+
+typedef struct fs_saturation_summary {
+  uint32_t n_active;         /* the works with a passage                                  */
+  uint32_t units_quoted;     /* Q                                                         */
+  uint32_t singletons;       /* Q1, the units with works(u) == 1                          */
+  uint32_t doubletons;       /* Q2, the units with works(u) == 2                          */
+} fs_saturation_summary;     /* 16 bytes                                                  */
+
+#define FS_SATURATION_MAX_PERMUTATIONS 4096u
+#define FS_SATURATION_MAX_POINTS 1024u
+#define FS_SATURATION_MAX_WORKS (1u << 28)
+/* Counted: the incidence matrix (ceil(n_units / 64) * 64 * ceil(active works / 64) * 8 bytes),
+ * the first times (4 bytes per unit and order, the orders padded to a multiple of 64), the two
+ * histograms (4 bytes per point and padded order, twice) and, where it is used, the table of
+ * times (4 bytes per active work and padded order).  Their sum may be up to this. */
+#define FS_SATURATION_MAX_BYTES (1u << 30)
+
+/* Host columns and the host unit map in; works[n_units] (works(u)), pts[points] (pts[c - 1] is
+ * point c), perms[permutations] and one summary out, on HIP device `device`; first is null or
+ * [n_units][permutations], first(r, u) at first[u * permutations + r], 0xFFFFFFFF for a unit
+ * nobody quotes (a quoted unit is recognised by works(u) > 0, never by that value: a time may be
+ * 0xFFFFFFFF).  Both entry points: FS_E_INVALID for null arguments, min_words == 0, permutations
+ * outside 1..FS_SATURATION_MAX_PERMUTATIONS, points outside 1..FS_SATURATION_MAX_POINTS, level
+ * outside 50..99, records out of (work, fan_ix) order, a work >= n_works, an orig_ix >= n_script
+ * or a unit_of entry that is neither below n_units nor 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows
+ * >= 2^32, n_script > FS_WORKS_MAX_SCRIPT, n_works > FS_SATURATION_MAX_WORKS or tables above
+ * FS_SATURATION_MAX_BYTES (the message states the parts).  No records, no active work and no
+ * units follow the definitions: Q = 0, every S_r(c) is 0 and the three per-order figures are 1;
+ * the n_r(c) count the works of the file all the same.
+ * The passes are separate launches and no workgroup waits on another; every merge is an integer
+ * min or add, so any schedule gives the same result: incidence (fs_companions' own) with
+ * works(u) and the summary's counts; the sample sizes, a workgroup per order and slab of works
+ * that hashes every work of the file into a histogram over the points in LDS and adds its
+ * non-zero buckets, then a scan over c; the min product, a wave per unit row and 64 orders at
+ * a time, a lane per order, the set bits of the row walked by wave-uniform control, one min per
+ * set bit against the work's time; the curve, bucket(first) of the quoted units into histograms in LDS
+ * per tile of units and 64 orders, added to hist[c][r], a scan over c, a lane per order for its
+ * three figures; and per point a workgroup that sorts the S_r(c) and the n_r(c) in LDS.
+ * Switches of the environment, read once per call; the output is the same wherever they stand:
+ *   FS_SATURATION_TABLE      where the product takes a work's time from.  1: a table
+ *                            time[active work][orders padded to 64], written once by a pass of
+ *                            its own, a set bit then one coalesced 256-byte read per wave;
+ *                            0 (default): the hash made again in the lane.  A call whose tables
+ *                            would pass the byte limit with the table of times and not without
+ *                            it takes 0
+ *   FS_SATURATION_OSPLIT     the workgroups that share the chunks of 64 orders of a unit row;
+ *                            a wave reads its row once for all the chunks it takes.  Default:
+ *                            1 from 2048 workgroups of four rows on, more below, a chunk each at
+ *                            the most
+ *   FS_SATURATION_KSPLIT     the workgroups that share the words of a unit row and merge their
+ *                            parts by an atomic min; default: 1 from 512 product workgroups on,
+ *                            more below, at least 8 words each
+ *   FS_SATURATION_MAX_BYTES  a lower bound than the macro's, for tests */
+int fs_saturation(int device, const uint32_t* work, const uint32_t* fan_ix,
+                  const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                  const uint32_t* unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
+                  uint32_t permutations, uint32_t points, uint64_t seed, uint32_t level,
+                  uint32_t* works, fs_saturation_point* pts, fs_saturation_perm* perms,
+                  fs_saturation_summary* summary, uint32_t* first);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (d_points, d_perms and d_summary 16-byte
+ * aligned, d_works and d_first 4-byte; d_first may be null), on the index's device and stream;
+ * returns when they are written. */
+int fs_saturation_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                       const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                       uint32_t max_gap, uint32_t permutations, uint32_t points, uint64_t seed,
+                       uint32_t level, uint32_t* d_works, fs_saturation_point* d_points,
+                       fs_saturation_perm* d_perms, fs_saturation_summary* d_summary,
+                       uint32_t* d_first);
+/* Of the last fs_saturation / fs_saturation_rows call on this thread, ten doubles: HIP-event
+ * milliseconds of incidence (with works(u) and the summary's counts), sample sizes (with their
+ * scan), the table of times, the product, the curve (with its scan and the per-order figures),
+ * the per-point statistics (with the copies out), and the total of the six; 0 for a pass that
+ * did not run.  Then 1 when the product read the table of times and 0 when it hashed, the
+ * shares of a unit row's words and the shares of its chunks of orders.
+ * tools/saturation_bench.py. */
+int fs_saturation_times(double* ms);
+/* bucket(h, points) as the kernels compute it, points from 1 to FS_SATURATION_MAX_POINTS.  No
+ * device is touched. */
+uint32_t fs_saturation_bucket(uint32_t h, uint32_t points);
+
 /* `ao3.py transitions`: which stretch of the script the fan works quote next, the directed
  * complement of fs_companions.  Records and passages as for fs_passages, in record order;
  * passage p has fan_first / fan_last and orig_first / orig_last as in fs_retelling_passage.
