@@ -236,6 +236,22 @@ FS_CONTRAST_MAX_WORKS = 1 << 20
 FS_CONTRAST_MAX_BYTES = 1 << 30
 CONTRAST_MS_NAMES = ("incidence", "selection", "product", "sweeps", "total")
 
+# fs_trends_unit: 48 bytes; fs_trends_perm: 16 bytes
+TRENDS_UNIT_DTYPE = np.dtype([("quoting", np.uint32), ("ge", np.uint32), ("adj_ge", np.uint32),
+                              ("first_x", np.uint32), ("last_x", np.uint32),
+                              ("reserved", np.uint32), ("offset_sum", np.uint64),
+                              ("statistic", np.uint64), ("d", np.int64)])
+assert TRENDS_UNIT_DTYPE.itemsize == 48
+TRENDS_PERM_DTYPE = np.dtype([("max_statistic", np.uint64), ("offset_sum", np.uint32),
+                              ("max_unit", np.uint32)])
+assert TRENDS_PERM_DTYPE.itemsize == 16
+FS_TRENDS_MAX_PERMUTATIONS = 4096
+FS_TRENDS_MAX_SPAN = 1024
+FS_TRENDS_MAX_WORKS = 1 << 20
+FS_TRENDS_MAX_BYTES = 1 << 30
+TRENDS_OUT = 0xFFFF                 # `when` of a work outside the pool
+TRENDS_MS_NAMES = ("pool", "labels", "product", "sweeps", "total")
+
 # fs_saturation_point: 64 bytes; fs_saturation_perm and fs_saturation_summary: 16 bytes
 SATURATION_POINT_DTYPE = np.dtype([("units_low", np.uint32), ("units_median", np.uint32),
                                    ("units_high", np.uint32), ("units_min", np.uint32),

@@ -27,7 +27,8 @@ works to say how sure the works-per-stretch counts are (fandom_search_amd/interv
 `contrast`, which says what one group of works quotes more than another and which of those
 differences survive a look at every unit at once (fandom_search_amd/contrast.py), and
 `saturation`, which says how much of what fans quote a sample of the works would have shown
-(fandom_search_amd/saturation.py).  The
+(fandom_search_amd/saturation.py), and `trends`, which says which stretches the later works quote
+more and which the earlier (fandom_search_amd/trends.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -420,10 +421,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`)."""
+    `contrast`, `saturation`, `trends`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -595,6 +596,43 @@ def ao3_parser():
                          help='seed of the orders, 0 to 2^64 - 1, default 0'),
                     _own('--level', default=95, type=int,
                          help='the interval as a whole percentage, 50 to 99, default 95')])
+
+    _analysis(subparsers, 'trends',
+              'says which stretches the later fan works quote more and which the earlier: '
+              'every dated work has a period from the metadata csv, per quoted region, script '
+              'word, scene or character whether the works quoting it are later or earlier '
+              'than the works as a whole, by how much, how often a random re-dating of the '
+              'works shifts them as far, and how often the largest shift over all units does '
+              '(the max-statistic correction of `contrast`)',
+              'prefix of the three csv files, PREFIX-trends.csv, PREFIX-trends-periods.csv '
+              'and PREFIX-trends-permutations.csv (default: the input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_quoting < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-works and --min-quoting must be at least 1, --max-gap at '
+                'least 0'),
+               (lambda a: not 1 <= a.permutations <= 4096,
+                '--permutations must be from 1 to 4096'),
+               (lambda a: not 0 <= a.seed < 1 << 64, '--seed must be from 0 to 2^64 - 1')],
+              first=[_own('meta', action='store',
+                          help='filename for the metadata csv (FILENAME, TITLE, AUTHOR, '
+                               'SUMMARY, NOTES, PUBLICATION_DATE, LANGUAGE, TAGS)'),
+                     _own('--by', default='year',
+                          help='the periods: year (default) or month of PUBLICATION_DATE')],
+              middle=[_own('--unit', default='region',
+                           choices=('region', 'word', 'scene', 'character'),
+                           help='the units: the quoted regions of `quotes` (default), '
+                                'every script word inside one, the scenes or the '
+                                'characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --unit region or word: fewest different works whose '
+                              'passages cover every word of a region, default 1'),
+                    _own('--min-quoting', default=5, type=int,
+                         help='fewest dated works quoting a unit of the family the '
+                              'adjustment covers, default 5'),
+                    _own('--permutations', default=1000, type=int,
+                         help='re-datings of the works, 1 to 4096, default 1000'),
+                    _own('--seed', default=0, type=int,
+                         help='seed of the re-datings, 0 to 2^64 - 1, default 0')])
     return parser
 
 

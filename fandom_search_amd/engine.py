@@ -725,6 +725,30 @@ class ScriptIndex(object):
                           [(n_units, abi.CONTRAST_UNIT_DTYPE),
                            (permutations, abi.CONTRAST_PERM_DTYPE)], [], [], out_ptrs, "")
 
+    def trends_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, when_ptr,
+                      min_words=6, max_gap=0, min_quoting=5, permutations=1000, seed=0,
+                      out_ptrs=None):
+        """`trends` over device-resident fs_row records sorted by (work, fan_ix), a
+        device-resident unit map of the script's words and device-resident period offsets, 16
+        bits per work: x(w) below 1024, or 0xFFFF for a work outside the pool (fs_trends_rows):
+        per unit the works quoting it, the sum of their offsets, its statistic and in how many
+        re-datings it, and the largest statistic of any unit, is reached; per re-dating the sum
+        of the pool's offsets and that largest statistic.  Without `out_ptrs`:
+        (abi.TRENDS_UNIT_DTYPE[n_units], abi.TRENDS_PERM_DTYPE[permutations]) on the host.
+        With `out_ptrs` = device addresses (units, re-datings): they are written and () comes
+        back.  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_trends_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                    int(max_gap), C.c_void_p(when_ptr), int(min_quoting),
+                                    int(permutations), int(seed), C.c_void_p(fixed[0]),
+                                    C.c_void_p(fixed[1]))
+        return _rows_call("fs_trends_rows", call,
+                          [(n_units, abi.TRENDS_UNIT_DTYPE),
+                           (permutations, abi.TRENDS_PERM_DTYPE)], [], [], out_ptrs, "")
+
     def saturation_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                           max_gap=0, permutations=1000, points=100, seed=0, level=95,
                           first=False, out_ptrs=None):

@@ -1243,6 +1243,107 @@ int fs_contrast_times(double* ms);
  * and its correction.  No device is touched. */
 uint64_t fs_contrast_isqrt(uint64_t x);
 
+/* `ao3.py trends`: which units the later (or the earlier) fan works quote, every unit tested at
+ * once against random re-datings of the same works, with the max-statistic correction of
+ * fs_contrast.  Records, passages, active works, the coverage, unit_of[n_script] and the works
+ * quoting a unit as for fs_intervals.  n_works is every work of the file, active or not.
+ * when[n_works] is 16 bits per work: its period offset x(w), 0 .. FS_TRENDS_MAX_SPAN - 1, or
+ * 0xFFFF for a work outside the pool.  The pool is the other works, N of them, active or not,
+ * in ascending work number: pool[0 .. N).
+ * Observed, per unit u: t(u) the active pool works quoting u, s(u) the sum of their x, X the sum
+ * of x over the pool,
+ *     D(u)   = s(u) * N - t(u) * X                       (signed; positive: quoted later)
+ *     den(u) = isqrt((t(u) * (N - t(u))) << 20)          (fs_contrast_isqrt)
+ *     Z(d,u) = (|d| << 10) / den(u), 0 when den(u) = 0;  Z(u) = Z(D(u), u)
+ * Re-dating r (0-based, r < permutations) gives every pool work the offset of a pool work drawn
+ * uniformly, with replacement: with h(r, w) the hash of fs_intervals (fs_contrast spells it out),
+ *     v = (h(r, w) * N) >> 32;   x_r(w) = x(pool[v])
+ * s_r(u) sums x_r over the active pool works quoting u, X_r over the pool (it varies with r),
+ *     D_r(u)     = s_r(u) * N - t(u) * X_r
+ *     GE(u)      = the re-datings r with |D_r(u)| >= |D(u)|
+ * The family is the units with t(u) >= min_quoting and t(u) < N.
+ *     MX_r       = the maximum over the family of Z(D_r(u), u); 0 with an empty family
+ *     MAX_UNIT_r = the first family unit attaining MX_r; 0xFFFFFFFF with an empty family
+ *     ADJ_GE(u)  = the re-datings r with MX_r >= Z(u) for a family unit, 0xFFFFFFFF otherwise
+ * Every output is an integer. */
+typedef struct fs_trends_unit {
+  uint32_t quoting;          /* t(u)                                                      */
+  uint32_t ge;               /* GE(u)                                                     */
+  uint32_t adj_ge;           /* ADJ_GE(u); 0xFFFFFFFF outside the family                  */
+  uint32_t first_x;          /* the smallest x among the works of t(u); 0xFFFFFFFF: none  */
+  uint32_t last_x;           /* the largest; 0xFFFFFFFF: none                             */
+  uint32_t reserved;         /* 0                                                         */
+  uint64_t offset_sum;       /* s(u)                                                      */
+  uint64_t statistic;        /* Z(u)                                                      */
+  int64_t d;                 /* D(u)                                                      */
+} fs_trends_unit;            /* 48 bytes                                                  */
+
+typedef struct fs_trends_perm {
+  uint64_t max_statistic;    /* MX_r                                                      */
+  uint32_t offset_sum;       /* X_r                                                       */
+  uint32_t max_unit;         /* MAX_UNIT_r                                                */
+} fs_trends_perm;            /* 16 bytes                                                  */
+
+#define FS_TRENDS_MAX_PERMUTATIONS 4096u
+/* x(w) is below this: ten bits, two planes of non-negative signed bytes, x & 127 and x >> 7 */
+#define FS_TRENDS_MAX_SPAN 1024u
+/* n_works up to this, so that every intermediate fits 64 bits: s and X are at most 2^20 * 1023,
+ * so |D| <= 2^50 and |D| << 10 <= 2^60; t * (N - t) <= 2^38 and, shifted, 2^58.  A sum of a
+ * plane's bytes is below 2^27 (x & 127) and 2^23 (x >> 7): no 32-bit accumulator wraps. */
+#define FS_TRENDS_MAX_WORKS (1u << 20)
+/* Counted: the incidence matrix (ceil(n_units / 64) * 64 * ceil(active works / 64) * 8 bytes),
+ * the two offset planes (permutations + 1 rows, padded to a multiple of 16, of ceil(active
+ * works / 64) * 64 bytes, twice) and the sums (4 bytes per padded unit and padded row).  Their
+ * sum may be up to this. */
+#define FS_TRENDS_MAX_BYTES (1u << 30)
+
+/* Host columns, the host unit map and the host offsets in; units[n_units] and
+ * perms[permutations] out, on HIP device `device`; sums is null or [n_units][permutations],
+ * s_r(u), the null distribution itself.  Both entry points: FS_E_INVALID for null arguments,
+ * min_words == 0, min_quoting == 0, permutations outside 1..FS_TRENDS_MAX_PERMUTATIONS, a `when`
+ * from FS_TRENDS_MAX_SPAN on that is not 0xFFFF, records out of (work, fan_ix) order, a work >=
+ * n_works, an orig_ix >= n_script or a unit_of entry that is neither below n_units nor
+ * 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT, n_works >
+ * FS_TRENDS_MAX_WORKS or tables above FS_TRENDS_MAX_BYTES (the message states the three).  No
+ * records, no active work and an empty pool follow the definitions: every sum is 0, so D = 0,
+ * GE = permutations, Z = 0 and nobody is in the family; without units only perms is written.
+ * The passes are separate launches and no workgroup waits on another: the pool (a check of
+ * `when`, a scan for the pool positions and N, the pool's offsets in pool order, and the pool as
+ * a row of bits over the active works beside fs_companions' incidence); the labels, a lane per
+ * (re-dating, work): the hash, the gather, X_r by a workgroup reduction, and for an active work
+ * a byte in either plane, re-dating-major, rows padded with zeros to 16 re-datings and 64 works,
+ * row `permutations` the observed offsets; the product, s[u][r] = sum over the works w quoting u
+ * of lo[r][w] + 128 * hi[r][w], by v_mfma_i32_16x16x64_i8 with one expansion of a word of M from
+ * bits to bytes held against both planes; the sweeps: a wave per unit for t, the smallest and
+ * largest x, D, den, Z, GE and an atomic max into MX_r (read first, left out where it cannot
+ * win), then MAX_UNIT_r by an atomic min among the units attaining MX_r together with ADJ_GE(u)
+ * against MX in LDS.  Switches of the environment, read once per call; the output is the same
+ * wherever they stand:
+ *   FS_TRENDS_MFMA       1 (default): the product by MFMA; 0: a plain integer kernel, a lane per
+ *                        (unit, re-dating) that walks the set bits of the unit's row
+ *   FS_TRENDS_KSPLIT     the workgroups that share the words of a product tile and add their
+ *                        parts; default: 1 from 512 product workgroups on, more below, at least
+ *                        8 words each
+ *   FS_TRENDS_MAX_BYTES  a lower bound than the macro's, for tests */
+int fs_trends(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              uint64_t n_rows, uint32_t n_works, uint32_t n_script, const uint32_t* unit_of,
+              uint32_t n_units, uint32_t min_words, uint32_t max_gap, const uint16_t* when,
+              uint32_t min_quoting, uint32_t permutations, uint64_t seed, fs_trends_unit* units,
+              fs_trends_perm* perms, uint32_t* sums);
+/* The same over device-resident fs_row records (16-byte aligned), a device-resident unit map of
+ * the index's n_script entries and device-resident offsets (2-byte aligned) into device buffers
+ * (16-byte aligned), on the index's device and stream; returns when they are written. */
+int fs_trends_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                   uint32_t max_gap, const uint16_t* d_when, uint32_t min_quoting,
+                   uint32_t permutations, uint64_t seed, fs_trends_unit* d_units,
+                   fs_trends_perm* d_perms);
+/* HIP-event milliseconds of the last fs_trends / fs_trends_rows call on this thread: pool (with
+ * the incidence, the run heads and the numbering of the active works, the host's wait for them
+ * included), labels, product, sweeps, and the total of the four; 0 for a pass that did not run.
+ * tools/trends_bench.py. */
+int fs_trends_times(double* ms);
+
 /* `ao3.py saturation`: what a sample of the fan works would show, the accumulation (rarefaction)
  * curve of the quoted units.  Records, passages, active works (numbered in work order), the
  * coverage, unit_of[n_script] and works(u), the active works quoting unit u, as for
