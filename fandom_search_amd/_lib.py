@@ -33,6 +33,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_intervals", "fs_intervals_rows", "fs_intervals_times",
            "fs_contrast", "fs_contrast_rows", "fs_contrast_times", "fs_contrast_isqrt",
            "fs_trends", "fs_trends_rows", "fs_trends_times",
+           "fs_neighbours", "fs_neighbours_rows", "fs_neighbours_times",
            "fs_saturation", "fs_saturation_rows", "fs_saturation_times", "fs_saturation_bucket",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
            "fs_sources", "fs_sources_times",
@@ -53,7 +54,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "contrast", "trends", "saturation", "transitions", "sources", "matrix",
+TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "saturation", "transitions", "sources", "matrix",
          "clusters", "groups")
 
 
@@ -265,6 +266,14 @@ def load():
     L.fs_trends_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                  C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.fs_neighbours.restype = C.c_int
+    L.fs_neighbours.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_neighbours_rows.restype = C.c_int
+    L.fs_neighbours_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
     L.fs_saturation.restype = C.c_int
     L.fs_saturation.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -252,6 +252,21 @@ FS_TRENDS_MAX_BYTES = 1 << 30
 TRENDS_OUT = 0xFFFF                 # `when` of a work outside the pool
 TRENDS_MS_NAMES = ("pool", "labels", "product", "sweeps", "total")
 
+# fs_neighbour: 48 bytes; fs_neighbour_work: 32 bytes; fs_neighbour_word: 8 bytes
+NEIGHBOUR_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "a", "b", "rank", "back_rank", "ppm", "score", "shared", "rarest", "rarest_depth",
+    "rarest_weight", "run_first", "run_words")])
+assert NEIGHBOUR_DTYPE.itemsize == 48
+NEIGHBOUR_WORK_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "covered", "own", "candidates", "listed", "listed_by", "mutual", "nearest", "nearest_ppm")])
+assert NEIGHBOUR_WORK_DTYPE.itemsize == 32
+NEIGHBOUR_WORD_DTYPE = np.dtype([("depth", np.uint32), ("weight", np.uint32)])
+assert NEIGHBOUR_WORD_DTYPE.itemsize == 8
+FS_NEIGHBOURS_RARITY, FS_NEIGHBOURS_FLAT = 0, 1
+FS_NEIGHBOURS_MAX_TOP = 32
+FS_NEIGHBOURS_MAX_BYTES = 1 << 30
+NEIGHBOURS_MS_NAMES = ("coverage", "weights", "product", "place", "detail", "total")
+
 # fs_saturation_point: 64 bytes; fs_saturation_perm and fs_saturation_summary: 16 bytes
 SATURATION_POINT_DTYPE = np.dtype([("units_low", np.uint32), ("units_median", np.uint32),
                                    ("units_high", np.uint32), ("units_min", np.uint32),

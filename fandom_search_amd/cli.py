@@ -28,7 +28,8 @@ works to say how sure the works-per-stretch counts are (fandom_search_amd/interv
 differences survive a look at every unit at once (fandom_search_amd/contrast.py), and
 `saturation`, which says how much of what fans quote a sample of the works would have shown
 (fandom_search_amd/saturation.py), and `trends`, which says which stretches the later works quote
-more and which the earlier (fandom_search_amd/trends.py).  The
+more and which the earlier (fandom_search_amd/trends.py), and `neighbours`, which lists each
+work's closest works by the rare lines both quote (fandom_search_amd/neighbours.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -421,10 +422,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`, `trends`)."""
+    `contrast`, `saturation`, `trends`, `neighbours`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -633,6 +634,34 @@ def ao3_parser():
                          help='re-datings of the works, 1 to 4096, default 1000'),
                     _own('--seed', default=0, type=int,
                          help='seed of the re-datings, 0 to 2^64 - 1, default 0')])
+
+    _analysis(subparsers, 'neighbours',
+              'lists each fan work\'s closest works by the rare lines both quote: a script '
+              'word weighs the more the fewer works cover it, the similarity of two works is '
+              'the weighted Jaccard of their coverages in parts per million; per work its '
+              '--top closest works with the rarest word they share and the run around it, '
+              'per work how its list and the others\' hold each other, per script word its '
+              'depth and weight',
+              'prefix of the three csv files, PREFIX-neighbours.csv, '
+              'PREFIX-neighbours-works.csv and PREFIX-neighbours-words.csv (default: the '
+              'input name without .csv)',
+              [(lambda a: not 1 <= a.top <= 32, '--top must be from 1 to 32'),
+               (lambda a: a.min_score < 1, '--min-score must be at least 1'),
+               (lambda a: not 0 <= a.min_similarity <= 100,
+                '--min-similarity must be from 0 to 100'),
+               _SPANS],
+              middle=[_own('--weight', default='rarity', choices=('rarity', 'flat'),
+                           help='what a shared script word weighs: the bits of (active works '
+                                '// works covering it), 1 for a word more than half the '
+                                'works cover (rarity, default), or 1 (flat)'),
+                      _own('--top', default=10, type=int,
+                           help='most neighbours listed per work, 1 to 32, default 10'),
+                      _own('--min-score', default=1, type=int,
+                           help='smallest weighted sum of the shared words of a candidate, '
+                                'default 1'),
+                      _own('--min-similarity', default=0, type=int,
+                           help='smallest similarity of a candidate as a whole percentage, '
+                                '0 to 100, default 0')])
     return parser
 
 

@@ -749,6 +749,33 @@ class ScriptIndex(object):
                           [(n_units, abi.TRENDS_UNIT_DTYPE),
                            (permutations, abi.TRENDS_PERM_DTYPE)], [], [], out_ptrs, "")
 
+    def neighbours_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, weight=0,
+                          top=10, min_score=1, min_similarity=0, out_ptrs=None, cap=None):
+        """`neighbours` over device-resident fs_row records sorted by (work, fan_ix) (after a
+        search or a gather; fs_neighbours_rows): per work its coverage, own score, candidates
+        and how its list and the others' hold each other, per script word its depth and weight
+        (`weight`: abi.FS_NEIGHBOURS_RARITY or abi.FS_NEIGHBOURS_FLAT), and every work's `top`
+        closest works in (work, rank) order.  Without `out_ptrs`:
+        (abi.NEIGHBOUR_WORK_DTYPE[n_works], abi.NEIGHBOUR_WORD_DTYPE[n_script],
+        abi.NEIGHBOUR_DTYPE[n_listed]) on the host.  With `out_ptrs` = device addresses (works;
+        words; listed pairs, a buffer of `cap` of them): the number of listed pairs;
+        FsError(FS_E_CAPACITY) with .required when that buffer is too small (works and words
+        are complete then).  Buffers torch has only just produced go in after torch_ready()."""
+        L = _lib.load()
+        n_script = int(self.info["n_script"])
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_neighbours_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                        int(min_words), int(max_gap), int(weight), int(top),
+                                        int(min_score), int(min_similarity), C.c_void_p(fixed[0]),
+                                        C.c_void_p(fixed[1]), C.c_void_p(grown[0]), int(caps[0]),
+                                        C.byref(counts[0]))
+        return _rows_call("fs_neighbours_rows", call,
+                          [(n_works, abi.NEIGHBOUR_WORK_DTYPE),
+                           (n_script, abi.NEIGHBOUR_WORD_DTYPE)], [abi.NEIGHBOUR_DTYPE],
+                          [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "listed pair buffer too small")
+
     def saturation_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
                           max_gap=0, permutations=1000, points=100, seed=0, level=95,
                           first=False, out_ptrs=None):

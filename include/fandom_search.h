@@ -1344,6 +1344,92 @@ int fs_trends_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t
  * tools/trends_bench.py. */
 int fs_trends_times(double* ms);
 
+/* `ao3.py neighbours`: each fan work's closest works by the rare script words both quote.
+ * Records, passages, coverage C_w and the active works (numbered in work order) as for fs_pairs;
+ * N active works.  depth(o) is the number of active works whose coverage holds script word o;
+ * weight(o) is 0 where depth(o) == 0, else 1 under FS_NEIGHBOURS_FLAT and the number of bits of
+ * N / depth(o) (integer division) under FS_NEIGHBOURS_RARITY: 1 for a word more than half the
+ * works cover, at most 32.  score(a, b) is the sum of weight(o) over C_a & C_b (below 2^24),
+ * own(a) = score(a, a), ppm(a, b) = score * 1000000 / (own(a) + own(b) - score), rounded down,
+ * in 64 bits.  b is a candidate of a when b != a, score >= min_score and ppm >= min_similarity *
+ * 10000.  The list of a: its first `top` candidates by the key (ppm << 32) | (0xFFFFFFFF - b),
+ * larger first.  Every output is an integer. */
+typedef struct fs_neighbour {
+  uint32_t a, b;             /* the work and the listed neighbour, work numbers          */
+  uint32_t rank;             /* of b in the list of a, from 1                            */
+  uint32_t back_rank;        /* of a in the list of b, from 1; 0xFFFFFFFF: not in it     */
+  uint32_t ppm;              /* ppm(a, b)                                                */
+  uint32_t score;            /* score(a, b)                                              */
+  uint32_t shared;           /* |C_a & C_b|                                              */
+  uint32_t rarest;           /* the shared script word of largest weight, the first
+                                among equals                                             */
+  uint32_t rarest_depth;     /* its depth                                                */
+  uint32_t rarest_weight;    /* its weight                                               */
+  uint32_t run_first;        /* start of the maximal run of consecutive shared script
+                                words that holds it                                      */
+  uint32_t run_words;        /* its length                                               */
+} fs_neighbour;              /* 48 bytes                                                 */
+
+typedef struct fs_neighbour_work {
+  uint32_t covered;          /* |C_w|; 0 for a work without a passage                    */
+  uint32_t own;              /* own(w)                                                   */
+  uint32_t candidates;       /* all candidates, not only the listed ones                 */
+  uint32_t listed;           /* entries of its list                                      */
+  uint32_t listed_by;        /* works whose list holds it                                */
+  uint32_t mutual;           /* listed neighbours whose list holds it                    */
+  uint32_t nearest;          /* rank 1; 0xFFFFFFFF without one                           */
+  uint32_t nearest_ppm;      /* its ppm; 0 without one                                   */
+} fs_neighbour_work;         /* 32 bytes                                                 */
+
+typedef struct fs_neighbour_word {
+  uint32_t depth;            /* active works covering the script word                    */
+  uint32_t weight;           /* 0 where depth is 0                                       */
+} fs_neighbour_word;         /* 8 bytes                                                  */
+
+#define FS_NEIGHBOURS_RARITY 0u
+#define FS_NEIGHBOURS_FLAT 1u
+#define FS_NEIGHBOURS_MAX_TOP 32u
+/* What is counted, with R the active works rounded up to 64, nk = ceil(n_script / 64) and P the
+ * partial lists of a row (four per share of the column tiles):
+ *   the coverage matrix            R * nk * 8 bytes
+ *   the partial lists              R * P * top * 8
+ *   their candidate counts         R * P * 4
+ *   the lists and the back ranks   R * top * 12
+ *   depth and weight               nk * 64 * 5
+ *   the words with a bit, by tile  R / 64 * ceil(nk / 64) * 8 */
+#define FS_NEIGHBOURS_MAX_BYTES (1u << 30)
+
+/* Host columns in; works[n_works], words[n_script] and `cap` listed pairs out, on HIP device
+ * `device`.  The listed pairs come in (a, rank) order.  Both entry points: the FS_E_INVALID and
+ * FS_E_UNSUPPORTED cases of fs_pairs (min_score in the place of min_shared, tables above
+ * FS_NEIGHBOURS_MAX_BYTES in the place of the matrix), and FS_E_INVALID for a `weight` that is
+ * neither FS_NEIGHBOURS_RARITY nor FS_NEIGHBOURS_FLAT, top == 0, top > FS_NEIGHBOURS_MAX_TOP or
+ * min_similarity > 100; FS_E_CAPACITY with *n_listed = listed pairs required when cap is
+ * smaller (works and words are complete then, the pairs untouched).  n_rows == 0: works without
+ * coverage, words without depth, *n_listed = 0 (fs_neighbours: without device work).
+ * Environment (diagnostics, read on each call):
+ *   FS_NEIGHBOURS_MFMA   0: the product without the matrix instruction (the same results)
+ *   FS_NEIGHBOURS_SPLIT  that many shares of the column tiles per stripe of rows, for tests */
+int fs_neighbours(int device, const uint32_t* work, const uint32_t* fan_ix,
+                  const uint32_t* orig_ix, uint64_t n_rows, uint32_t n_works, uint32_t n_script,
+                  uint32_t min_words, uint32_t max_gap, uint32_t weight, uint32_t top,
+                  uint32_t min_score, uint32_t min_similarity, fs_neighbour_work* works,
+                  fs_neighbour_word* words, fs_neighbour* listed, uint64_t cap,
+                  uint64_t* n_listed);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_neighbours_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                       uint32_t min_words, uint32_t max_gap, uint32_t weight, uint32_t top,
+                       uint32_t min_score, uint32_t min_similarity, fs_neighbour_work* d_works,
+                       fs_neighbour_word* d_words, fs_neighbour* d_listed, uint64_t cap,
+                       uint64_t* n_listed);
+/* HIP-event milliseconds of the last fs_neighbours / fs_neighbours_rows call on this thread:
+ * coverage matrix, depth and weight (with own), product (with the merge of the partial lists),
+ * place (back ranks, counts, scan, the works table and the listed pairs), detail, and the total
+ * of the five; 0 for a pass that did not run.  tools/neighbours_bench.py. */
+int fs_neighbours_times(double* ms);
+
 /* `ao3.py saturation`: what a sample of the fan works would show, the accumulation (rarefaction)
  * curve of the quoted units.  Records, passages, active works (numbered in work order), the
  * coverage, unit_of[n_script] and works(u), the active works quoting unit u, as for
