@@ -42,6 +42,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_index_scan_shape", "fs_debug_stamps",
+           "fs_debug_ids16_window",
            "fs_search_profile", "fs_index_component_sizes", "fs_index_share_info", "fs_index_share_counts", "fs_index_lsh_counts",
            "fs_stream_floor",
            "fs_textenc_create", "fs_textenc_destroy", "fs_textenc_add", "fs_textenc_encode_files",
@@ -377,6 +378,7 @@ def load():
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_double)]
     optional = {                       # (absent from older builds loaded through FS_LIB_FILE)
         "fs_debug_stamps": [C.c_void_p, C.c_uint32, u64p, C.c_uint64, u64p],
+        "fs_debug_ids16_window": [C.POINTER(C.c_uint16), C.c_uint64, C.c_uint32, u32p],
         "fs_stream_floor": [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)],
         "fs_index_scan_shape": [C.c_void_p, C.c_void_p, C.POINTER(abi.FsScanShape)],
         "fs_index_share_counts": [C.c_void_p, u64p],

@@ -1,6 +1,7 @@
 // fs_api.hip -- C ABI of libfandomsearch_hip.so (include/fandom_search.h): host
 // side index build and the orchestration of the device pipeline.
 #include "fs_internal.h"
+#include "fs_ids16.h"
 #include <sched.h>
 
 #include <math.h>
@@ -1552,6 +1553,32 @@ extern "C" int fs_debug_stamps(fs_index* ix, uint32_t lane, uint64_t* out, uint6
   *n = ln.dbg_words;
   if (!out || cap < ln.dbg_words || !ln.dbg_words) return ln.dbg_words && out ? FS_E_CAPACITY : FS_OK;
   FS_HIP(hipMemcpy(out, ln.w_dbg.p, ln.dbg_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return FS_OK;
+}
+
+// Diagnostics, host only: the n ids of the window at position p of a 16-bit id array as
+// range_round takes them from CorpusDev::tok16 -- the dwords at the even position p & ~1 (four,
+// n = 8: five; the caller's array holds them, as the device copy does with its pad), then
+// fs_ids16_window (fs_ids16.h), the function the kernel calls.
+template <int N>
+static void ids16_window_host(const uint16_t* ids, uint64_t p, uint32_t* out) {
+  uint32_t d[5] = {0, 0, 0, 0, 0};
+  memcpy(d, ids + (p & ~1ull), (N == 8 ? 5 : 4) * sizeof(uint32_t));
+  fs_ids16_window<N>(d, (uint32_t)(p & 1), out);
+}
+
+extern "C" int fs_debug_ids16_window(const uint16_t* ids, uint64_t p, uint32_t n, uint32_t* out) {
+  if (!ids || !out) return FS_E_INVALID;
+  switch (n) {
+    case 2: ids16_window_host<2>(ids, p, out); break;
+    case 3: ids16_window_host<3>(ids, p, out); break;
+    case 4: ids16_window_host<4>(ids, p, out); break;
+    case 5: ids16_window_host<5>(ids, p, out); break;
+    case 6: ids16_window_host<6>(ids, p, out); break;
+    case 7: ids16_window_host<7>(ids, p, out); break;
+    case 8: ids16_window_host<8>(ids, p, out); break;
+    default: return FS_E_INVALID;
+  }
   return FS_OK;
 }
 

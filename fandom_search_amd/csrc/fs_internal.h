@@ -126,7 +126,9 @@ struct GramIndexDev {
 struct CorpusDev {
   const uint32_t* tok;       // [n_tok + pad] vector ids
   const uint16_t* tok16;     // [n_tok + pad] the same ids as 16-bit words (padded and zeroed alike), or nullptr:
-                             // an id of 2^16 or more, or an out-of-vocabulary id (k_scan_rows' id stream only)
+                             // an id of 2^16 or more, or an out-of-vocabulary id (k_scan_rows' 16-bit instances
+                             // only: their id stream and the ids their rounds verify, fs_ids16.h; even
+                             // positions are 4-byte aligned)
   const uint32_t* str;       // [n_tok] string ids or nullptr (== vector ids)
   const uint64_t* work_off;  // [n_works + 1]
   const uint2* blk_work;     // [ceil(n_tok / 256)] {work of token 256*i, end of that work}

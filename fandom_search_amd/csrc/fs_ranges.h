@@ -16,7 +16,10 @@
 //      64-byte entry of the batch table (fs_hash.h), compared id for id, and the work
 //      boundary from the token block's entry (two levels of loads, every load of a level
 //      requested before any is used); the entry carries the best rank's record of the
-//      n-gram for this batch (k_ctab)
+//      n-gram for this batch (k_ctab).  The ids come from the array the scan streams: the
+//      32-bit ids or, in the 16-bit instances (I16), the 16-bit copy, whose lines the wave has
+//      just read (aligned dwords and a shift by the position's parity, fs_ids16.h) -- such a
+//      search does not touch the 32-bit array at all
 //   2. compacts the hits behind the <= n-1 hits carried over from the last round
 //   3. emits the records of the words in [E, F): E = words done so far, F = the first
 //      position whose hit status is not known yet (the next round's first candidate, or
@@ -30,6 +33,7 @@
 // positions alone.
 #pragma once
 #include "fs_device.h"
+#include "fs_ids16.h"
 
 namespace fsdev {
 
@@ -135,7 +139,8 @@ struct RangeOut {
 // and the first minimum of dist * lev right here.  `sf`: the character classes;
 // `give_up`: the host word that sends the search through the chained kernels (set when a
 // text is too long for this path: they report it).
-template <int N, bool STR = false>
+// I16 (k_scan_rows' 16-bit instances; never with STR): the candidates' ids come from c.tok16.
+template <int N, bool STR = false, bool I16 = false>
 __device__ __forceinline__ void range_round(const CorpusDev& c, const GramIndexDev& g,
                                             uint32_t disp_off, RangeLds& S,
                                             uint32_t p, uint32_t F, uint32_t a,
@@ -166,7 +171,22 @@ __device__ __forceinline__ void range_round(const CorpusDev& c, const GramIndexD
         sid[4] = t1.x; sid[5] = t1.y; sid[6] = t1.z; sid[7] = t1.w;
       }
     }
-    {
+    static_assert(!(I16 && STR), "the 16-bit copy: vector ids only");
+    if constexpr (I16) {
+      // the ids from the 16-bit copy, whose lines this wave has just streamed (fs_ids16.h): the
+      // dwords at the even position p & ~1, 4-byte aligned.  The copy is padded by
+      // fs_scan_pad_tokens() zeroed ids like c.tok: the 8 (N = 8: 10) ids read here end at most
+      // 10 - N behind the last window's end, and a halo window in front of a range lies at p >= 0.
+      const uint16_t* q = c.tok16 + (p & ~1u);
+      const uint4 q0 = *reinterpret_cast<const uint4*>(q);
+      uint32_t d[5] = {q0.x, q0.y, q0.z, q0.w, 0};
+      if constexpr (N == 8) d[4] = *reinterpret_cast<const uint32_t*>(q + 8);
+      bw = c.blk4[p >> 8];
+      asm volatile("" : "+v"(bw.x), "+v"(bw.y), "+v"(bw.z), "+v"(bw.w), "+v"(d[0]));
+#pragma unroll
+      for (int k = N; k < 8; ++k) f[k] = 0;
+      fs_ids16_window<N>(d, p & 1u, f);
+    } else {
       const uint4 q0 = *reinterpret_cast<const uint4*>(c.tok + p);   // unaligned 16-byte loads;
       f[0] = q0.x; f[1] = q0.y; f[2] = q0.z; f[3] = q0.w;            // the buffer is padded
       if constexpr (N > 6) {

@@ -1090,8 +1090,8 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
         }
         const uint32_t p = make_round(W.rec, a, rt, rt + m, hn, a - hn);
         if (!(diag & 1))
-          range_round<N, STR>(c, g, disp_off, S, p, F, a, range_id, out, R,
-                              &strf, reinterpret_cast<uint32_t*>(fin.host_st + 1), keep_regs, clk);
+          range_round<N, STR, I16>(c, g, disp_off, S, p, F, a, range_id, out, R,
+                                   &strf, reinterpret_cast<uint32_t*>(fin.host_st + 1), keep_regs, clk);
         rt += m;
         halo_n = 0;
         ++n_rounds;
@@ -1191,8 +1191,8 @@ __global__ __launch_bounds__(1024, INL ? 4 : 5) void k_scan_rows(CorpusDev c, Gr
       wave_sync();
       const uint32_t p = make_round(s_wave[(slot - 1) / kCoopPerWave].rec, d_a, d_r0, d_r1, HALO, d_P - HALO);
       if (!(diag & 1))
-        range_round<N, STR>(c, g, disp_off, S, p, d_F, d_P, 0u, xout, Rs,
-                            &strf, reinterpret_cast<uint32_t*>(fin.host_st + 1), false, clk, &C.pool);
+        range_round<N, STR, I16>(c, g, disp_off, S, p, d_F, d_P, 0u, xout, Rs,
+                                 &strf, reinterpret_cast<uint32_t*>(fin.host_st + 1), false, clk, &C.pool);
       // its records count for the wave that posted it, its hits and pairs for this one
       R.hits_run += Rs.hits_run;
       R.match_acc += Rs.match_acc;

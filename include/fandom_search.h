@@ -2122,6 +2122,13 @@ int fs_csvw_format(fs_csvw* w, const fs_row* rows, uint64_t n_rows,
  * *n = words available; FS_E_CAPACITY when cap is smaller.  tools/scan_timeline.py. */
 int fs_debug_stamps(fs_index* ix, uint32_t lane, uint64_t* out, uint64_t cap, uint64_t* n);
 
+/* Diagnostics, no GPU involved: out[0 .. n) = the ids of the window at position p of a 16-bit
+ * id array, n = 2..8, taken the way the search's verification takes them from a batch's 16-bit
+ * copy: the 32-bit words from the even position p & ~1 on, shifted down by one id when p is
+ * odd.  Reads 8 ids from there (n = 8: 10), which the caller's array must hold (the device copy
+ * is padded with zeroed ids).  tests/test_ids16_window.py. */
+int fs_debug_ids16_window(const uint16_t* ids, uint64_t p, uint32_t n, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

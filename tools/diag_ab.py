@@ -99,6 +99,7 @@ def main():
         print(json.dumps(dict(variant=v, kernel_us_mean=round(float(np.mean(r["kernel"])), 2),
                               kernel_us_min=round(min(r["kernel"]), 2), kernel_us_max=round(max(r["kernel"]), 2),
                               step_us_mean=round(float(np.mean(r["step"])), 2), step_us_min=round(min(r["step"]), 2),
+                              step_us_median=round(float(np.median(r["step"])), 2), step_us_max=round(max(r["step"]), 2),
                               rows=r["rows"])), flush=True)
 
 
