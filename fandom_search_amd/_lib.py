@@ -34,6 +34,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_contrast", "fs_contrast_rows", "fs_contrast_times", "fs_contrast_isqrt",
            "fs_trends", "fs_trends_rows", "fs_trends_times",
            "fs_neighbours", "fs_neighbours_rows", "fs_neighbours_times",
+           "fs_misquotes", "fs_misquotes_times",
            "fs_saturation", "fs_saturation_rows", "fs_saturation_times", "fs_saturation_bucket",
            "fs_transitions", "fs_transitions_rows", "fs_transitions_times",
            "fs_sources", "fs_sources_times",
@@ -55,7 +56,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "saturation", "transitions", "sources", "matrix",
+TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
          "clusters", "groups")
 
 
@@ -275,6 +276,11 @@ def load():
     L.fs_neighbours_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_misquotes.restype = C.c_int
+    L.fs_misquotes.argtypes = [C.c_int, u32p, u32p, u32p, u32p, u32p, C.c_uint64, C.c_uint32,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                               C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p]
     L.fs_saturation.restype = C.c_int
     L.fs_saturation.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -267,6 +267,26 @@ FS_NEIGHBOURS_MAX_TOP = 32
 FS_NEIGHBOURS_MAX_BYTES = 1 << 30
 NEIGHBOURS_MS_NAMES = ("coverage", "weights", "product", "place", "detail", "total")
 
+# fs_misquote, fs_misquote_pair and fs_misquote_work: 32 bytes each
+MISQUOTE_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "orig_ix", "spell", "records", "works", "readers", "telling", "weight", "first_work")])
+assert MISQUOTE_DTYPE.itemsize == 32
+MISQUOTE_PAIR_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "a", "b", "shared", "score", "a_on_common", "b_on_common", "strongest",
+    "strongest_weight")])
+assert MISQUOTE_PAIR_DTYPE.itemsize == 32
+MISQUOTE_WORK_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "passage_records", "departures", "misquotes", "telling", "singular", "partners", "closest",
+    "closest_score")])
+assert MISQUOTE_WORK_DTYPE.itemsize == 32
+FS_MISQUOTES_RARITY, FS_MISQUOTES_FLAT = 0, 1
+FS_MISQUOTES_SLOT_BYTES = 32
+FS_MISQUOTES_RECORD_SLOT_BYTES = 40
+FS_MISQUOTES_MAX_BYTES = 1 << 30
+FS_MISQUOTES_MAX_ROWS = 1 << 27
+MISQUOTES_MS_NAMES = ("passages", "cells", "number", "postings", "expand", "place", "detail",
+                      "total")
+
 # fs_saturation_point: 64 bytes; fs_saturation_perm and fs_saturation_summary: 16 bytes
 SATURATION_POINT_DTYPE = np.dtype([("units_low", np.uint32), ("units_median", np.uint32),
                                    ("units_high", np.uint32), ("units_min", np.uint32),

@@ -29,7 +29,9 @@ differences survive a look at every unit at once (fandom_search_amd/contrast.py)
 `saturation`, which says how much of what fans quote a sample of the works would have shown
 (fandom_search_amd/saturation.py), and `trends`, which says which stretches the later works quote
 more and which the earlier (fandom_search_amd/trends.py), and `neighbours`, which lists each
-work's closest works by the rare lines both quote (fandom_search_amd/neighbours.py).  The
+work's closest works by the rare lines both quote (fandom_search_amd/neighbours.py), and
+`misquotes`, which lists the works that share departures from the script
+(fandom_search_amd/misquotes.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -422,10 +424,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`, `trends`, `neighbours`)."""
+    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, misquotes, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -662,6 +664,41 @@ def ao3_parser():
                       _own('--min-similarity', default=0, type=int,
                            help='smallest similarity of a candidate as a whole percentage, '
                                 '0 to 100, default 0')])
+
+    _analysis(subparsers, 'misquotes',
+              'lists the works that share departures from the script: a misquote is a '
+              'script word with a fan spelling that is not its own, inside a passage; one '
+              'that few of the works quoting the word share is telling and weighs the more '
+              'the fewer share it; per listed misquote its records, works and readers, per '
+              'pair of works the telling misquotes both have, their score and how much of '
+              'their common ground they agree on, per work its departures and its closest '
+              'work',
+              'prefix of the three csv files, PREFIX-misquotes.csv, '
+              'PREFIX-misquotes-pairs.csv and PREFIX-misquotes-works.csv (default: the '
+              'input name without .csv)',
+              [(lambda a: a.min_works < 2, '--min-works must be at least 2'),
+               (lambda a: not 1 <= a.max_share <= 100, '--max-share must be from 1 to 100'),
+               (lambda a: a.min_shared < 1 or a.min_score < 1,
+                '--min-shared and --min-score must be at least 1'),
+               _SPANS],
+              last=[_own('--min-works', default=2, type=int,
+                         help='fewest different works a listed misquote has, at least 2, '
+                              'default 2'),
+                    _own('--max-share', default=50, type=int,
+                         help='most of the works quoting a script word, as a whole '
+                              'percentage, that may share a telling misquote of it, 1 to '
+                              '100, default 50'),
+                    _own('--weight', default='rarity', choices=('rarity', 'flat'),
+                         help='what a telling misquote weighs: the bits of (works quoting '
+                              'the word // works sharing the misquote) (rarity, default), '
+                              'or 1 (flat)'),
+                    _own('--min-shared', default=1, type=int,
+                         help='fewest telling misquotes a kept pair shares, default 1'),
+                    _own('--min-score', default=1, type=int,
+                         help='smallest sum of their weights of a kept pair, default 1'),
+                    _own('--keep-case', action='store_true',
+                         help='compare the fan words with the script as written; by '
+                              'default spellings equal in lower case are one')])
     return parser
 
 

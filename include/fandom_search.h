@@ -1430,6 +1430,100 @@ int fs_neighbours_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint
  * of the five; 0 for a pass that did not run.  tools/neighbours_bench.py. */
 int fs_neighbours_times(double* ms);
 
+/* `ao3.py misquotes`: the works that share departures from the script.  Records sorted by
+ * (work, fan_ix) with the spelling id of their fan word; passages as for fs_passages; only the
+ * records inside a kept passage count, and a work with one is active.  same[o] is the spelling
+ * that is script word o itself (0xFFFFFFFF: none).  readers(o): the works with a record at o.
+ * A departure is a record whose spelling is not same(o); a misquote m is a pair (o, spelling)
+ * with a departure, records(m) its departures, works(m) the works among them.  m is listed when
+ * works(m) >= min_works, and numbered among the listed ones by orig_ix ascending, works
+ * descending, records descending, spell ascending.  A listed m is telling when works(m) * 100 <=
+ * max_share * readers(o) (in 64 bits); its weight is then 1 under FS_MISQUOTES_FLAT and the
+ * number of bits of readers(o) / works(m) (integer division) under FS_MISQUOTES_RARITY, and 0
+ * when it is not telling.  For works a < b, shared(a, b) is the number of telling misquotes both
+ * have and score(a, b) the sum of their weights; the pair is kept when shared >= min_shared and
+ * score >= min_score.  Every output is an integer. */
+typedef struct fs_misquote {
+  uint32_t orig_ix;          /* the script word                                          */
+  uint32_t spell;            /* what was written in its place                            */
+  uint32_t records;          /* departures                                               */
+  uint32_t works;            /* different works among them                               */
+  uint32_t readers;          /* readers(orig_ix)                                         */
+  uint32_t telling;          /* 1 or 0                                                   */
+  uint32_t weight;           /* 0 when not telling                                       */
+  uint32_t first_work;       /* the smallest work number that has it                     */
+} fs_misquote;               /* 32 bytes                                                 */
+
+typedef struct fs_misquote_pair {
+  uint32_t a, b;             /* work numbers, a < b                                      */
+  uint32_t shared;           /* telling misquotes both have                              */
+  uint32_t score;            /* the sum of their weights                                 */
+  uint32_t a_on_common;      /* telling misquotes of a at script words b reads           */
+  uint32_t b_on_common;      /* telling misquotes of b at script words a reads           */
+  uint32_t strongest;        /* the shared misquote of largest weight (its number), the
+                                smallest number among equals                             */
+  uint32_t strongest_weight; /* its weight                                               */
+} fs_misquote_pair;          /* 32 bytes                                                 */
+
+typedef struct fs_misquote_work {
+  uint32_t passage_records;  /* records inside kept passages; 0: not active              */
+  uint32_t departures;       /* those that are departures                                */
+  uint32_t misquotes;        /* listed misquotes it has                                  */
+  uint32_t telling;          /* telling misquotes it has                                 */
+  uint32_t singular;         /* misquotes only it has, works(m) == 1                     */
+  uint32_t partners;         /* kept pairs it is in                                      */
+  uint32_t closest;          /* the partner of largest score, the smallest work number
+                                among equals; 0xFFFFFFFF without a partner               */
+  uint32_t closest_score;    /* that score; 0 without a partner                          */
+} fs_misquote_work;          /* 32 bytes                                                 */
+
+#define FS_MISQUOTES_RARITY 0u
+#define FS_MISQUOTES_FLAT 1u
+/* What is counted.  P is the number of contributions, the sum of k * (k - 1) / 2 over the
+ * telling misquotes with k = works(m), N the active works:
+ *   the pair table     S slots of FS_MISQUOTES_SLOT_BYTES: key 8, shared 4, score 4,
+ *                      strongest 8, its place among the kept pairs 8; S the power of two at
+ *                      least twice min(P, N * (N - 1) / 2) and at least 64
+ *   the record tables  R slots of FS_MISQUOTES_RECORD_SLOT_BYTES: the keys (o, work),
+ *                      (o, spell) and (misquote, work), 8 each, and records, works, first work
+ *                      and number of the misquote in the slot, 4 each; R the power of two at
+ *                      least twice n_rows and at least 64
+ * Either may take FS_MISQUOTES_MAX_BYTES, which admits 2^24 contributions; beyond that the
+ * call is refused before the table is allocated. */
+#define FS_MISQUOTES_SLOT_BYTES 32u
+#define FS_MISQUOTES_RECORD_SLOT_BYTES 40u
+#define FS_MISQUOTES_MAX_BYTES (1u << 30)
+
+/* Host columns in; works[n_works] (always complete: zeros and closest = 0xFFFFFFFF for a work
+ * without a passage), up to cap_m listed misquotes in the order of their numbers and up to
+ * cap_p kept pairs in (a, b) order out, on HIP device `device`.  FS_E_CAPACITY when either cap
+ * is too small: *n_misquotes and *n_pairs say what is required, works is complete, the other
+ * two buffers are untouched.  FS_E_INVALID: records not sorted by (work, fan_ix); a work >=
+ * n_works, an orig_ix >= n_script, a spell >= n_spell; a same[o] that is neither 0xFFFFFFFF nor
+ * below n_spell; min_words == 0, min_works < 2, max_share outside 1 .. 100, min_shared == 0,
+ * min_score == 0, a `weight` that is neither FS_MISQUOTES_RARITY nor FS_MISQUOTES_FLAT.
+ * FS_E_UNSUPPORTED: n_rows >= 2^27 (a score is 32 bits and a weight at most 32), n_script >
+ * FS_WORKS_MAX_SCRIPT, tables above the bound (the message names P and --max-share).
+ * n_rows == 0: works without passages, no misquotes, no pairs, without device work.
+ * Environment (diagnostics, read once per call):
+ *   FS_MISQUOTES_MAX_PAIRS  the most contributions P a call takes; it only lowers the bound
+ *   FS_MISQUOTES_HASH_BITS  k bits of every table's hash are kept; at 0 every key collides and
+ *                           the output is the same */
+int fs_misquotes(int device, const uint32_t* work, const uint32_t* fan_ix,
+                 const uint32_t* orig_ix, const uint32_t* spell, const uint32_t* same,
+                 uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t n_spell,
+                 uint32_t min_words, uint32_t max_gap, uint32_t min_works, uint32_t max_share,
+                 uint32_t weight, uint32_t min_shared, uint32_t min_score,
+                 fs_misquote_work* works, fs_misquote* misquotes, uint64_t cap_m,
+                 uint64_t* n_misquotes, fs_misquote_pair* pairs, uint64_t cap_p,
+                 uint64_t* n_pairs);
+/* HIP-event milliseconds of the last fs_misquotes call on this thread: passages (with the
+ * checks of the records), cells, number (classify and number the misquotes), postings, expand,
+ * place (keep, partners, closest, the kept pairs in order), detail (with the copies out), and
+ * the total of the seven; 0 for a pass that did not run.  tools/misquotes_bench.py.  There is
+ * no _rows twin: fs_row carries no fan word (see fs_variants). */
+int fs_misquotes_times(double* ms);
+
 /* `ao3.py saturation`: what a sample of the fan works would show, the accumulation (rarefaction)
  * curve of the quoted units.  Records, passages, active works (numbered in work order), the
  * coverage, unit_of[n_script] and works(u), the active works quoting unit u, as for
