@@ -40,6 +40,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_sources", "fs_sources_times",
            "fs_matrix", "fs_matrix_rows", "fs_matrix_times",
            "fs_clusters", "fs_clusters_rows", "fs_clusters_times",
+           "fs_tree", "fs_tree_rows", "fs_tree_times",
            "fs_groups", "fs_groups_rows", "fs_groups_times",
            "fs_search_corpus_begin", "fs_search_corpus_end", "fs_index_set_scan_timing",
            "fs_index_reload_switches", "fs_search_kernel_name", "fs_index_scan_shape", "fs_debug_stamps",
@@ -57,7 +58,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
 TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
-         "clusters", "groups")
+         "clusters", "tree", "groups")
 
 
 class FsError(RuntimeError):
@@ -314,6 +315,14 @@ def load():
     L.fs_clusters_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_tree.restype = C.c_int
+    L.fs_tree.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                          C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_tree_rows.restype = C.c_int
+    L.fs_tree_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                               C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p]
     L.fs_groups.restype = C.c_int
     L.fs_groups.argtypes = [C.c_int, u32p, u32p, u32p, C.POINTER(C.c_uint8), C.c_uint64,
                             C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, C.c_uint32,

@@ -380,6 +380,25 @@ CLUSTER_DTYPE = np.dtype([("root", np.uint32), ("n_works", np.uint32), ("n_links
 assert CLUSTER_DTYPE.itemsize == 48
 FS_CLUSTERS_MAX_BYTES = 1 << 30
 
+# fs_tree_merge: 64 bytes; fs_tree_work and fs_tree_level: 32 bytes
+TREE_MERGE_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "a", "b", "level", "shared", "a_covered", "b_covered", "left", "right", "left_works",
+    "right_works", "works", "first_work", "tree", "run_first", "run_words", "reserved")])
+assert TREE_MERGE_DTYPE.itemsize == 64
+TREE_WORK_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "covered", "tree", "tree_works", "edges", "joined_merge", "joined_level", "best", "leaf")])
+assert TREE_WORK_DTYPE.itemsize == 32
+TREE_LEVEL_DTYPE = np.dtype([(n, np.uint32) for n in (
+    "level", "merges", "merges_above", "families", "largest", "joined", "singles", "reserved")])
+assert TREE_LEVEL_DTYPE.itemsize == 32
+FS_TREE_JACCARD, FS_TREE_SHARED = 0, 1
+TREE_MEASURES = ("jaccard", "shared")
+FS_TREE_MAX_BYTES = 1 << 30
+FS_TREE_ROW_BYTES = 60
+FS_TREE_MAX_ROUNDS = 40
+TREE_MS_NAMES = ("cover", "flatten", "best", "choose", "hook", "detail", "replay", "total",
+                 "rounds")
+
 # fs_group: 64 bytes; fs_group_cell: 24 bytes; fs_group_word: 16 bytes
 GROUP_DTYPE = np.dtype([("n_works", np.uint32), ("n_passage_works", np.uint32),
                         ("n_words", np.uint32), ("n_exact", np.uint32),

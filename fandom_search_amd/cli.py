@@ -31,7 +31,8 @@ differences survive a look at every unit at once (fandom_search_amd/contrast.py)
 more and which the earlier (fandom_search_amd/trends.py), and `neighbours`, which lists each
 work's closest works by the rare lines both quote (fandom_search_amd/neighbours.py), and
 `misquotes`, which lists the works that share departures from the script
-(fandom_search_amd/misquotes.py).  The
+(fandom_search_amd/misquotes.py), and `tree`, which shows how the families of works merge as
+the bar drops (fandom_search_amd/tree.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -424,10 +425,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`)."""
+    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, misquotes, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, misquotes, tree, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -699,6 +700,31 @@ def ao3_parser():
                     _own('--keep-case', action='store_true',
                          help='compare the fan words with the script as written; by '
                               'default spellings equal in lower case are one')])
+
+    _analysis(subparsers, 'tree',
+              'shows how the families of `clusters` merge as the bar drops, every bar at '
+              'once: two works sharing --min-shared script words have an edge at the level '
+              'of their Jaccard in parts per million (or of their shared words), the edges '
+              'are taken from the highest level down and one between two families merges '
+              'them; per merge its level, its edge and the two sides, per work its tree, '
+              'its first merge and its place in a leaf order, per level the families there '
+              'are then',
+              'prefix of the three csv files, PREFIX-tree.csv, PREFIX-tree-works.csv and '
+              'PREFIX-tree-levels.csv (default: the input name without .csv)',
+              [(lambda a: a.min_shared < 1, '--min-shared must be at least 1'),
+               (lambda a: a.min_level < 0 or (a.measure == 'jaccard' and a.min_level > 1000000),
+                '--min-level must be at least 0, and at most 1000000 under --measure jaccard'),
+               (lambda a: a.min_level > 0xFFFFFFFF, '--min-level must be below 2^32'),
+               _SPANS],
+              middle=[_own('--measure', default='jaccard', choices=('jaccard', 'shared'),
+                           help='the level of an edge: the shared words as parts per million '
+                                'of the words either work covers, rounded down (jaccard, '
+                                'default), or the shared words (shared)'),
+                      _own('--min-shared', default=6, type=int,
+                           help='fewest script words two works share to have an edge, '
+                                'default 6'),
+                      _own('--min-level', default=0, type=int,
+                           help='smallest level of an edge, default 0')])
     return parser
 
 

@@ -37,6 +37,7 @@
 // land on an entry after its owner has looked its root up.  So k_clusters_flatten writes what it
 // finds into `root`, which no find ever stores to, and every later kernel reads `root` alone.
 #include "fs_tiles.h"
+#include "fs_unionfind.h"
 
 namespace {
 
@@ -62,35 +63,6 @@ struct ClusterArgs : CoverArgs {
   fs_cluster_work* works;
   fs_cluster* clusters;
 };
-
-__device__ inline uint32_t uf_load(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x, with path halving
-__device__ inline uint32_t uf_find(uint32_t* parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = uf_load(parent + x);
-    if (p == x) return x;
-    const uint32_t g = uf_load(parent + p);
-    if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = g;
-  }
-}
-
-__device__ inline void uf_unite(uint32_t* parent, uint32_t x, uint32_t y) {
-  for (;;) {
-    x = uf_find(parent, x);
-    y = uf_find(parent, y);
-    if (x == y) return;
-    if (x > y) {
-      const uint32_t t = x;
-      x = y;
-      y = t;
-    }
-    if (atomicCAS(parent + y, y, x) == y) return;        // y was still a root: hooked under x
-  }
-}
 
 __global__ __launch_bounds__(kRunBlock) void k_clusters_init(ClusterArgs a) {
   const uint32_t i = blockIdx.x * kRunBlock + threadIdx.x;

@@ -140,54 +140,16 @@ __global__ __launch_bounds__(kRunBlock) void k_pairs_works(PairsArgs a, const ui
   reinterpret_cast<uint4*>(a.works)[w] = o;
 }
 
-// One lane per kept pair: the AND of the two rows walked a 64-bit word at a time, the open
-// run's start and length carried from word to word.
+// One lane per kept pair: what its two rows share (shared_run, fs_tiles.h).
 __global__ __launch_bounds__(kRunBlock) void k_pairs_detail(PairsArgs a, uint64_t n_pairs) {
   const uint64_t p = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
   if (p >= n_pairs) return;
   const uint4 head = reinterpret_cast<const uint4*>(a.pairs + p)[0];
   const uint32_t ia = a.act[head.x], ib = a.act[head.y];
-  const unsigned long long* ra = a.cov + (size_t)(ia / kTile) * a.nk * kTile + ia % kTile;
-  const unsigned long long* rb = a.cov + (size_t)(ib / kTile) * a.nk * kTile + ib % kTile;
-  uint32_t first = FS_NONE, last = 0, best_s = 0, best_n = 0, cur_s = 0, cur_n = 0;
-  for (uint32_t k = 0; k < a.nk; ++k) {
-    unsigned long long x = ra[(size_t)k * kTile] & rb[(size_t)k * kTile];
-    const uint32_t base = k * 64;
-    if (x == 0) {
-      if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
-      cur_n = 0;
-      continue;
-    }
-    if (first == FS_NONE) first = base + (uint32_t)__builtin_ctzll(x);
-    last = base + 63 - (uint32_t)__builtin_clzll(x);
-    if (x == ~0ull) {
-      if (!cur_n) cur_s = base;
-      cur_n += 64;
-      continue;
-    }
-    const uint32_t t = (uint32_t)__builtin_ctzll(~x);      // ones from bit 0 on: the open run goes on
-    if (t) {
-      if (!cur_n) cur_s = base;
-      cur_n += t;
-      x &= ~0ull << t;
-    }
-    if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
-    cur_n = 0;
-    while (x) {
-      const uint32_t s = (uint32_t)__builtin_ctzll(x);     // s >= 1: bit t is clear
-      const uint32_t l = (uint32_t)__builtin_ctzll(~(x >> s));
-      if (s + l == 64) {                                   // up to the word's last bit: left open
-        cur_s = base + s;
-        cur_n = l;
-        break;
-      }
-      if (l > best_n) { best_n = l; best_s = base + s; }
-      x &= ~0ull << (s + l);
-    }
-  }
-  if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
-  reinterpret_cast<uint4*>(a.pairs + p)[1] = make_uint4(last, best_s, best_n, 0u);
-  a.pairs[p].first = first;
+  const SharedRun r = shared_run(a.cov + (size_t)(ia / kTile) * a.nk * kTile + ia % kTile,
+                                 a.cov + (size_t)(ib / kTile) * a.nk * kTile + ib % kTile, a.nk);
+  reinterpret_cast<uint4*>(a.pairs + p)[1] = make_uint4(r.last, r.run_first, r.run_words, 0u);
+  a.pairs[p].first = r.first;
 }
 
 thread_local double t_ms[4];    // coverage, count, place, detail of the last call

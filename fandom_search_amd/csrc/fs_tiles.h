@@ -137,6 +137,57 @@ __device__ inline void tile_counts(const CoverArgs& a, uint32_t ti, uint32_t tj,
               s_b, s_sh);
 }
 
+// What two rows of the matrix share (k_pairs_detail, k_tree_detail): the AND of the rows at ra
+// and rb, nk words kTile apart, walked a 64-bit word at a time, the open run's start and length
+// carried from word to word.  The number of shared words, the smallest (FS_NONE without one) and
+// the largest of them, and the start and length of their longest run, the first among equals.
+struct SharedRun {
+  uint32_t shared, first, last, run_first, run_words;
+};
+
+__device__ inline SharedRun shared_run(const unsigned long long* ra, const unsigned long long* rb,
+                                       uint32_t nk) {
+  uint32_t shared = 0, first = FS_NONE, last = 0, best_s = 0, best_n = 0, cur_s = 0, cur_n = 0;
+  for (uint32_t k = 0; k < nk; ++k) {
+    unsigned long long x = ra[(size_t)k * kTile] & rb[(size_t)k * kTile];
+    const uint32_t base = k * 64;
+    if (x == 0) {
+      if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+      cur_n = 0;
+      continue;
+    }
+    shared += (uint32_t)__popcll(x);
+    if (first == FS_NONE) first = base + (uint32_t)__builtin_ctzll(x);
+    last = base + 63 - (uint32_t)__builtin_clzll(x);
+    if (x == ~0ull) {
+      if (!cur_n) cur_s = base;
+      cur_n += 64;
+      continue;
+    }
+    const uint32_t t = (uint32_t)__builtin_ctzll(~x);      // ones from bit 0 on: the open run goes on
+    if (t) {
+      if (!cur_n) cur_s = base;
+      cur_n += t;
+      x &= ~0ull << t;
+    }
+    if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+    cur_n = 0;
+    while (x) {
+      const uint32_t s = (uint32_t)__builtin_ctzll(x);     // s >= 1: bit t is clear
+      const uint32_t l = (uint32_t)__builtin_ctzll(~(x >> s));
+      if (s + l == 64) {                                   // up to the word's last bit: left open
+        cur_s = base + s;
+        cur_n = l;
+        break;
+      }
+      if (l > best_n) { best_n = l; best_s = base + s; }
+      x &= ~0ull << (s + l);
+    }
+  }
+  if (cur_n > best_n) { best_n = cur_n; best_s = cur_s; }
+  return SharedRun{shared, first, last, best_s, best_n};
+}
+
 // The shared passes of one call, in this order: number(), the caller's own refusals over
 // a.n_active, reserve(), cover().
 struct CoverJob {

@@ -850,6 +850,33 @@ class ScriptIndex(object):
                           [abi.CLUSTER_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
                           "cluster buffer too small")
 
+    def tree_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, measure='jaccard',
+                    min_shared=6, min_level=0, out_ptrs=None, caps=None):
+        """`tree` over device-resident fs_row records sorted by (work, fan_ix) (after a search
+        or a gather; fs_tree_rows): per work its tree, first merge and leaf, the merges in merge
+        order and the levels, the highest first.  Without `out_ptrs`:
+        (abi.TREE_WORK_DTYPE[n_works], abi.TREE_MERGE_DTYPE[n_merges],
+        abi.TREE_LEVEL_DTYPE[n_levels]) on the host.  With `out_ptrs` = device addresses (works;
+        merges and levels, buffers of `caps` = (merges, levels) of them): (n_merges, n_levels);
+        FsError(FS_E_CAPACITY) with the same in .required when either buffer is too small (the
+        works are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        from .tree import measure_code
+        L = _lib.load()
+        code = measure_code(measure)
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_tree_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                  int(min_words), int(max_gap), code, int(min_shared),
+                                  int(min_level), C.c_void_p(fixed[0]), C.c_void_p(grown[0]),
+                                  int(caps[0]), C.byref(counts[0]), C.c_void_p(grown[1]),
+                                  int(caps[1]), C.byref(counts[1]))
+        if caps is None:
+            caps = (0, 0) if out_ptrs is not None else (4096, 256)
+        return _rows_call("fs_tree_rows", call, [(n_works, abi.TREE_WORK_DTYPE)],
+                          [abi.TREE_MERGE_DTYPE, abi.TREE_LEVEL_DTYPE], list(caps), out_ptrs,
+                          "merge or level buffer too small")
+
     def retellings_device(self, rows_ptr, n_rows, n_works, min_words=6, max_gap=0, out_ptrs=None,
                           cap=None):
         """`retellings` over device-resident fs_row records sorted by (work, fan_ix) (after a

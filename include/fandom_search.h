@@ -521,6 +521,110 @@ int fs_clusters_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32
  * depth pass, merge pass; 0 for a pass that did not run.  tools/clusters_bench.py. */
 int fs_clusters_times(double* ms);
 
+/* `ao3.py tree`: how the families of works merge as the bar drops, the single-linkage
+ * dendrogram of the active works.  Records, passages and coverage as for fs_pairs; a work with
+ * a passage is active, N of them.  Active works a < b have an edge when shared = |C_a & C_b| >=
+ * min_shared and level >= min_level, where level is
+ *   FS_TREE_JACCARD  shared * 1000000 / (|C_a| + |C_b| - shared), rounded down
+ *   FS_TREE_SHARED   shared
+ * Edge e comes before edge f when its level is higher, then when its a is smaller, then its b:
+ * one strict order over all edges.  The edges are taken in that order and one is kept when its
+ * ends are in different families (Kruskal); the kept edges are the merges, at most N - 1, and
+ * form the one maximum spanning forest of that order.  Merge k joins the family holding a, its
+ * left side, and the family holding b, its right side.  The trees are the connected components
+ * of the forest, a lone active work too, ranked by their works, the most first, then by their
+ * earliest work.  The leaves are laid out tree by tree in rank order, and inside a tree the
+ * left side of its last merge before the right side, recursively.  Every output is an integer;
+ * merges, trees and leaves are numbered from 0. */
+#define FS_TREE_JACCARD 0u
+#define FS_TREE_SHARED 1u
+
+typedef struct fs_tree_merge {
+  uint32_t a, b;             /* the edge: work numbers, a < b                           */
+  uint32_t level;            /* its level                                               */
+  uint32_t shared;           /* script words in both coverages                          */
+  uint32_t a_covered;        /* |C_a|                                                   */
+  uint32_t b_covered;        /* |C_b|                                                   */
+  uint32_t left, right;      /* the merge that made that side; 0xFFFFFFFF when the side
+                                is the single work a (left) or b (right)                */
+  uint32_t left_works;       /* works of the left side                                  */
+  uint32_t right_works;      /* works of the right side                                 */
+  uint32_t works;            /* their sum: works of the merged family                   */
+  uint32_t first_work;       /* its smallest work number                                */
+  uint32_t tree;             /* rank of the tree the merge is in                        */
+  uint32_t run_first;        /* start of the longest run of consecutive script words in
+                                both coverages, the first one among equals              */
+  uint32_t run_words;        /* its length                                              */
+  uint32_t reserved;         /* 0                                                       */
+} fs_tree_merge;             /* 64 bytes                                                */
+
+typedef struct fs_tree_work {
+  uint32_t covered;          /* |C_w|; 0 for a work without a passage, and then the
+                                other fields are 0xFFFFFFFF (tree, joined_merge, best,
+                                leaf) and 0                                             */
+  uint32_t tree;             /* rank of its tree                                        */
+  uint32_t tree_works;       /* works in its tree                                       */
+  uint32_t edges;            /* merges whose edge ends in the work                      */
+  uint32_t joined_merge;     /* the first of them; 0xFFFFFFFF without one               */
+  uint32_t joined_level;     /* its level; 0 without one                                */
+  uint32_t best;             /* the other end of that edge, which is the work's first
+                                edge in the order; 0xFFFFFFFF without one               */
+  uint32_t leaf;             /* its place in the leaf order                             */
+} fs_tree_work;              /* 32 bytes                                                */
+
+typedef struct fs_tree_level {
+  uint32_t level;            /* a level at which merges happen, the highest first       */
+  uint32_t merges;           /* merges at exactly this level                            */
+  uint32_t merges_above;     /* merges at higher levels                                 */
+  uint32_t families;         /* after every merge at this level or above: families of
+                                two works or more                                       */
+  uint32_t largest;          /* works of the largest of them                            */
+  uint32_t joined;           /* active works in one of them                             */
+  uint32_t singles;          /* active works in none                                    */
+  uint32_t reserved;         /* 0                                                       */
+} fs_tree_level;             /* 32 bytes                                                */
+
+/* Counted against this, with A = the active works and nk = ceil(n_script / 64), before the
+ * work x work product runs:
+ *   the coverage rows        A * nk * 8
+ *   the per-work tables      A * FS_TREE_ROW_BYTES: parent and root (4 bytes each), the work's
+ *                            best edge of a round (8), the best level and the chosen edge of
+ *                            its component (4 and 8), and its slot of the edge list (32)
+ * The records, the run heads, the host's copy of the edges and the outputs are not counted. */
+#define FS_TREE_MAX_BYTES (1u << 30)
+#define FS_TREE_ROW_BYTES 60u
+/* Rounds of the forest's construction after which a call gives up (FS_E_DEVICE): every round
+ * that finds an edge at least halves the families that still have one, so 2^32 works need 32. */
+#define FS_TREE_MAX_ROUNDS 40u
+
+/* Host columns in; works[n_works], `cap_merges` merges in merge order and `cap_levels` levels
+ * out, on HIP device `device`.  Both entry points: FS_E_INVALID for min_words == 0, min_shared
+ * == 0, a measure that is none of the two, min_level > 1000000 under FS_TREE_JACCARD, records
+ * out of (work, fan_ix) order, a work >= n_works or an orig_ix >= n_script; FS_E_UNSUPPORTED
+ * for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT or tables above FS_TREE_MAX_BYTES;
+ * FS_E_CAPACITY with *n_merges and *n_levels = the records required when either capacity is
+ * smaller (works is complete then, merges and levels untouched).  n_rows == 0: works without
+ * coverage, *n_merges = *n_levels = 0 (fs_tree: without device work). */
+int fs_tree(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+            uint64_t n_rows, uint32_t n_works, uint32_t n_script, uint32_t min_words,
+            uint32_t max_gap, uint32_t measure, uint32_t min_shared, uint32_t min_level,
+            fs_tree_work* works, fs_tree_merge* merges, uint64_t cap_merges,
+            uint64_t* n_merges, fs_tree_level* levels, uint64_t cap_levels, uint64_t* n_levels);
+/* The same over device-resident fs_row records (16-byte aligned) into device buffers (16-byte
+ * aligned), n_script taken from the index, on the index's device and stream; returns when
+ * they are written. */
+int fs_tree_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                 uint32_t min_words, uint32_t max_gap, uint32_t measure, uint32_t min_shared,
+                 uint32_t min_level, fs_tree_work* d_works, fs_tree_merge* d_merges,
+                 uint64_t cap_merges, uint64_t* n_merges, fs_tree_level* d_levels,
+                 uint64_t cap_levels, uint64_t* n_levels);
+/* Of the last fs_tree / fs_tree_rows call on this thread, ms[0 .. 8]: HIP-event milliseconds
+ * of the coverage matrix, then summed over the rounds the flatten, best, choose and hook
+ * passes, then the detail pass; host milliseconds of the replay and of the whole call; and in
+ * ms[8] a count, not a time: the hooking rounds, the rounds that added an edge.  0 for a pass
+ * that did not run.  tools/tree_bench.py. */
+int fs_tree_times(double* ms);
+
 /* `ao3.py groups`: the same records reduced by groups of works (a year, an author, a tag).
  * Records, passages and coverage as for fs_pairs.  Membership is many-to-many: work w is in the
  * groups mem_grp[mem_off[w] .. mem_off[w + 1]), strictly ascending (a work may be in none, a
