@@ -156,6 +156,26 @@ assert COMPANION_DTYPE.itemsize == 32
 FS_COMPANIONS_MAX_BYTES = 1 << 30
 COMPANIONS_MS_NAMES = ("incidence", "count", "place", "detail")
 
+# fs_bundle: 64 bytes; fs_bundle_unit: 16 bytes; fs_bundle_level: 24 bytes
+FS_BUNDLES_MAX_SIZE = 8
+FS_BUNDLES_MAX_SETS = 1 << 22
+FS_BUNDLES_MAX_BYTES = 1 << 30
+FS_BUNDLES_TIMES = 32
+BUNDLE_DTYPE = np.dtype([("units", np.uint32, (FS_BUNDLES_MAX_SIZE,)), ("size", np.uint32),
+                         ("works", np.uint32), ("first_work", np.uint32),
+                         ("extensions", np.uint32), ("closed", np.uint32),
+                         ("reserved", np.uint32, (3,))])
+assert BUNDLE_DTYPE.itemsize == 64
+BUNDLE_UNIT_DTYPE = np.dtype([("works", np.uint32), ("sets", np.uint32), ("largest", np.uint32),
+                              ("reserved", np.uint32)])
+assert BUNDLE_UNIT_DTYPE.itemsize == 16
+BUNDLE_LEVEL_DTYPE = np.dtype([("size", np.uint32), ("frequent", np.uint32),
+                               ("candidates", np.uint64), ("closed", np.uint32),
+                               ("maximal", np.uint32)])
+assert BUNDLE_LEVEL_DTYPE.itemsize == 24
+# fs_bundles_times: the two passes in front, four per level of size 3 .. 9, then these two
+BUNDLES_LEVEL_MS_NAMES = ("join", "count", "place", "mark")
+
 # fs_line, fs_line_work, fs_line_cell: 32 bytes each
 LINE_DTYPE = np.dtype([("works", np.uint32), ("whole_works", np.uint32),
                        ("most_works", np.uint32), ("head_works", np.uint32),

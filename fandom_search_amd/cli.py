@@ -32,7 +32,8 @@ more and which the earlier (fandom_search_amd/trends.py), and `neighbours`, whic
 work's closest works by the rare lines both quote (fandom_search_amd/neighbours.py), and
 `misquotes`, which lists the works that share departures from the script
 (fandom_search_amd/misquotes.py), and `tree`, which shows how the families of works merge as
-the bar drops (fandom_search_amd/tree.py).  The
+the bar drops (fandom_search_amd/tree.py), and `bundles`, which lists the sets of stretches
+the same works quote (fandom_search_amd/bundles.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -425,10 +426,10 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`)."""
+    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`, `bundles`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, trends, neighbours, misquotes, tree, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, bundles, trends, neighbours, misquotes, tree, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -725,6 +726,33 @@ def ao3_parser():
                                 'default 6'),
                       _own('--min-level', default=0, type=int,
                            help='smallest level of an edge, default 0')])
+
+    _analysis(subparsers, 'bundles',
+              'lists the sets of quoted regions, scenes or characters that the same '
+              'fan works quote: every set of 2 to --max-size units that at least '
+              '--min-all works quote in full, whether it is closed, the sets '
+              'extending it, per unit the sets holding it, per size the counts',
+              'prefix of the three csv files, PREFIX-bundles.csv, '
+              'PREFIX-bundles-units.csv and PREFIX-bundles-levels.csv (default: the '
+              'input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_all < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-works and --min-all must be at least 1, --max-gap at '
+                'least 0'),
+               (lambda a: not 2 <= a.max_size <= 8, '--max-size must be from 2 to 8')],
+              middle=[_own('--by', default='region', choices=('region', 'scene', 'character'),
+                           help='the units: the quoted regions of `quotes` (default), '
+                                'the scenes or the characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --by region: fewest different works whose passages '
+                              'cover every word of a region, default 1'),
+                    _own('--min-all', default=5, type=int,
+                         help='fewest works quoting every unit of a set, default 5'),
+                    _own('--max-size', default=4, type=int,
+                         help='most units in a listed set, 2 to 8, default 4; the sets '
+                              'of one unit more are mined too and not listed'),
+                    _own('--all', action='store_true',
+                         help='list every frequent set, not only the closed ones')])
     return parser
 
 

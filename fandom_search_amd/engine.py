@@ -606,6 +606,32 @@ class ScriptIndex(object):
                           [abi.COMPANION_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
                           "pair buffer too small")
 
+    def bundles_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
+                       max_gap=0, min_all=5, max_size=4, out_ptrs=None, cap=None):
+        """`bundles` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident unit map of the script's words (fs_bundles_rows): per unit its works and
+        the listed sets holding it, per size 2 .. max_size + 1 the level's counts, and every set
+        of 2 .. max_size units that >= min_all works quote in full, by size, then
+        lexicographically.  Without `out_ptrs`: (abi.BUNDLE_UNIT_DTYPE[n_units],
+        abi.BUNDLE_LEVEL_DTYPE[max_size], abi.BUNDLE_DTYPE[n_sets]) on the host.  With `out_ptrs`
+        = device addresses (units; levels; sets, a buffer of `cap` of them): the number of
+        sets; FsError(FS_E_CAPACITY) with .required when that buffer is too small (the units
+        and the levels are complete then).  Buffers torch has only just produced go in after
+        torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_bundles_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                     C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                     int(max_gap), int(min_all), int(max_size),
+                                     C.c_void_p(fixed[0]), C.c_void_p(fixed[1]),
+                                     C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]))
+        return _rows_call("fs_bundles_rows", call,
+                          [(n_units, abi.BUNDLE_UNIT_DTYPE),
+                           (max(1, int(max_size)), abi.BUNDLE_LEVEL_DTYPE)],
+                          [abi.BUNDLE_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "set buffer too small")
+
     def lines_device(self, rows_ptr, n_rows, n_works, line_first_ptr, n_lines, min_words=6,
                      max_gap=0, most=50, out_ptrs=None, caps=None):
         """`lines` over device-resident fs_row records sorted by (work, fan_ix) and a

@@ -921,6 +921,95 @@ int fs_companions_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint
  * results), place pass, detail pass; 0 for a pass that did not run.  tools/companions_bench.py. */
 int fs_companions_times(double* ms);
 
+/* `ao3.py bundles`: sets of stretches of the script that the same fan works quote, where
+ * fs_companions relates them two at a time.  Records, passages, active works (N of them),
+ * unit_of[n_script], M_u and works(u) as for fs_companions.  A set S is two or more different
+ * units; works(S) = |AND of M_u over S|, the active works quoting every unit of S.  S is frequent
+ * when works(S) >= min_all.  Every frequent set of 2 .. max_size units is listed; the frequent
+ * sets of max_size + 1 units are mined too, used and not listed.
+ *  - extensions(S): the frequent sets with one unit more that hold S.  S is closed when none of
+ *    them has works equal to works(S), maximal when extensions is 0.  Both are exact for every
+ *    listed size, because level max_size + 1 is mined.
+ *  - F_k is the list of the frequent sets of k units, each with its units ascending, in
+ *    lexicographic order.  The candidates of level k + 1 are F_k[i] plus the last unit of F_k[j]
+ *    for i < j where the two agree in their first k - 1 units, taken in (i, j) order, which is
+ *    lexicographic again.  F_2 is the kept pairs of fs_companions under min_both = min_all,
+ *    min_share = 0.
+ *  - A level with more than FS_BUNDLES_MAX_SETS candidates (F_2: kept pairs) ends the call with
+ *    FS_E_UNSUPPORTED before an output is written; the error text names the level and the
+ *    count.  The environment's FS_BUNDLES_MAX_SETS, read on each call, replaces the bound (tests).
+ * Every output is an integer count, a minimum or an OR and every place a scanned count, so no
+ * schedule changes a byte. */
+#define FS_BUNDLES_MAX_SIZE 8u
+#define FS_BUNDLES_MAX_SETS (1u << 22)
+/* What a call keeps in device memory may be up to this: the incidence matrix twice (the tiles
+ * of fs_companions and a unit-major copy, ceil(N / 64) rounded up to 4 words a unit), the level
+ * lists (k + 4 words a set of k units) and the candidate buffers (24 bytes a set of the level
+ * joined and 20 a candidate, of one level at a time). */
+#define FS_BUNDLES_MAX_BYTES (1u << 30)
+#define FS_BUNDLES_TIMES 32
+
+typedef struct fs_bundle {
+  uint32_t units[8];         /* ascending; 0xFFFFFFFF behind the first `size`            */
+  uint32_t size;             /* 2 .. max_size                                           */
+  uint32_t works;            /* works(S)                                                */
+  uint32_t first_work;       /* smallest work number (not active number) among them     */
+  uint32_t extensions;       /* frequent sets of size + 1 units holding S               */
+  uint32_t closed;           /* 1 or 0                                                  */
+  uint32_t reserved[3];      /* 0                                                       */
+} fs_bundle;                 /* 64 bytes                                                */
+
+typedef struct fs_bundle_unit {
+  uint32_t works;            /* |M_u|                                                   */
+  uint32_t sets;             /* listed sets (2 .. max_size units, closed or not) with u */
+  uint32_t largest;          /* the largest size among them; 0 without one              */
+  uint32_t reserved;         /* 0                                                       */
+} fs_bundle_unit;            /* 16 bytes                                                */
+
+typedef struct fs_bundle_level {
+  uint32_t size;             /* 2 .. max_size + 1                                       */
+  uint32_t frequent;         /* |F_size|                                                */
+  uint64_t candidates;       /* joined candidates, before any pruning; size 2: the pairs
+                                of units with works(u) >= min_all                       */
+  uint32_t closed, maximal;  /* of F_size; 0xFFFFFFFF each for size max_size + 1        */
+} fs_bundle_level;           /* 24 bytes                                                */
+
+/* Host columns and the host unit map in; units[n_units], levels[max_size] (sizes 2 ..
+ * max_size + 1) and `cap` sets out, on HIP device `device`.  The sets come by size ascending,
+ * then lexicographically.  Both entry points: FS_E_INVALID for null arguments, min_words == 0,
+ * min_all == 0, max_size outside 2 .. FS_BUNDLES_MAX_SIZE, records out of (work, fan_ix) order,
+ * a work >= n_works, an orig_ix >= n_script or a unit_of entry that is neither below n_units nor
+ * 0xFFFFFFFF; FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT, tables above
+ * FS_BUNDLES_MAX_BYTES (the text names them) or a level above FS_BUNDLES_MAX_SETS, no output
+ * written; FS_E_CAPACITY with *n_sets = sets required when cap is smaller (units and levels are
+ * complete then, sets untouched).  n_rows == 0 or n_units == 0: units and levels of zeros,
+ * *n_sets = 0 (fs_bundles: without device work, the unit map unread).
+ * The count pass takes a parent set's extensions piece by piece: 64 extensions are a
+ * workgroup's work item, so a parent with a thousand extensions is spread over many CUs.
+ * FS_BUNDLES_PRUNE (default 1; 0: off), a diagnostic of the environment read on each call,
+ * drops a candidate before the count when one of its other subsets of the parent's size is not
+ * frequent; the output is the same wherever it stands. */
+int fs_bundles(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+               uint64_t n_rows, uint32_t n_works, uint32_t n_script, const uint32_t* unit_of,
+               uint32_t n_units, uint32_t min_words, uint32_t max_gap, uint32_t min_all,
+               uint32_t max_size, fs_bundle_unit* units, fs_bundle_level* levels,
+               fs_bundle* sets, uint64_t cap, uint64_t* n_sets);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (d_units and d_sets 16-byte, d_levels
+ * 8-byte aligned), on the index's device and stream; returns when they are written. */
+int fs_bundles_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                    const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                    uint32_t max_gap, uint32_t min_all, uint32_t max_size,
+                    fs_bundle_unit* d_units, fs_bundle_level* d_levels, fs_bundle* d_sets,
+                    uint64_t cap, uint64_t* n_sets);
+/* HIP-event milliseconds of the last fs_bundles / fs_bundles_rows call on this thread,
+ * ms[0 .. FS_BUNDLES_TIMES): [0] incidence (with the row popcounts and the unit-major copy), [1]
+ * level 2 (count, scan, place, first works); for the level of size s = 3 .. 9 at [2 + 4 (s - 3)]:
+ * join (with the scans and the candidates' parents and pruning), count, place (with its scan and
+ * the first works), mark; [30] the tally and the records; [31] the total of all before it.  0
+ * for a pass that did not run.  tools/bundles_bench.py. */
+int fs_bundles_times(double* ms);
+
 /* `ao3.py lines`: the lines of the script by how completely the fan works quote them.  Records,
  * passages, active works (works with a passage; N of them, numbered in work order) and the
  * coverage C_w as for fs_pairs.  line_first[n_lines + 1] cuts the script into lines: line l owns
