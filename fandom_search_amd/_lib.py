@@ -28,6 +28,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
            "fs_companions", "fs_companions_rows", "fs_companions_times",
            "fs_bundles", "fs_bundles_rows", "fs_bundles_times",
+           "fs_routes", "fs_routes_rows", "fs_routes_times",
            "fs_lines", "fs_lines_rows", "fs_lines_times",
            "fs_fragments", "fs_fragments_rows", "fs_fragments_times",
            "fs_digest", "fs_digest_rows", "fs_digest_times",
@@ -58,7 +59,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "bundles", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
+TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "bundles", "routes", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
          "clusters", "tree", "groups")
 
 
@@ -227,6 +228,15 @@ def load():
     L.fs_bundles_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_routes.restype = C.c_int
+    L.fs_routes.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                            u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+    L.fs_routes_rows.restype = C.c_int
+    L.fs_routes_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 u64p]
     L.fs_lines.restype = C.c_int
     L.fs_lines.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, u32p,
                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -176,6 +176,28 @@ assert BUNDLE_LEVEL_DTYPE.itemsize == 24
 # fs_bundles_times: the two passes in front, four per level of size 3 .. 9, then these two
 BUNDLES_LEVEL_MS_NAMES = ("join", "count", "place", "mark")
 
+# fs_route: 64 bytes; fs_route_unit: 16 bytes; fs_route_level: 24 bytes
+FS_ROUTES_MAX_LENGTH = 8
+FS_ROUTES_MAX_SKIP = 63
+FS_ROUTES_MAX_SETS = 1 << 22
+FS_ROUTES_MAX_BYTES = 1 << 30
+FS_ROUTES_TIMES = 43
+ROUTE_DTYPE = np.dtype([("units", np.uint32, (FS_ROUTES_MAX_LENGTH,)), ("length", np.uint32),
+                        ("works", np.uint32), ("first_work", np.uint32),
+                        ("prefix_works", np.uint32), ("forward", np.uint32),
+                        ("backward", np.uint32), ("closed", np.uint32),
+                        ("reserved", np.uint32)])
+assert ROUTE_DTYPE.itemsize == 64
+ROUTE_UNIT_DTYPE = np.dtype([("works", np.uint32), ("routes", np.uint32),
+                             ("longest", np.uint32), ("reserved", np.uint32)])
+assert ROUTE_UNIT_DTYPE.itemsize == 16
+ROUTE_LEVEL_DTYPE = np.dtype([("length", np.uint32), ("frequent", np.uint32),
+                              ("candidates", np.uint64), ("closed", np.uint32),
+                              ("reserved", np.uint32)])
+assert ROUTE_LEVEL_DTYPE.itemsize == 24
+# fs_routes_times: the pass in front, five per level of length 2 .. 9, then the records and the total
+ROUTES_LEVEL_MS_NAMES = ("join", "step", "count", "place", "mark")
+
 # fs_line, fs_line_work, fs_line_cell: 32 bytes each
 LINE_DTYPE = np.dtype([("works", np.uint32), ("whole_works", np.uint32),
                        ("most_works", np.uint32), ("head_works", np.uint32),

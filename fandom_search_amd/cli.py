@@ -33,7 +33,8 @@ work's closest works by the rare lines both quote (fandom_search_amd/neighbours.
 `misquotes`, which lists the works that share departures from the script
 (fandom_search_amd/misquotes.py), and `tree`, which shows how the families of works merge as
 the bar drops (fandom_search_amd/tree.py), and `bundles`, which lists the sets of stretches
-the same works quote (fandom_search_amd/bundles.py).  The
+the same works quote (fandom_search_amd/bundles.py), and `routes`, which lists the sequences
+of stretches the works quote in order (fandom_search_amd/routes.py).  The
 reference's scrape / clean / getmeta / vis sub-commands are outside this package
 (out of scope)."""
 
@@ -426,10 +427,11 @@ def full_parser():
 def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
-    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`, `bundles`)."""
+    `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`, `bundles`,
+    `routes`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, bundles, trends, neighbours, misquotes, tree, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, bundles, routes, trends, neighbours, misquotes, tree, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -753,6 +755,39 @@ def ao3_parser():
                               'of one unit more are mined too and not listed'),
                     _own('--all', action='store_true',
                          help='list every frequent set, not only the closed ones')])
+
+    _analysis(subparsers, 'routes',
+              'lists the sequences of quoted regions, scenes or characters that the '
+              'fan works quote in that order: every route of 2 to --max-length units '
+              'that at least --min-all works follow, whether it is closed, the routes '
+              'continuing it, per unit the routes holding it, per length the counts',
+              'prefix of the three csv files, PREFIX-routes.csv, '
+              'PREFIX-routes-units.csv and PREFIX-routes-levels.csv (default: the '
+              'input name without .csv)',
+              [(lambda a: (a.min_words < 1 or a.min_works < 1 or a.min_all < 1
+                           or a.max_gap < 0),
+                '--min-words, --min-works and --min-all must be at least 1, --max-gap at '
+                'least 0'),
+               (lambda a: not 2 <= a.max_length <= 8, '--max-length must be from 2 to 8'),
+               (lambda a: a.max_skip is not None and not 0 <= a.max_skip <= 63,
+                '--max-skip must be from 0 to 63')],
+              middle=[_own('--by', default='region', choices=('region', 'scene', 'character'),
+                           help='the units: the quoted regions of `quotes` (default), '
+                                'the scenes or the characters of the script')],
+              last=[_own('--min-works', default=1, type=int,
+                         help='with --by region: fewest different works whose passages '
+                              'cover every word of a region, default 1'),
+                    _own('--min-all', default=5, type=int,
+                         help='fewest works following a route, default 5'),
+                    _own('--max-length', default=4, type=int,
+                         help='most units in a listed route, 2 to 8, default 4; the '
+                              'routes of one unit more are mined too and not listed'),
+                    _own('--max-skip', default=None, type=int,
+                         help='most other elements of a work\'s sequence between two '
+                              'units of a route, 0 to 63; 0: the route is a contiguous '
+                              'run; default: any distance'),
+                    _own('--all', action='store_true',
+                         help='list every frequent route, not only the closed ones')])
     return parser
 
 

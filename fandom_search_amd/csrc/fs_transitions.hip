@@ -12,7 +12,8 @@
 // (steps << 32 | ~b), which holds the tie rule; and the cells' places come from scanned counts
 // and from counting the cells in front, never from arrival.
 //
-// Separate launches; no workgroup waits on another:
+// Separate launches; no workgroup waits on another (the first four are fs_sequence.h, which
+// fs_routes.hip shares):
 //   k_tr_check     one lane per record: work < n_works, orig_ix < n_script
 //   k_tr_units_ok  one lane per script word: a unit number that is neither < n_units nor none
 //   (fs_runs_find) the run heads, as fs_passages joins them
@@ -35,9 +36,8 @@
 //   k_tr_scatter   one lane per cell index: a kept cell to a free place of its unit's range
 //   k_tr_rank      one lane per kept cell: the cells of its unit with a smaller b are its place;
 //                  a unit of more than kLong kept cells is counted by the whole wave
-#include "fs_internal.h"
 #include "fs_probe.h"
-#include "fs_prims.h"
+#include "fs_sequence.h"
 
 namespace {
 
@@ -48,25 +48,13 @@ constexpr uint32_t kLong = 64;              // units of more kept cells are rank
 
 static_assert(sizeof(fs_transition_unit) == 40 && sizeof(fs_transition) == 32, "fs_transitions");
 
-// status words
-enum { kStBadRecord = 0, kStBadUnit = 1, kStSeq = 2, kStWords = 4 };
 // per-unit figures counted by k_tr_count, [figure][unit]
 enum { kUPassages = 0, kUWorks, kUStarts, kUEnds, kUOut, kUIn, kUFigures };
 // per-cell figures; the smallest work is kept as the largest ~work, 0 for none
 enum { kCSteps = 0, kCAdvances, kCWorks, kCFirst, kCFigures };
 
-struct TrArgs {
-  const uint32_t* heads;         // [n_runs + 1]
-  const uint32_t* unit_of;       // [n_script]
-  uint32_t n, n_runs, n_works, n_script, n_units, n_seq;
-  uint32_t min_words, within, min_steps, min_step_works, min_share;
-  uint32_t* cnt;                 // [workgroups of runs] listed runs, then their exclusive scan
-  uint32_t* work;                // [n_seq] each: the sequence elements in record order
-  uint32_t* ff;
-  uint32_t* fl;
-  uint32_t* of;
-  uint32_t* ol;
-  uint32_t* unit;
+struct TrArgs : SeqArgs {        // the records and the sequence: fs_sequence.h
+  uint32_t within, min_steps, min_step_works, min_share;
   uint64_t mask;                 // slots - 1 of each table
   uint64_t hash_mask;            // FS_TRANSITIONS_HASH_BITS: the bits of a key's hash kept
   uint64_t n_index;              // cell indices: n_units^2 (dense) or slots (hashed)
@@ -81,77 +69,10 @@ struct TrArgs {
   uint32_t* cursor;
   unsigned long long* best;      // [n_units] steps << 32 | ~b of the best kept cell
   unsigned long long* total;     // kept cells
-  uint32_t* status;
   fs_transition_unit* units;
   fs_transition* tmp;            // the kept cells, unit by unit, unranked
   fs_transition* cells;
 };
-
-__global__ __launch_bounds__(kBlock) void k_tr_check(RowsSrc src, TrArgs a) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  bool bad = false;
-  if (i < a.n) {
-    const uint4 k = src.key(i);
-    bad = k.x >= a.n_works || k.z >= a.n_script;
-  }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.status[kStBadRecord], 1u);
-}
-
-__global__ __launch_bounds__(kBlock) void k_tr_units_ok(TrArgs a) {
-  const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
-  bool bad = false;
-  if (o < a.n_script) {
-    const uint32_t u = a.unit_of[o];
-    bad = u != FS_NONE && u >= a.n_units;
-  }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.status[kStBadUnit], 1u);
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_tr_scan(const uint32_t* in, uint32_t* out,
-                                                        uint32_t n, unsigned long long* total32,
-                                                        uint32_t* total) {
-  __shared__ unsigned long long s_total;
-  scan_array<uint32_t, unsigned long long>(in, n, out, &s_total);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (total32) *total32 = s_total;
-    if (total) *total = (uint32_t)s_total;
-  }
-}
-
-// kPlace false: the kept runs with a unit of this workgroup's 256 runs into cnt; true: those
-// runs to their places, cnt holding the scan.  (Every orig_ix is below n_script here:
-// k_tr_check found nothing.)
-template <bool kPlace>
-__global__ __launch_bounds__(kBlock) void k_tr_seq(RowsSrc src, TrArgs a) {
-  __shared__ uint32_t s_w[kBlock / 64];
-  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
-  uint32_t b = 0, e = 0, u = FS_NONE;
-  uint4 x = make_uint4(0u, 0u, 0u, 0u);
-  if (r < a.n_runs) {
-    b = a.heads[r];
-    e = a.heads[r + 1];
-    if (e - b >= a.min_words) {
-      x = src.key(b);
-      u = a.unit_of[x.z];
-    }
-  }
-  const bool keep = u != FS_NONE;
-  uint32_t rank, total;
-  block_rank<kBlock>(keep, s_w, &rank, &total);
-  if (!kPlace) {
-    if (threadIdx.x == 0) a.cnt[blockIdx.x] = total;
-  } else if (keep) {
-    const uint32_t p = a.cnt[blockIdx.x] + rank;
-    const uint4 y = src.key(e - 1);
-    a.work[p] = x.x;
-    a.ff[p] = x.y;
-    a.fl[p] = y.y;
-    a.of[p] = x.z;
-    a.ol[p] = y.z;
-    a.unit[p] = u;
-  }
-}
 
 // the slot of `key` in `tab`; true when this call put it there
 __device__ inline bool set_insert(const TrArgs& a, unsigned long long* tab, unsigned long long key,
@@ -318,16 +239,15 @@ uint64_t tr_hash_mask() {
 
 // one call: count() through the per-unit results and the number of kept cells, then write()
 struct TrJob {
-  DBuf<uint32_t> status, cnt, seq, ufig;
+  SeqJob sq;
+  DBuf<uint32_t> ufig;
   DBuf<unsigned long long> cell_tab, cw_tab, uw_tab, best, total;
   DBuf<uint4> cell_cnt;
   DBuf<fs_transition> tmp;
-  fs_runs* runs = nullptr;
   Clock<6> clk;
   TrArgs a{};
   bool dense = false;
   uint64_t n_cells = 0;
-  ~TrJob() { if (runs) fs_runs_free(runs); }
 
   int none(hipStream_t s) {
     if (a.n_units)
@@ -344,7 +264,6 @@ struct TrJob {
             uint32_t within, uint32_t min_steps, uint32_t min_step_works, uint32_t min_share,
             fs_transition_unit* d_units, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
-    const RowsSrc src{d_rows};
     a.n = n;
     a.n_works = n_works;
     a.n_script = n_script;
@@ -357,53 +276,11 @@ struct TrJob {
     a.min_share = min_share;
     a.units = d_units;
     if (!n || !n_units) return none(s);
-    if (!n_works || !n_script) {
-      fs_set_error("a work >= n_works or an orig_ix >= n_script");
-      return FS_E_INVALID;
-    }
     const dim3 blk(kBlock);
-    FS_TRY(status.reserve(kStWords));
-    FS_HIP(hipMemsetAsync(status.p, 0, kStWords * sizeof(uint32_t), s));
-    a.status = status.p;
     FS_TRY(clk.mark(0, s));
-    hipLaunchKernelGGL(k_tr_check, dim3(blocks_of(n, kBlock)), blk, 0, s, src, a);
-    hipLaunchKernelGGL(k_tr_units_ok, dim3(blocks_of(n_script, kBlock)), blk, 0, s, a);
-    FS_HIP(hipGetLastError());
-    FS_TRY(fs_runs_find(d_rows, n, min_words, max_gap, s, &runs, &a.heads, &a.n_runs));
-    uint32_t st[kStWords];
-    FS_HIP(hipMemcpyAsync(st, status.p, sizeof st, hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    if (st[kStBadRecord]) {
-      fs_set_error("a work >= n_works (%u) or an orig_ix >= n_script (%u)", n_works, n_script);
-      return FS_E_INVALID;
-    }
-    if (st[kStBadUnit]) {
-      fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF", n_units);
-      return FS_E_INVALID;
-    }
-
-    // the sequence elements, in record order
-    const uint32_t run_blocks = blocks_of(a.n_runs, kBlock);
-    FS_TRY(cnt.reserve(run_blocks));
-    a.cnt = cnt.p;
-    if (run_blocks) hipLaunchKernelGGL((k_tr_seq<false>), dim3(run_blocks), blk, 0, s, src, a);
-    hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.cnt, run_blocks,
-                       (unsigned long long*)nullptr, a.status + kStSeq);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(st, status.p, sizeof st, hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    a.n_seq = st[kStSeq];
+    FS_TRY(sq.list(d_rows, a, max_gap, s));
     if (!a.n_seq) return none(s);
     const size_t m = a.n_seq, nu = n_units;
-    FS_TRY(seq.reserve(6 * m));
-    a.work = seq.p;
-    a.ff = seq.p + m;
-    a.fl = seq.p + 2 * m;
-    a.of = seq.p + 3 * m;
-    a.ol = seq.p + 4 * m;
-    a.unit = seq.p + 5 * m;
-    hipLaunchKernelGGL((k_tr_seq<true>), dim3(run_blocks), blk, 0, s, src, a);
-    FS_HIP(hipGetLastError());
     FS_TRY(clk.mark(1, s));
 
     // the figures.  FS_TRANSITIONS_DENSE: a diagnostic, read on each call

@@ -632,6 +632,34 @@ class ScriptIndex(object):
                           [abi.BUNDLE_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
                           "set buffer too small")
 
+    def routes_device(self, rows_ptr, n_rows, n_works, unit_of_ptr, n_units, min_words=6,
+                      max_gap=0, max_skip=abi.FS_NONE, min_all=5, max_length=4, out_ptrs=None,
+                      cap=None):
+        """`routes` over device-resident fs_row records sorted by (work, fan_ix) and a
+        device-resident unit map of the script's words (fs_routes_rows): per unit its works and
+        the listed routes holding it, per length 2 .. max_length + 1 the level's counts, and
+        every route of 2 .. max_length units that >= min_all works quote in that order, at most
+        max_skip elements between two of its units (abi.FS_NONE: any distance), by length, then
+        lexicographically.  Without `out_ptrs`: (abi.ROUTE_UNIT_DTYPE[n_units],
+        abi.ROUTE_LEVEL_DTYPE[max_length], abi.ROUTE_DTYPE[n_routes]) on the host.  With
+        `out_ptrs` = device addresses (units; levels; routes, a buffer of `cap` of them): the
+        number of routes; FsError(FS_E_CAPACITY) with .required when that buffer is too small
+        (the units and the levels are complete then).  Buffers torch has only just produced go
+        in after torch_ready()."""
+        L = _lib.load()
+
+        def call(fixed, grown, caps, counts):
+            return L.fs_routes_rows(self._h, C.c_void_p(rows_ptr), int(n_rows), int(n_works),
+                                    C.c_void_p(unit_of_ptr), int(n_units), int(min_words),
+                                    int(max_gap), int(max_skip), int(min_all), int(max_length),
+                                    C.c_void_p(fixed[0]), C.c_void_p(fixed[1]),
+                                    C.c_void_p(grown[0]), int(caps[0]), C.byref(counts[0]))
+        return _rows_call("fs_routes_rows", call,
+                          [(n_units, abi.ROUTE_UNIT_DTYPE),
+                           (max(1, int(max_length)), abi.ROUTE_LEVEL_DTYPE)],
+                          [abi.ROUTE_DTYPE], [_first_cap(cap, out_ptrs, 4096)], out_ptrs,
+                          "route buffer too small")
+
     def lines_device(self, rows_ptr, n_rows, n_works, line_first_ptr, n_lines, min_words=6,
                      max_gap=0, most=50, out_ptrs=None, caps=None):
         """`lines` over device-resident fs_row records sorted by (work, fan_ix) and a

@@ -1010,6 +1010,109 @@ int fs_bundles_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_
  * for a pass that did not run.  tools/bundles_bench.py. */
 int fs_bundles_times(double* ms);
 
+/* `ao3.py routes`: sequences of stretches of the script that the fan works quote in that order,
+ * the ordered counterpart of fs_bundles, where fs_transitions relates the units one step at a
+ * time.  Records, passages (min_words, max_gap), unit_of[n_script] and n_units as for
+ * fs_transitions; a passage's unit is unit_of[orig_first], and a passage without a unit is left
+ * out before anything else.
+ *  - Sequence: a work's unit-bearing passages in record order, consecutive passages of one unit
+ *    written once; in s_1 .. s_m neighbours always differ.  A work with m < 2 supports no route.
+ *  - Route: P = (a_1 .. a_k), 2 <= k <= max_length, a_i != a_i+1; a unit may come back.
+ *  - A work supports P when there are p_1 < ... < p_k with s_{p_i} = a_i and p_i+1 - p_i <=
+ *    max_skip + 1 for every i.  max_skip is 0 .. FS_ROUTES_MAX_SKIP elements of the sequence
+ *    between two units of the route (0: a contiguous run), or 0xFFFFFFFF for any distance.
+ *  - works(P) is the number of supporting works; P is frequent when works(P) >= min_all.
+ *  - F_1 is the units u with works(u) >= min_all, works(u) counting the works with m >= 2 whose
+ *    sequence holds u.  F_k is kept in lexicographic order.  The candidates of level k + 1 are
+ *    F_k[i] plus the last unit of F_k[j] for every j whose first k - 1 units are the last k - 1
+ *    of F_k[i] (k = 1: every ordered pair of different frequent units); those j are one
+ *    contiguous range, so candidates in (i, j) order are lexicographic again.  The join is
+ *    complete under every max_skip, because a contiguous part of a supported route is supported;
+ *    nothing else is pruned, because under a bounded skip dropping a middle unit does not keep
+ *    support.
+ *  - Levels 2 .. max_length + 1 are mined, 2 .. max_length listed.  forward(P): the frequent
+ *    routes P + b; backward(P): the frequent routes a + P; P is closed when none of those has
+ *    works equal to works(P), exact for every listed length.  prefix_works(P): the works of P
+ *    without its last unit (k = 2: works(a_1)).
+ *  - A level with more than FS_ROUTES_MAX_SETS candidates ends the call with FS_E_UNSUPPORTED
+ *    before an output is written; the error text names the level and the count.  The
+ *    environment's FS_ROUTES_MAX_SETS, read on each call, replaces the bound (tests).
+ * Every output is an integer count, a minimum or an OR and every place a scanned count, so no
+ * schedule changes a byte. */
+#define FS_ROUTES_MAX_LENGTH 8u
+#define FS_ROUTES_MAX_SKIP 63u
+#define FS_ROUTES_MAX_SETS (1u << 22)
+/* What a call keeps in device memory may be up to this.  With E the elements of all sequences
+ * of two or more and a row ceil(E / 64) 64-bit words: the heads, the tails, the unit and the
+ * work of every position, the set behind works(u) and a row per frequent unit; a row per route
+ * of two adjacent levels at a time; the level lists (k + 8 words a route of k units) and the
+ * candidate buffers (28 bytes a route of the level joined, 12 a slice of its rows and 16 a
+ * candidate, of one level at a time). */
+#define FS_ROUTES_MAX_BYTES (1u << 30)
+#define FS_ROUTES_TIMES 43
+
+typedef struct fs_route {
+  uint32_t units[8];         /* in route order; 0xFFFFFFFF behind the first `length`     */
+  uint32_t length;           /* 2 .. max_length                                         */
+  uint32_t works;            /* works(P)                                                */
+  uint32_t first_work;       /* smallest supporting work number                         */
+  uint32_t prefix_works;     /* works of P without its last unit                        */
+  uint32_t forward;          /* frequent routes P + b                                   */
+  uint32_t backward;         /* frequent routes a + P                                   */
+  uint32_t closed;           /* 1 or 0                                                  */
+  uint32_t reserved;         /* 0                                                       */
+} fs_route;                  /* 64 bytes                                                */
+
+typedef struct fs_route_unit {
+  uint32_t works;            /* works with m >= 2 whose sequence holds u                */
+  uint32_t routes;           /* listed routes (closed or not) holding u, each once      */
+  uint32_t longest;          /* the largest length among them; 0 without one            */
+  uint32_t reserved;         /* 0                                                       */
+} fs_route_unit;             /* 16 bytes                                                */
+
+typedef struct fs_route_level {
+  uint32_t length;           /* 2 .. max_length + 1                                     */
+  uint32_t frequent;         /* |F_length|                                              */
+  uint64_t candidates;       /* joined candidates                                       */
+  uint32_t closed;           /* of F_length; 0xFFFFFFFF for length max_length + 1       */
+  uint32_t reserved;         /* 0                                                       */
+} fs_route_level;            /* 24 bytes                                                */
+
+/* Host columns and the host unit map in; units[n_units], levels[max_length] (lengths 2 ..
+ * max_length + 1) and `cap` routes out, on HIP device `device`.  The routes come by length
+ * ascending, then lexicographically.  Both entry points: FS_E_INVALID for null arguments,
+ * min_words == 0, min_all == 0, max_length outside 2 .. FS_ROUTES_MAX_LENGTH, max_skip in
+ * FS_ROUTES_MAX_SKIP + 1 .. 0xFFFFFFFE, records out of (work, fan_ix) order, a work >= n_works,
+ * an orig_ix >= n_script or a unit_of entry that is neither below n_units nor 0xFFFFFFFF;
+ * FS_E_UNSUPPORTED for n_rows >= 2^32, n_script > FS_WORKS_MAX_SCRIPT, tables above
+ * FS_ROUTES_MAX_BYTES (the text names them) or a level above FS_ROUTES_MAX_SETS, no output
+ * written; FS_E_CAPACITY with *n_routes = routes required when cap is smaller (units and levels
+ * are complete then, routes untouched).  n_rows == 0 or n_units == 0: units and levels of
+ * zeros, *n_routes = 0 (fs_routes: without device work, the unit map unread).
+ * The rows are stepped and counted in slices of FS_ROUTES_SLICE_WORDS 64-bit words (default and
+ * most 256), a diagnostic of the environment read on each call; a work whose sequence spans
+ * slices is carried across them, and the output is the same wherever it stands.  The count pass
+ * takes a route's extensions piece by piece, 64 a workgroup's work item. */
+int fs_routes(int device, const uint32_t* work, const uint32_t* fan_ix, const uint32_t* orig_ix,
+              uint64_t n_rows, uint32_t n_works, uint32_t n_script, const uint32_t* unit_of,
+              uint32_t n_units, uint32_t min_words, uint32_t max_gap, uint32_t max_skip,
+              uint32_t min_all, uint32_t max_length, fs_route_unit* units,
+              fs_route_level* levels, fs_route* routes, uint64_t cap, uint64_t* n_routes);
+/* The same over device-resident fs_row records (16-byte aligned) and a device-resident unit map
+ * of the index's n_script entries into device buffers (d_units and d_routes 16-byte, d_levels
+ * 8-byte aligned), on the index's device and stream; returns when they are written. */
+int fs_routes_rows(fs_index* ix, const fs_row* d_rows, uint64_t n_rows, uint32_t n_works,
+                   const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words,
+                   uint32_t max_gap, uint32_t max_skip, uint32_t min_all, uint32_t max_length,
+                   fs_route_unit* d_units, fs_route_level* d_levels, fs_route* d_routes,
+                   uint64_t cap, uint64_t* n_routes);
+/* HIP-event milliseconds of the last fs_routes / fs_routes_rows call on this thread,
+ * ms[0 .. FS_ROUTES_TIMES): [0] the sequence, the positions and the rows of the units; for the
+ * level of length l = 2 .. 9 at [1 + 5 (l - 2)]: join, step, count, place (with its scan, the
+ * rows and the first works), mark; [41] the tally and the records; [42] the total of all before
+ * it.  0 for a pass that did not run.  tools/routes_bench.py. */
+int fs_routes_times(double* ms);
+
 /* `ao3.py lines`: the lines of the script by how completely the fan works quote them.  Records,
  * passages, active works (works with a passage; N of them, numbered in work order) and the
  * coverage C_w as for fs_pairs.  line_first[n_lines + 1] cuts the script into lines: line l owns
