@@ -8,8 +8,7 @@
 // Every output is an integer count, a minimum or an OR, and every place comes from a scanned
 // count, so no schedule changes a byte.  Separate launches on one stream; no workgroup waits
 // on another:
-//   incidence        k_comp_units_ok, CoverJob::number, k_pairs_list, k_comp_incidence and
-//                    k_pairs_covered as fs_companions.hip runs them, then
+//   incidence        IncJob of fs_incidence.h: M and works(u), then
 //   k_bun_rows       the unit-major copy of M, [unit][nkp] with nkp = ceil(N / 64) rounded up to
 //                    four words: the count pass reads the rows of arbitrary units, and the tiled
 //                    layout keeps a row's words 512 bytes apart
@@ -386,10 +385,9 @@ struct LevelBufs {
 
 // one call: mine() through the units, the levels and the number of sets, then write()
 struct BunJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, uworks, cnt, any, bad, n_cand, n_item, parent, dead, count, keep, pos,
-      stats;
-  DBuf<unsigned long long> mat, rows, off, cand_off, item_off, totals;
+  IncJob inc;
+  DBuf<uint32_t> cnt, any, n_cand, n_item, parent, dead, count, keep, pos, stats;
+  DBuf<unsigned long long> rows, off, cand_off, item_off, totals;
   DBuf<fs_bundle_unit> units;       // the caller's are written when nothing can refuse any more
   LevelBufs lv[kMaxSize + 2];       // by size
   BunLevel f[kMaxSize + 2] = {};
@@ -397,7 +395,6 @@ struct BunJob {
   BunArgs a{};
   uint32_t max_size = 0;
   uint64_t n_sets = 0, max_sets = 0, bytes = 0, scratch = 0;
-  uint32_t bad_units = 0;
   fs_bundle_level levels[kMaxSize] = {};     // sizes 2 .. max_size + 1
 
   void blank_levels() {
@@ -444,87 +441,50 @@ struct BunJob {
     for (double& t : t_ms) t = 0.0;
     max_size = k_max;
     blank_levels();
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.min_all = min_all;
     if (!n || !n_units) return none(d_units, s);
     max_sets = env_u32("FS_BUNDLES_MAX_SETS", FS_BUNDLES_MAX_SETS, 1u << 26);
     const uint32_t prune = env_u32("FS_BUNDLES_PRUNE", 1u, 1u);
-    // the unit map's check rides in front of number(), which waits for the stream
-    FS_TRY(bad.reserve(1));
-    FS_HIP(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-    if (n_script)
-      hipLaunchKernelGGL(k_comp_units_ok, dim3(blocks_of(n_script, kRunBlock)), dim3(kRunBlock),
-                         0, s, d_unit_of, n_script, n_units, bad.p);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-    const int rc = cj.number(d_rows, a.r, max_gap, s);
-    FS_HIP(hipStreamSynchronize(s));
-    if (rc != FS_OK) return rc;
-    if (bad_units) {
-      fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF", n_units);
-      return FS_E_INVALID;
-    }
+    FS_TRY(inc.number(d_rows, a, max_gap, s));
     if (!a.r.n_active) return none(d_units, s);
-    const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-    const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64, nkp = (nk + 3) / 4 * 4;
-    if (u_tiles * kTile * nk * 8 + (uint64_t)n_units * nkp * 8 > FS_BUNDLES_MAX_BYTES) {
+    const uint64_t nkp = ((uint64_t)a.m.nk + 3) / 4 * 4;
+    bytes = IncJob::mat_bytes(a) + (uint64_t)n_units * nkp * 8;
+    if (bytes > FS_BUNDLES_MAX_BYTES) {
       fs_set_error("%u units over %u works with a passage: the incidence matrix and its "
                    "unit-major copy come to more than %u bytes", n_units, a.r.n_active,
                    FS_BUNDLES_MAX_BYTES);
       return FS_E_UNSUPPORTED;
     }
-    bytes = u_tiles * kTile * nk * 8 + (uint64_t)n_units * nkp * 8;
-    a.m.nk = (uint32_t)nk;
     a.nkp = (uint32_t)nkp;
-    a.m.n_tiles = (uint32_t)u_tiles;
-    a.m.n_chunks = (a.m.n_tiles + kChunk - 1) / kChunk;
-    a.m.n_active = n_units;
     const size_t rows_n = (size_t)a.m.n_tiles * kTile, cells = rows_n * a.m.n_chunks;
     const uint64_t blocks = (uint64_t)a.m.n_tiles * a.m.n_chunks;
     if (blocks > 0x7FFFFFFFull || (uint64_t)n_units * nkp > 0x7FFFFFFFull * kRunBlock) {
       fs_set_error("%u units: more tiles of pairs than a launch takes", n_units);
       return FS_E_UNSUPPORTED;
     }
-    const size_t a_rows = (size_t)a.r.n_tiles * kTile;     // active numbers, padded
-    FS_TRY(work_of.reserve(a_rows));
-    FS_TRY(mat.reserve(rows_n * nk));
+    FS_TRY(inc.reserve(a, true, s));
     FS_TRY(rows.reserve((size_t)n_units * nkp));
-    FS_TRY(uworks.reserve(rows_n));
     FS_TRY(cnt.reserve(cells));
     FS_TRY(off.reserve(cells));
     FS_TRY(any.reserve((size_t)blocks));
     FS_TRY(totals.reserve(2));
     FS_TRY(stats.reserve(2 * (kMaxSize + 2)));
     FS_TRY(units.reserve(n_units));
-    FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-    FS_HIP(hipMemsetAsync(mat.p, 0, rows_n * nk * sizeof(unsigned long long), s));
     FS_HIP(hipMemsetAsync(cnt.p, 0, cells * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(any.p, 0, (size_t)blocks * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(stats.p, 0, 2 * (kMaxSize + 2) * sizeof(uint32_t), s));
-    a.r.work_of = work_of.p;
-    a.m.cov = mat.p;
-    a.m.covered = uworks.p;
     a.rows = rows.p;
     a.cnt = cnt.p;
     a.off = off.p;
     a.any = any.p;
     const dim3 blk(kRunBlock);
     FS_TRY(clk.mark(0, s));
-    hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
-                       cj.flag.p);
-    hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                       RowsSrc{d_rows}, a, cj.flag.p);
-    hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
+    inc.incidence(d_rows, a, s);
     hipLaunchKernelGGL(k_bun_rows, dim3(blocks_of((uint64_t)n_units * nkp, kRunBlock)), blk, 0,
                        s, a, rows.p);
     hipLaunchKernelGGL(k_bun_units, dim3(blocks_of(n_units, kRunBlock)), blk, 0, s,
-                       (const uint32_t*)uworks.p, units.p, n_units);
+                       (const uint32_t*)a.m.covered, units.p, n_units);
     FS_TRY(clk.mark(1, s));
     // level 2: stats[0] is borrowed for the number of units with works >= min_all
     hipLaunchKernelGGL(k_bun_singles, dim3(blocks_of(n_units, kRunBlock)), blk, 0, s, a,
@@ -658,7 +618,7 @@ struct BunJob {
     for (uint32_t k = 2; k <= max_size; ++k) {
       if (!f[k].n) continue;
       hipLaunchKernelGGL(k_bun_emit, dim3(blocks_of(f[k].n, kRunBlock)), dim3(kRunBlock), 0, s,
-                         f[k], (const uint32_t*)work_of.p, a.r.n_active, d_sets, base);
+                         f[k], (const uint32_t*)a.r.work_of, a.r.n_active, d_sets, base);
       base += f[k].n;
     }
     FS_TRY(clk.mark(46, s));

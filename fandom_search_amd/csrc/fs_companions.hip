@@ -6,6 +6,7 @@
 //
 // Every output is an integer, so partial results merge in any order.  Separate launches; no
 // workgroup waits on another:
+//   incidence        IncJob of fs_incidence.h, which the other units over M share:
 //   k_comp_units_ok  one lane per script word: a unit number that is neither < n_units nor none
 //   CoverJob::number the run heads, the check of every record, the active works numbered
 //   k_pairs_list     one lane per work: the work of an active number
@@ -23,7 +24,7 @@
 // M is stored as fs_tiles.h stores the coverage matrix, [tile of 64 units][k][64] with k over
 // the 64-bit words of the active works, so tile_counts runs on it through a CoverArgs whose cov,
 // nk and n_tiles describe M.  Rows past n_units are zero and are never kept (min_both >= 1).
-// k_comp_units_ok and k_comp_incidence live in fs_incidence.h, which fs_intervals.hip shares.
+// k_comp_units_ok, k_comp_incidence and the host sequence around them live in fs_incidence.h.
 #include "fs_incidence.h"
 
 namespace {
@@ -182,13 +183,12 @@ thread_local double t_ms[4];    // incidence, count, place, detail of the last c
 
 // one call: count() through the per-unit results and the number of pairs, then write()
 struct CompJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, uworks, partners, cnt, any, bad;
-  DBuf<unsigned long long> mat, best, off, total;
+  IncJob inc;
+  DBuf<uint32_t> partners, cnt, any;
+  DBuf<unsigned long long> best, off, total;
   Clock<8> clk;
   CompArgs a{};
   uint64_t n_pairs = 0;
-  uint32_t bad_units = 0;
 
   int none(hipStream_t s) {
     if (a.n_units)
@@ -204,69 +204,35 @@ struct CompJob {
             const uint32_t* d_unit_of, uint32_t n_units, uint32_t min_words, uint32_t max_gap,
             uint32_t min_both, uint32_t min_share, fs_companion_unit* d_units, hipStream_t s) {
     for (double& t : t_ms) t = 0.0;
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.min_both = min_both;
     a.min_share = min_share;
     a.units = d_units;
     if (!n || !n_units) return none(s);
-    // the unit map's check rides in front of number(), which waits for the stream
-    FS_TRY(bad.reserve(1));
-    FS_HIP(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-    if (n_script)
-      hipLaunchKernelGGL(k_comp_units_ok, dim3((n_script + kRunBlock - 1) / kRunBlock),
-                         dim3(kRunBlock), 0, s, d_unit_of, n_script, n_units, bad.p);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-    const int rc = cj.number(d_rows, a.r, max_gap, s);
-    FS_HIP(hipStreamSynchronize(s));
-    if (rc != FS_OK) return rc;
-    if (bad_units) {
-      fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF", n_units);
-      return FS_E_INVALID;
-    }
+    FS_TRY(inc.number(d_rows, a, max_gap, s));
     if (!a.r.n_active) return none(s);
-    const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-    const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64;
-    if (u_tiles * kTile * nk * 8 > FS_COMPANIONS_MAX_BYTES) {
+    if (IncJob::mat_bytes(a) > FS_COMPANIONS_MAX_BYTES) {
       fs_set_error("%u units over %u works with a passage: an incidence matrix of more than %u "
                    "bytes", n_units, a.r.n_active, FS_COMPANIONS_MAX_BYTES);
       return FS_E_UNSUPPORTED;
     }
-    a.m.nk = (uint32_t)nk;
-    a.m.n_tiles = (uint32_t)u_tiles;
-    a.m.n_chunks = (a.m.n_tiles + kChunk - 1) / kChunk;
-    a.m.n_active = n_units;
     const size_t rows = (size_t)a.m.n_tiles * kTile, cells = rows * a.m.n_chunks;
     const uint64_t blocks = (uint64_t)a.m.n_tiles * a.m.n_chunks;
     if (blocks > 0x7FFFFFFFull) {
       fs_set_error("%u units: more tiles of pairs than a launch takes", n_units);
       return FS_E_UNSUPPORTED;
     }
-    const size_t a_rows = (size_t)a.r.n_tiles * kTile;     // active numbers, padded
-    FS_TRY(work_of.reserve(a_rows));
-    FS_TRY(mat.reserve(rows * nk));
-    FS_TRY(uworks.reserve(rows));
+    FS_TRY(inc.reserve(a, true, s));
     FS_TRY(partners.reserve(rows));
     FS_TRY(best.reserve(rows));
     FS_TRY(cnt.reserve(cells));
     FS_TRY(off.reserve(cells));
     FS_TRY(any.reserve((size_t)blocks));
     FS_TRY(total.reserve(1));
-    FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-    FS_HIP(hipMemsetAsync(mat.p, 0, rows * nk * sizeof(unsigned long long), s));
     FS_HIP(hipMemsetAsync(partners.p, 0, rows * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(best.p, 0, rows * sizeof(unsigned long long), s));
     FS_HIP(hipMemsetAsync(cnt.p, 0, cells * sizeof(uint32_t), s));
     FS_HIP(hipMemsetAsync(any.p, 0, (size_t)blocks * sizeof(uint32_t), s));
-    a.r.work_of = work_of.p;
-    a.m.cov = mat.p;
-    a.m.covered = uworks.p;
     a.partners = partners.p;
     a.best = best.p;
     a.cnt = cnt.p;
@@ -275,11 +241,7 @@ struct CompJob {
     a.total = total.p;
     const dim3 blk(kRunBlock);
     FS_TRY(clk.mark(0, s));
-    hipLaunchKernelGGL(k_pairs_list, dim3((n_works + kRunBlock - 1) / kRunBlock), blk, 0, s, a.r,
-                       cj.flag.p);
-    hipLaunchKernelGGL(k_comp_incidence, dim3((a.r.n_runs + kRunBlock - 1) / kRunBlock), blk, 0,
-                       s, RowsSrc{d_rows}, a, cj.flag.p);
-    hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
+    inc.incidence(d_rows, a, s);
     FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_comp_tiles<0>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_pairs_scan<unsigned long long>, dim3(1), dim3(kScanBlock), 0, s, cnt.p,

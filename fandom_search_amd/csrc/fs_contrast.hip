@@ -9,8 +9,7 @@
 // Every output is an integer, so partial results merge in any order.  Separate launches; no
 // workgroup waits on another:
 //   k_con_sides      a lane per work: a side byte above 2, NA and N
-//   k_comp_units_ok, CoverJob::number, k_pairs_list, k_comp_incidence
-//                    M and the active numbering, the passes of fs_companions.hip
+//   incidence        IncJob of fs_incidence.h: M and the active numbering, without works(u)
 //   k_con_select     a workgroup per row of L.  A permutation: the NA-th smallest key by a radix
 //                    select over 12 + 12 + 8 bits, a histogram in LDS per pass and the hash made
 //                    again in each (no N x P keys are stored); the works at the boundary key in
@@ -277,9 +276,9 @@ __global__ __launch_bounds__(kRunBlock) void k_con_none(ConArgs a) {
 thread_local double t_ms[5];
 
 struct ConJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, tally, counts, a_act, mu;
-  DBuf<unsigned long long> mat, lab, mx;
+  IncJob inc;
+  DBuf<uint32_t> tally, counts, a_act, mu;
+  DBuf<unsigned long long> lab, mx;
   Clock<5> clk;
   ConArgs a{};
 
@@ -293,13 +292,7 @@ struct ConJob {
     for (double& t : t_ms) t = 0.0;
     const uint64_t max_bytes =
         env_u32("FS_CONTRAST_MAX_BYTES", FS_CONTRAST_MAX_BYTES, FS_CONTRAST_MAX_BYTES);
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.P = permutations;
     a.R = permutations + 2;
     a.Rp = (a.R + kTile - 1) / kTile * kTile;
@@ -311,31 +304,26 @@ struct ConJob {
     a.units = d_units;
     a.perms = d_perms;
     const dim3 blk(kRunBlock);
-    // the checks of the sides and of the unit map ride in front of number(), which waits
-    uint32_t st[4] = {0, 0, 0, 0};
-    FS_TRY(tally.reserve(4));
-    FS_HIP(hipMemsetAsync(tally.p, 0, 4 * sizeof(uint32_t), s));
+    // the check of the sides rides in front of number(), which waits and refuses after it
+    uint32_t st[3] = {0, 0, 0};
+    FS_TRY(tally.reserve(3));
+    FS_HIP(hipMemsetAsync(tally.p, 0, sizeof st, s));
     FS_TRY(clk.mark(0, s));
     if (n_works)
       hipLaunchKernelGGL(k_con_sides, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, d_side,
                          n_works, tally.p);
-    if (n && n_script && n_units)
-      hipLaunchKernelGGL(k_comp_units_ok, dim3(blocks_of(n_script, kRunBlock)), blk, 0, s,
-                         d_unit_of, n_script, n_units, tally.p + 3);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(st, tally.p, sizeof st, hipMemcpyDeviceToHost, s));
     int rc = FS_OK;
-    if (n) rc = cj.number(d_rows, a.r, max_gap, s);
-    FS_HIP(hipStreamSynchronize(s));
+    if (n)
+      rc = inc.number(d_rows, a, max_gap, s);
+    else
+      FS_HIP(hipStreamSynchronize(s));
     if (st[0]) {
       fs_set_error("a side byte above 2 (0 out, 1 side A, 2 side B)");
       return FS_E_INVALID;
     }
     if (rc != FS_OK) return rc;
-    if (st[3]) {
-      fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF", n_units);
-      return FS_E_INVALID;
-    }
     a.NA = st[1];
     a.N = st[2];
     const bool some = n && a.r.n_active;
@@ -350,11 +338,11 @@ struct ConJob {
     a.mu = mu.p;
     size_t rows = 0;
     if (some) {
-      const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-      const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64;
-      const uint64_t mat_bytes = u_tiles * kTile * nk * 8;
+      rows = (size_t)a.m.n_tiles * kTile;
+      const size_t nk = a.m.nk;
+      const uint64_t mat_bytes = IncJob::mat_bytes(a);
       const uint64_t lab_bytes = (uint64_t)a.Rp * nk * 8;
-      const uint64_t count_bytes = u_tiles * kTile * a.Rp * 4;
+      const uint64_t count_bytes = (uint64_t)rows * a.Rp * 4;
       if (mat_bytes + lab_bytes + count_bytes > max_bytes) {
         fs_set_error("%u units over %u works with a passage in %u permutations: an incidence "
                      "matrix of %llu bytes, labels of %llu bytes and counts of %llu bytes are "
@@ -363,27 +351,13 @@ struct ConJob {
                      (unsigned long long)count_bytes, (unsigned long long)max_bytes);
         return FS_E_UNSUPPORTED;
       }
-      a.m.nk = (uint32_t)nk;
-      a.m.n_tiles = (uint32_t)u_tiles;
-      a.m.n_active = n_units;
-      rows = (size_t)a.m.n_tiles * kTile;
-      const size_t a_rows = (size_t)a.r.n_tiles * kTile;     // active numbers, padded: 64 nk
-      FS_TRY(work_of.reserve(a_rows));
-      FS_TRY(mat.reserve(rows * nk));
+      FS_TRY(inc.reserve(a, false, s));                      // with no units: work_of alone
       FS_TRY(lab.reserve((size_t)a.Rp * nk));
       FS_TRY(counts.reserve(rows * a.Rp));
-      FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-      if (rows) FS_HIP(hipMemsetAsync(mat.p, 0, rows * nk * sizeof(unsigned long long), s));
       FS_HIP(hipMemsetAsync(lab.p, 0, (size_t)a.Rp * nk * sizeof(unsigned long long), s));
-      a.r.work_of = work_of.p;
-      a.m.cov = mat.p;
       a.lab = lab.p;
       a.counts = counts.p;
-      hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
-                         cj.flag.p);
-      if (n_units)
-        hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                           RowsSrc{d_rows}, a, cj.flag.p);
+      inc.incidence(d_rows, a, s);
     }
     FS_TRY(clk.mark(1, s));
     if (some) hipLaunchKernelGGL(k_con_select, dim3(a.R), dim3(kSel), 0, s, a);

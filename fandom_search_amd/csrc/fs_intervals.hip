@@ -6,8 +6,7 @@
 //
 // Every output is an integer, so partial results merge in any order.  Separate launches; no
 // workgroup waits on another:
-//   k_comp_units_ok, CoverJob::number, k_pairs_list, k_comp_incidence, k_pairs_covered
-//                    M and works(u), the passes of fs_companions.hip
+//   incidence        IncJob of fs_incidence.h: M and works(u)
 //   k_int_totals     a workgroup per replicate: N_b over every work of the file, A_b over the
 //                    active ones
 //   k_int_mult       a lane per four bytes of mult[b][active work], replicate-major, the rows
@@ -44,9 +43,7 @@ namespace {
 constexpr uint32_t kProd = 256;               // threads of k_int_product: four waves
 constexpr uint32_t kUT = 4;                   // B fragments (16 units) a wave holds: a tile of M
 constexpr uint32_t kRT = 4;                   // A fragments (16 replicates) against each of them
-constexpr uint32_t kSplitBlocks = 512;        // below this many product workgroups the words k
-constexpr uint32_t kSplitWords = 8;           // are shared out, at least this many to each
-constexpr uint32_t kStat = 256;               // threads of k_int_stats
+constexpr uint32_t kStat = 256;              // threads of k_int_stats
 constexpr uint32_t kMaxReps = FS_INTERVALS_MAX_REPLICATES;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -318,9 +315,8 @@ __global__ __launch_bounds__(kRunBlock) void k_int_reps(IntArgs a) {
 thread_local double t_ms[6];
 
 struct IntJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, uworks, bad, counts, tot, order;
-  DBuf<unsigned long long> mat;
+  IncJob inc;
+  DBuf<uint32_t> counts, tot, order;
   DBuf<uint8_t> mult;
   Clock<6> clk;
   IntArgs a{};
@@ -334,13 +330,7 @@ struct IntJob {
     const uint32_t mfma = env_u32("FS_INTERVALS_MFMA", 1u, 1u);
     const uint64_t max_bytes =
         env_u32("FS_INTERVALS_MAX_BYTES", FS_INTERVALS_MAX_BYTES, FS_INTERVALS_MAX_BYTES);
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.B = replicates;
     a.Bp = (replicates + 15) / 16 * 16;
     a.P = 1;
@@ -354,33 +344,16 @@ struct IntJob {
     a.tot = tot.p;
     const dim3 blk(kRunBlock);
     if (n) {
-      // the unit map's check rides in front of number(), which waits for the stream
-      uint32_t bad_units = 0;
-      FS_TRY(bad.reserve(1));
-      FS_HIP(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-      if (n_script && n_units)
-        hipLaunchKernelGGL(k_comp_units_ok, dim3(blocks_of(n_script, kRunBlock)), blk, 0, s,
-                           d_unit_of, n_script, n_units, bad.p);
-      FS_HIP(hipGetLastError());
-      FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-      const int rc = cj.number(d_rows, a.r, max_gap, s);
-      FS_HIP(hipStreamSynchronize(s));
-      if (rc != FS_OK) return rc;
-      if (bad_units) {
-        fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF",
-                     n_units);
-        return FS_E_INVALID;
-      }
-      a.flag = cj.flag.p;
+      FS_TRY(inc.number(d_rows, a, max_gap, s));
+      a.flag = inc.cj.flag.p;
     }
     const bool some = n && a.r.n_active && n_units;
     size_t rows = 0;
     if (some) {
-      const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-      const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64;
-      const uint64_t mat_bytes = u_tiles * kTile * nk * 8;
-      const uint64_t mult_bytes = (uint64_t)a.Bp * nk * 64;
-      const uint64_t count_bytes = u_tiles * kTile * a.Bp * 4;
+      rows = (size_t)a.m.n_tiles * kTile;
+      const uint64_t mat_bytes = IncJob::mat_bytes(a);
+      const uint64_t mult_bytes = (uint64_t)a.Bp * a.m.nk * 64;
+      const uint64_t count_bytes = (uint64_t)rows * a.Bp * 4;
       if (mat_bytes + mult_bytes + count_bytes > max_bytes) {
         fs_set_error("%u units over %u works with a passage in %u replicates: an incidence "
                      "matrix of %llu bytes, multiplicities of %llu bytes and counts of %llu "
@@ -389,34 +362,16 @@ struct IntJob {
                      (unsigned long long)count_bytes, (unsigned long long)max_bytes);
         return FS_E_UNSUPPORTED;
       }
-      a.m.nk = (uint32_t)nk;
-      a.m.n_tiles = (uint32_t)u_tiles;
-      a.m.n_active = n_units;
-      a.Wp = (uint32_t)nk * 64;
-      rows = (size_t)a.m.n_tiles * kTile;
-      const size_t a_rows = (size_t)a.r.n_tiles * kTile;   // active numbers, padded: Wp
-      FS_TRY(work_of.reserve(a_rows));
-      FS_TRY(mat.reserve(rows * nk));
-      FS_TRY(uworks.reserve(rows));
+      a.Wp = a.m.nk * 64;                                  // the active numbers, padded
+      FS_TRY(inc.reserve(a, true, s));
       FS_TRY(mult.reserve((size_t)mult_bytes));
       FS_TRY(counts.reserve(rows * a.Bp));
       FS_TRY(order.reserve(2 * (size_t)n_units));
-      FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-      FS_HIP(hipMemsetAsync(mat.p, 0, rows * nk * sizeof(unsigned long long), s));
-      a.r.work_of = work_of.p;
-      a.m.cov = mat.p;
-      a.m.covered = uworks.p;
       a.mult = mult.p;
       a.counts = counts.p;
     }
     FS_TRY(clk.mark(0, s));
-    if (some) {
-      hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
-                         cj.flag.p);
-      hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                         RowsSrc{d_rows}, a, cj.flag.p);
-      hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
-    }
+    if (some) inc.incidence(d_rows, a, s);
     FS_TRY(clk.mark(1, s));
     hipLaunchKernelGGL(k_int_totals, dim3(a.B), blk, 0, s, a);
     if (some)
@@ -425,18 +380,9 @@ struct IntJob {
     FS_TRY(clk.mark(2, s));
     if (some) {
       if (mfma) {
-        // few tiles: the words k are shared out until there are kSplitBlocks workgroups, at
-        // least kSplitWords words each (FS_INTERVALS_KSPLIT: that many shares, for the tests)
+        // few tiles: the words k are shared out (inc_ksplit)
         const uint32_t gy = (a.Bp / 16 + 4 * kRT - 1) / (4 * kRT);
-        const uint64_t blocks = (uint64_t)a.m.n_tiles * gy;
-        uint32_t ksplit = env_u32("FS_INTERVALS_KSPLIT", 0u, 65535u);
-        if (!ksplit && blocks < kSplitBlocks) {
-          const uint32_t room = (uint32_t)((kSplitBlocks + blocks - 1) / blocks);
-          const uint32_t most = (a.m.nk + kSplitWords - 1) / kSplitWords;
-          ksplit = room < most ? room : most;
-        }
-        if (ksplit > a.m.nk) ksplit = a.m.nk;
-        a.ksplit = ksplit ? ksplit : 1u;
+        a.ksplit = inc_ksplit("FS_INTERVALS_KSPLIT", (uint64_t)a.m.n_tiles * gy, a.m.nk);
         if (a.ksplit > 1)
           FS_HIP(hipMemsetAsync(counts.p, 0, rows * a.Bp * sizeof(uint32_t), s));
         hipLaunchKernelGGL(k_int_product, dim3(a.m.n_tiles, gy, a.ksplit), dim3(kProd), 0, s, a);
@@ -455,7 +401,7 @@ struct IntJob {
     if (some) {
       // the observed order: works descending, then the unit; rank = 1 + the units with more
       std::vector<uint32_t> works(n_units), at(n_units), rn(2 * (size_t)n_units);
-      FS_HIP(hipMemcpyAsync(works.data(), uworks.p, (size_t)n_units * sizeof(uint32_t),
+      FS_HIP(hipMemcpyAsync(works.data(), a.m.covered, (size_t)n_units * sizeof(uint32_t),
                             hipMemcpyDeviceToHost, s));
       FS_HIP(hipStreamSynchronize(s));
       for (uint32_t u = 0; u < n_units; ++u) at[u] = u;

@@ -8,8 +8,7 @@
 //
 // Every output is an integer and every merge an integer min or add, so partial results merge in
 // any order.  Separate launches; no workgroup waits on another:
-//   k_comp_units_ok, CoverJob::number, k_pairs_list, k_comp_incidence, k_pairs_covered
-//                    M and works(u), the passes of fs_companions.hip
+//   incidence        IncJob of fs_incidence.h: M and works(u)
 //   k_sat_summary    Q, Q1 and Q2 from works(u): a ballot per wave, one atomic add per count
 //   k_sat_sizes      a workgroup per order and slab of works: every work of the file hashed into
 //                    a histogram over the points in LDS, one global atomic per non-zero bucket
@@ -41,8 +40,6 @@ namespace {
 constexpr uint32_t kProd = 256;               // threads of k_sat_product: four waves, a row each
 constexpr uint32_t kChunkBlocks = 2048;       // product workgroups wanted before a wave takes
                                               // more than one chunk of 64 orders
-constexpr uint32_t kSplitBlocks = 512;        // below this many product workgroups the words k
-constexpr uint32_t kSplitWords = 8;           // are shared out, at least this many to each
 constexpr uint32_t kSlab = 1u << 16;          // works a k_sat_sizes workgroup hashes
 constexpr uint32_t kCurveUnits = 128;         // units of a k_sat_curve workgroup: a byte counts them
 constexpr uint32_t kStat = 256;               // threads of k_sat_points
@@ -331,9 +328,8 @@ __global__ __launch_bounds__(kRunBlock) void k_sat_first_out(SatArgs a) {
 thread_local double t_ms[10];
 
 struct SatJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, uworks, bad, times, first, hist, sums;
-  DBuf<unsigned long long> mat;
+  IncJob inc;
+  DBuf<uint32_t> times, first, hist, sums;
   Clock<7> clk;
   SatArgs a{};
 
@@ -348,13 +344,7 @@ struct SatJob {
     uint32_t table = env_u32("FS_SATURATION_TABLE", kTableDefault, 1u);
     const uint64_t max_bytes =
         env_u32("FS_SATURATION_MAX_BYTES", FS_SATURATION_MAX_BYTES, FS_SATURATION_MAX_BYTES);
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.R = permutations;
     a.Rp = (permutations + 63) / 64 * 64;
     a.P = 1;
@@ -376,30 +366,10 @@ struct SatJob {
     a.whist = hist.p + hist_words;
     a.sums = sums.p;
     const dim3 blk(kRunBlock);
-    if (n) {
-      // the unit map's check rides in front of number(), which waits for the stream
-      uint32_t bad_units = 0;
-      FS_TRY(bad.reserve(1));
-      FS_HIP(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-      if (n_script && n_units)
-        hipLaunchKernelGGL(k_comp_units_ok, dim3(blocks_of(n_script, kRunBlock)), blk, 0, s,
-                           d_unit_of, n_script, n_units, bad.p);
-      FS_HIP(hipGetLastError());
-      FS_HIP(hipMemcpyAsync(&bad_units, bad.p, sizeof bad_units, hipMemcpyDeviceToHost, s));
-      const int rc = cj.number(d_rows, a.r, max_gap, s);
-      FS_HIP(hipStreamSynchronize(s));
-      if (rc != FS_OK) return rc;
-      if (bad_units) {
-        fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF",
-                     n_units);
-        return FS_E_INVALID;
-      }
-    }
+    if (n) FS_TRY(inc.number(d_rows, a, max_gap, s));
     const bool some = n && a.r.n_active && n_units;
     if (some) {
-      const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-      const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64;
-      const uint64_t mat_bytes = u_tiles * kTile * nk * 8;
+      const uint64_t mat_bytes = IncJob::mat_bytes(a);
       const uint64_t first_bytes = (uint64_t)n_units * a.Rp * 4;
       const uint64_t hist_bytes = 2ull * hist_words * 4;
       const uint64_t table_bytes = (uint64_t)a.r.n_active * a.Rp * 4;
@@ -414,21 +384,9 @@ struct SatJob {
       }
       // the table of times is the part a call can do without
       if (mat_bytes + first_bytes + hist_bytes + table_bytes > max_bytes) table = 0;
-      a.m.nk = (uint32_t)nk;
-      a.m.n_tiles = (uint32_t)u_tiles;
-      a.m.n_active = n_units;
-      const size_t rows = (size_t)a.m.n_tiles * kTile;
-      const size_t a_rows = (size_t)a.r.n_tiles * kTile;   // active numbers, padded
-      FS_TRY(work_of.reserve(a_rows));
-      FS_TRY(mat.reserve(rows * nk));
-      FS_TRY(uworks.reserve(rows));
+      FS_TRY(inc.reserve(a, true, s));
       FS_TRY(first.reserve((size_t)n_units * a.Rp));
       if (table) FS_TRY(times.reserve((size_t)a.r.n_active * a.Rp));
-      FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-      FS_HIP(hipMemsetAsync(mat.p, 0, rows * nk * sizeof(unsigned long long), s));
-      a.r.work_of = work_of.p;
-      a.m.cov = mat.p;
-      a.m.covered = uworks.p;
       a.first = first.p;
       a.times = times.p;
       // A wave reads its row once for all the chunks of 64 orders it takes.  Few rows: the
@@ -439,27 +397,14 @@ struct SatJob {
       if (!osplit) osplit = (kChunkBlocks + row_blocks - 1) / row_blocks;
       a.osplit = osplit < n_oc ? osplit : n_oc;
       a.oc_per = (n_oc + a.osplit - 1) / a.osplit;
-      // still few workgroups: the words k are shared out until there are kSplitBlocks of them,
-      // at least kSplitWords words each (FS_SATURATION_KSPLIT: that many shares, for the tests)
-      const uint64_t blocks = (uint64_t)row_blocks * a.osplit;
-      uint32_t ksplit = env_u32("FS_SATURATION_KSPLIT", 0u, 65535u);
-      if (!ksplit && blocks < kSplitBlocks) {
-        const uint32_t room = (uint32_t)((kSplitBlocks + blocks - 1) / blocks);
-        const uint32_t most = (a.m.nk + kSplitWords - 1) / kSplitWords;
-        ksplit = room < most ? room : most;
-      }
-      if (ksplit > a.m.nk) ksplit = a.m.nk;
-      a.ksplit = ksplit ? ksplit : 1u;
+      // still few workgroups: the words k are shared out (inc_ksplit)
+      a.ksplit = inc_ksplit("FS_SATURATION_KSPLIT", (uint64_t)row_blocks * a.osplit, a.m.nk);
       if (a.ksplit > 1)
         FS_HIP(hipMemsetAsync(first.p, 0xFF, (size_t)n_units * a.Rp * sizeof(uint32_t), s));
     }
     FS_TRY(clk.mark(0, s));
     if (some) {
-      hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
-                         cj.flag.p);
-      hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                         RowsSrc{d_rows}, a, cj.flag.p);
-      hipLaunchKernelGGL(k_pairs_covered, dim3(a.m.n_tiles), dim3(kTile), 0, s, a.m);
+      inc.incidence(d_rows, a, s);
       hipLaunchKernelGGL(k_sat_summary, dim3(blocks_of(n_units, kRunBlock)), blk, 0, s, a);
     }
     FS_TRY(clk.mark(1, s));
@@ -492,7 +437,7 @@ struct SatJob {
     if (n_units) {
       const size_t first_words = (size_t)n_units * a.R;
       if (some) {
-        FS_HIP(hipMemcpyAsync(d_works, uworks.p, (size_t)n_units * sizeof(uint32_t),
+        FS_HIP(hipMemcpyAsync(d_works, a.m.covered, (size_t)n_units * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
         if (d_first)
           hipLaunchKernelGGL(k_sat_first_out, dim3(blocks_of(first_words, kRunBlock)), blk, 0, s,

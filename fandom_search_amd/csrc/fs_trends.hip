@@ -12,8 +12,7 @@
 //   k_trd_when       a lane per work: an offset above 1023 that is not 0xFFFF, the pool flags
 //   k_pairs_scan     the pool positions and N
 //   k_trd_pool       a lane per work: the offsets of the pool in pool order
-//   k_comp_units_ok, CoverJob::number, k_pairs_list, k_comp_incidence
-//                    M and the active numbering, the passes of fs_companions.hip
+//   incidence        IncJob of fs_incidence.h: M and the active numbering, without works(u)
 //   k_trd_pbits      the pool as a row of bits over the active works: t(u) is an AND and a popcount
 //   k_trd_labels     a lane per (row, work): the hash, the gather, X_r by a workgroup reduction
 //                    and one atomic add, and for an active work the two bytes.  Row P: the
@@ -46,8 +45,6 @@ namespace {
 constexpr uint32_t kProd = 256;               // threads of k_trd_product: four waves
 constexpr uint32_t kUT = 4;                   // B fragments (16 units) a wave holds: a tile of M
 constexpr uint32_t kRT = 2;                   // A fragments (16 rows) of either plane against them
-constexpr uint32_t kSplitBlocks = 512;        // below this many product workgroups the words k
-constexpr uint32_t kSplitWords = 8;           // are shared out, at least this many to each
 constexpr uint32_t kAdjUnits = 64;            // units a workgroup of k_trd_adjust takes
 constexpr uint32_t kMaxPerms = FS_TRENDS_MAX_PERMUTATIONS;
 constexpr uint32_t kOut = 0xFFFFu;            // `when` of a work outside the pool
@@ -337,10 +334,10 @@ __global__ __launch_bounds__(kRunBlock) void k_trd_none(TrdArgs a) {
 thread_local double t_ms[5];
 
 struct TrdJob {
-  CoverJob cj;
-  DBuf<uint32_t> work_of, tally, inpool, pos, sums, xr, mu;
+  IncJob inc;
+  DBuf<uint32_t> tally, inpool, pos, sums, xr, mu;
   DBuf<uint16_t> pool_x;
-  DBuf<unsigned long long> mat, pbits, mx;
+  DBuf<unsigned long long> pbits, mx;
   DBuf<uint8_t> planes;
   Clock<5> clk;
   TrdArgs a{};
@@ -355,13 +352,7 @@ struct TrdJob {
     const uint32_t mfma = env_u32("FS_TRENDS_MFMA", kMfmaDefault, 1u);
     const uint64_t max_bytes =
         env_u32("FS_TRENDS_MAX_BYTES", FS_TRENDS_MAX_BYTES, FS_TRENDS_MAX_BYTES);
-    a.r.n = n;
-    a.r.n_works = n_works;
-    a.r.n_script = n_script;
-    a.r.nk = (n_script + 63) / 64;
-    a.r.min_words = min_words;
-    a.unit_of = d_unit_of;
-    a.n_units = n_units;
+    IncJob::set(a, n, n_works, n_script, min_words, d_unit_of, n_units);
     a.P = permutations;
     a.R = permutations + 1;
     a.Rp = (a.R + 15) / 16 * 16;
@@ -371,12 +362,12 @@ struct TrdJob {
     a.units = d_units;
     a.perms = d_perms;
     const dim3 blk(kRunBlock);
-    // the checks of the offsets and of the unit map ride in front of number(), which waits
-    uint32_t st[4] = {0, 0, 0, 0};
-    FS_TRY(tally.reserve(4));
+    // the check of the offsets rides in front of number(), which waits and refuses after it
+    uint32_t st[2] = {0, 0};                                 // a bad offset, N
+    FS_TRY(tally.reserve(2));
     FS_TRY(inpool.reserve(n_works));
     FS_TRY(pos.reserve(n_works));
-    FS_HIP(hipMemsetAsync(tally.p, 0, 4 * sizeof(uint32_t), s));
+    FS_HIP(hipMemsetAsync(tally.p, 0, sizeof st, s));
     FS_TRY(clk.mark(0, s));
     if (n_works) {
       hipLaunchKernelGGL(k_trd_when, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, d_when,
@@ -384,24 +375,19 @@ struct TrdJob {
       hipLaunchKernelGGL(k_pairs_scan<uint32_t>, dim3(1), dim3(kScanBlock), 0, s, inpool.p,
                          (uint64_t)n_works, pos.p, tally.p + 1);
     }
-    if (n && n_script && n_units)
-      hipLaunchKernelGGL(k_comp_units_ok, dim3(blocks_of(n_script, kRunBlock)), blk, 0, s,
-                         d_unit_of, n_script, n_units, tally.p + 3);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(st, tally.p, sizeof st, hipMemcpyDeviceToHost, s));
     int rc = FS_OK;
-    if (n) rc = cj.number(d_rows, a.r, max_gap, s);
-    FS_HIP(hipStreamSynchronize(s));
+    if (n)
+      rc = inc.number(d_rows, a, max_gap, s);
+    else
+      FS_HIP(hipStreamSynchronize(s));
     if (st[0]) {
       fs_set_error("a `when` above %u that is not 0xFFFF (a work outside the pool)",
                    FS_TRENDS_MAX_SPAN - 1u);
       return FS_E_INVALID;
     }
     if (rc != FS_OK) return rc;
-    if (st[3]) {
-      fs_set_error("a unit_of entry that is neither below n_units (%u) nor 0xFFFFFFFF", n_units);
-      return FS_E_INVALID;
-    }
     a.N = st[1];
     a.pos = pos.p;
     FS_TRY(pool_x.reserve(a.N));
@@ -420,11 +406,10 @@ struct TrdJob {
     a.mu = mu.p;
     size_t rows = 0;
     if (some) {
-      const uint64_t u_tiles = ((uint64_t)n_units + kTile - 1) / kTile;
-      const uint64_t nk = ((uint64_t)a.r.n_active + 63) / 64;
-      const uint64_t mat_bytes = u_tiles * kTile * nk * 8;
-      const uint64_t plane_bytes = 2 * (uint64_t)a.Rp * nk * 64;
-      const uint64_t sum_bytes = u_tiles * kTile * a.Rp * 4;
+      rows = (size_t)a.m.n_tiles * kTile;
+      const uint64_t mat_bytes = IncJob::mat_bytes(a);
+      const uint64_t plane_bytes = 2 * (uint64_t)a.Rp * a.m.nk * 64;
+      const uint64_t sum_bytes = (uint64_t)rows * a.Rp * 4;
       if (mat_bytes + plane_bytes + sum_bytes > max_bytes) {
         fs_set_error("%u units over %u works with a passage in %u re-datings: an incidence "
                      "matrix of %llu bytes, two offset planes of %llu bytes and sums of %llu "
@@ -433,31 +418,18 @@ struct TrdJob {
                      (unsigned long long)sum_bytes, (unsigned long long)max_bytes);
         return FS_E_UNSUPPORTED;
       }
-      a.m.nk = (uint32_t)nk;
-      a.m.n_tiles = (uint32_t)u_tiles;
-      a.m.n_active = n_units;
-      a.Wp = (uint32_t)nk * 64;
-      rows = (size_t)a.m.n_tiles * kTile;
-      const size_t a_rows = (size_t)a.r.n_tiles * kTile;     // active numbers, padded: Wp
-      FS_TRY(work_of.reserve(a_rows));
-      FS_TRY(mat.reserve(rows * nk));
-      FS_TRY(pbits.reserve(nk));
+      a.Wp = a.m.nk * 64;                                    // the active numbers, padded
+      FS_TRY(inc.reserve(a, false, s));
+      FS_TRY(pbits.reserve(a.m.nk));
       FS_TRY(planes.reserve((size_t)plane_bytes));
       FS_TRY(sums.reserve(rows * a.Rp));
-      FS_HIP(hipMemsetAsync(work_of.p, 0xFF, a_rows * sizeof(uint32_t), s));
-      FS_HIP(hipMemsetAsync(mat.p, 0, rows * nk * sizeof(unsigned long long), s));
       FS_HIP(hipMemsetAsync(planes.p, 0, (size_t)plane_bytes, s));
-      a.r.work_of = work_of.p;
-      a.m.cov = mat.p;
       a.pbits = pbits.p;
       a.lo = planes.p;
       a.hi = planes.p + (size_t)plane_bytes / 2;
       a.sums = sums.p;
-      a.flag = cj.flag.p;
-      hipLaunchKernelGGL(k_pairs_list, dim3(blocks_of(n_works, kRunBlock)), blk, 0, s, a.r,
-                         cj.flag.p);
-      hipLaunchKernelGGL(k_comp_incidence, dim3(blocks_of(a.r.n_runs, kRunBlock)), blk, 0, s,
-                         RowsSrc{d_rows}, a, cj.flag.p);
+      a.flag = inc.cj.flag.p;
+      inc.incidence(d_rows, a, s);
       hipLaunchKernelGGL(k_trd_pbits, dim3(blocks_of(a.Wp, kRunBlock)), blk, 0, s, a);
     }
     FS_TRY(clk.mark(1, s));
@@ -466,18 +438,9 @@ struct TrdJob {
     FS_TRY(clk.mark(2, s));
     if (some) {
       if (mfma) {
-        // few tiles: the words k are shared out until there are kSplitBlocks workgroups, at
-        // least kSplitWords words each (FS_TRENDS_KSPLIT: that many shares, for the tests)
+        // few tiles: the words k are shared out (inc_ksplit)
         const uint32_t gy = (a.Rp / 16 + 4 * kRT - 1) / (4 * kRT);
-        const uint64_t blocks = (uint64_t)a.m.n_tiles * gy;
-        uint32_t ksplit = env_u32("FS_TRENDS_KSPLIT", 0u, 65535u);
-        if (!ksplit && blocks < kSplitBlocks) {
-          const uint32_t room = (uint32_t)((kSplitBlocks + blocks - 1) / blocks);
-          const uint32_t most = (a.m.nk + kSplitWords - 1) / kSplitWords;
-          ksplit = room < most ? room : most;
-        }
-        if (ksplit > a.m.nk) ksplit = a.m.nk;
-        a.ksplit = ksplit ? ksplit : 1u;
+        a.ksplit = inc_ksplit("FS_TRENDS_KSPLIT", (uint64_t)a.m.n_tiles * gy, a.m.nk);
         if (a.ksplit > 1)
           FS_HIP(hipMemsetAsync(sums.p, 0, rows * a.Rp * sizeof(uint32_t), s));
         hipLaunchKernelGGL(k_trd_product, dim3(a.m.n_tiles, gy, a.ksplit), dim3(kProd), 0, s, a);

@@ -359,6 +359,19 @@ def test_no_records_no_units_and_no_passage(index):
     assert len(units) == 0 and len(sets) == 0
     units, levels, sets = check(index, cols, n_works, unit_map(5), 5, m=WIDTH + 1)
     assert units.tolist() == [(0, 0, 0, 0)] * 5 and len(sets) == 0
+    # without a unit no record is read: one work, eight records, the last of a work >= n_works
+    from fandom_search_amd.engine import torch_ready
+    stray = (np.array([0] * 7 + [1], np.uint32), np.arange(8, dtype=np.uint32),
+             np.arange(10, 18, dtype=np.uint32))
+    no_unit = np.full(N_SCRIPT, NONE, np.uint32)
+    d_rows, d_map = on_device(stray, no_unit)
+    torch_ready()
+    for units, levels, sets in (
+            bundles.find_bundles(*stray, 1, N_SCRIPT, no_unit, 0, 3, 0, 2, 4),
+            index.bundles_device(d_rows.data_ptr(), 8, 1, d_map.data_ptr(), 0, 3, 0, 2, 4)):
+        assert len(units) == 0 and len(sets) == 0
+        assert levels.tolist() == [(2, 0, 0, 0, 0), (3, 0, 0, 0, 0), (4, 0, 0, 0, 0),
+                                   (5, 0, 0, NONE, NONE)]
 
 
 def test_refusals(index):

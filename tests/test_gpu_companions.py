@@ -258,6 +258,17 @@ def test_no_records_and_no_units(index):
     assert len(units) == 0 and len(found) == 0
     units, found = check(index, cols, n_works, unit_of, 5, m=41)     # no work has a passage
     assert units.tolist() == [(0, 0, NONE, 0)] * 5 and len(found) == 0
+    # without a unit no record is read: one work, eight records, the last of a work >= n_works
+    from fandom_search_amd.engine import torch_ready
+    stray = (np.array([0] * 7 + [1], np.uint32), np.arange(8, dtype=np.uint32),
+             np.arange(10, 18, dtype=np.uint32))
+    no_unit = np.full(N_SCRIPT, NONE, np.uint32)
+    d_rows, d_map = on_device(stray, no_unit)
+    torch_ready()
+    for units, found in (
+            companions.find_companions(*stray, 1, N_SCRIPT, no_unit, 0, 3, 0, 2, 0),
+            index.companions_device(d_rows.data_ptr(), 8, 1, d_map.data_ptr(), 0, 3, 0, 2, 0)):
+        assert len(units) == 0 and len(found) == 0
 
 
 def test_refusals(index):

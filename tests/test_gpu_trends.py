@@ -315,6 +315,13 @@ def test_refusals_and_the_size_cap(index, monkeypatch):
     late[n_works - 1] = 1024
     assert "`when` above 1023" in refused(when=late)
     refused(n_works=int(cols[0].max()))                    # a work >= n_works
+    # and without a unit the records are checked all the same: one work, eight records, the last
+    # of a work >= n_works
+    stray = (np.array([0] * 7 + [1], np.uint32), np.arange(8, dtype=np.uint32),
+             np.arange(10, 18, dtype=np.uint32))
+    text = refused(stray, n_works=1, unit_of=np.full(N_SCRIPT, NONE, np.uint32), n_units=0,
+                   when=np.zeros(1, np.uint16), m=3)
+    assert "a work >= n_works or an orig_ix >= n_script" in text
     far = cols[2].copy()
     far[20] = N_SCRIPT
     refused((cols[0], cols[1], far))                       # an orig_ix >= n_script
