@@ -23,6 +23,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
            "fs_reuse_histogram", "fs_reuse_histogram_rows", "fs_passages", "fs_passages_rows",
            "fs_works", "fs_works_rows", "fs_quotes", "fs_quotes_rows", "fs_variants",
            "fs_readings", "fs_readings_times",
+           "fs_fanon", "fs_fanon_dev", "fs_fanon_times",
            "fs_retellings", "fs_retellings_rows", "fs_retellings_times",
            "fs_alignments", "fs_alignments_rows", "fs_alignments_times",
            "fs_pairs", "fs_pairs_rows", "fs_pairs_times",
@@ -59,7 +60,7 @@ SYMBOLS = ("fs_version", "fs_strerror", "fs_last_error", "fs_index_create",
 
 
 # the commands with an fs_<name>_times(double *ms) beside their entry points
-TIMED = ("readings", "retellings", "alignments", "pairs", "companions", "bundles", "routes", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
+TIMED = ("readings", "fanon", "retellings", "alignments", "pairs", "companions", "bundles", "routes", "lines", "fragments", "digest", "intervals", "contrast", "trends", "neighbours", "misquotes", "saturation", "transitions", "sources", "matrix",
          "clusters", "tree", "groups")
 
 
@@ -368,6 +369,17 @@ def load():
     L.fs_readings.argtypes = [C.c_int, u32p, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                               C.c_void_p, C.c_uint64, u64p, u64p, u64p]
+    L.fs_fanon.restype = C.c_int
+    L.fs_fanon.argtypes = [C.c_int, u32p, u64p, C.c_uint32, C.c_uint32, u32p, u64p, C.c_uint32,
+                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, u64p, u64p,
+                           u64p]
+    L.fs_fanon_dev.restype = C.c_int
+    L.fs_fanon_dev.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                               C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p,
+                               u64p, u64p, u64p, u64p]
     L.fs_retellings.restype = C.c_int
     L.fs_retellings.argtypes = [C.c_int, u32p, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]

@@ -482,6 +482,32 @@ FS_READINGS_MAX_BYTES = 1 << 30
 FS_READINGS_SLOT_BYTES = 64
 READINGS_MS_NAMES = ("passages", "tables", "spans", "readings", "copy_out", "total")
 
+# fs_fanon_work 40 bytes, fs_fanon_gram 16, fs_fanon_passage 24, fs_fanon_phrase 32
+FANON_WORK_DTYPE = np.dtype([("n_tokens", np.uint32), ("n_positions", np.uint32),
+                             ("shared_positions", np.uint32), ("canon_positions", np.uint32),
+                             ("common_positions", np.uint32), ("n_passages", np.uint32),
+                             ("shared_tokens", np.uint32), ("canon_tokens", np.uint32),
+                             ("longest_start", np.uint32), ("longest_tokens", np.uint32)])
+assert FANON_WORK_DTYPE.itemsize == 40
+FANON_GRAM_DTYPE = np.dtype([("work", np.uint32), ("start", np.uint32), ("works", np.uint32),
+                             ("occurrences", np.uint32)])
+assert FANON_GRAM_DTYPE.itemsize == 16
+FANON_PASSAGE_DTYPE = np.dtype([("work", np.uint32), ("start", np.uint32),
+                                ("n_tokens", np.uint32), ("phrase", np.uint32),
+                                ("least", np.uint32), ("most", np.uint32)])
+assert FANON_PASSAGE_DTYPE.itemsize == 24
+FANON_PHRASE_DTYPE = np.dtype([("work", np.uint32), ("start", np.uint32),
+                               ("n_tokens", np.uint32), ("n_passages", np.uint32),
+                               ("n_works", np.uint32), ("least", np.uint32), ("most", np.uint32),
+                               ("reserved", np.uint32)])
+assert FANON_PHRASE_DTYPE.itemsize == 32
+FS_FANON_NO_ID = 0xFFFFFFFF
+FS_FANON_MIN_LENGTH = 2
+FS_FANON_MAX_LENGTH = 32
+FS_FANON_TILE = 256
+FS_FANON_MAX_BYTES = 8 << 30
+FANON_MS_NAMES = ("insert", "flag", "phrases", "place", "works", "copy_out", "total")
+
 # fs_retelling 40 bytes, fs_retelling_passage 48
 RETELLING_DTYPE = np.dtype([("n_passages", np.uint32), ("passage_words", np.uint32),
                             ("chain_passages", np.uint32), ("chain_words", np.uint32),

@@ -21,7 +21,8 @@ with gaps, for quotes with inserted or dropped words (fandom_search_amd/alignmen
 `lines`, which ranks the lines of the script markup by the works quoting them and says how
 completely each is quoted (fandom_search_amd/lines.py), and `fragments`, which lists the
 phrases the works quote word for word, each with the works quoting it in full
-(fandom_search_amd/fragments.py), and `digest`, which picks the fewest works that together show
+(fandom_search_amd/fragments.py), and `fanon`, which reads the fan works themselves and lists
+the phrases they share with each other and the script lacks (fandom_search_amd/fanon.py), and `digest`, which picks the fewest works that together show
 everything the works quote (fandom_search_amd/digest.py), and `intervals`, which resamples the
 works to say how sure the works-per-stretch counts are (fandom_search_amd/intervals.py), and
 `contrast`, which says what one group of works quotes more than another and which of those
@@ -428,10 +429,10 @@ def ao3_parser():
     """The parser `ao3.py` runs: full_parser(), whose surface the tests pin as it stands, and
     behind it the commands added since (`lines`, `fragments`, `digest`, `intervals`,
     `contrast`, `saturation`, `trends`, `neighbours`, `misquotes`, `tree`, `bundles`,
-    `routes`)."""
+    `routes`, `fanon`)."""
     parser = full_parser()
     subparsers = parser._subparsers._group_actions[0]
-    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, bundles, routes, trends, neighbours, misquotes, tree, contrast, saturation or validate')
+    subparsers.help = subparsers.help.replace(' or validate', ', lines, fragments, digest, intervals, bundles, routes, fanon, trends, neighbours, misquotes, tree, contrast, saturation or validate')
 
     _analysis(subparsers, 'lines',
               'ranks the lines of the script markup by the fan works quoting them '
@@ -788,7 +789,61 @@ def ao3_parser():
                               'run; default: any distance'),
                     _own('--all', action='store_true',
                          help='list every frequent route, not only the closed ones')])
+
+    _fanon_parser(subparsers)
     return parser
+
+
+FANON_CHECKS = [
+    (lambda a: not 2 <= a.length <= 32, '--length must be from 2 to 32'),
+    (lambda a: a.min_works < 1, '--min-works must be at least 1'),
+    (lambda a: not 1 <= a.max_share <= 100, '--max-share must be from 1 to 100'),
+    (lambda a: a.top < 0, '--top must be at least 0')]
+
+
+def _fanon_parser(subparsers):
+    """`fanon`, the one analysis command over the fan works themselves and no match csv: its
+    arguments are those `search` lists the works with, and its own."""
+    p = subparsers.add_parser(
+        'fanon', help='lists the phrases fan works share with each other and the script '
+                      'lacks: runs of --length-token grams that at least --min-works works '
+                      'hold, no script holds and not more than --max-share percent of the '
+                      'works hold; per work how much of it is shared, and its longest '
+                      'shared passage')
+    p.add_argument('fan_works', action='store', help='directory of fanwork text files')
+    p.add_argument('scripts', action='store', nargs='*', metavar='script',
+                   help='filenames for markup versions of scripts: a gram that stands in '
+                        'one of them is canon and not listed')
+    p.add_argument('-o', '--output', action='store', default=None,
+                   help='prefix of the four csv files, PREFIX-fanon.csv, '
+                        'PREFIX-fanon-passages.csv, PREFIX-fanon-grams.csv and '
+                        'PREFIX-fanon-works.csv (default: the base name of the directory)')
+    p.add_argument('--length', default=8, type=int,
+                   help='tokens of a gram, 2 to 32, default 8')
+    p.add_argument('--min-works', default=2, type=int,
+                   help='fewest different works holding a shared gram, default 2')
+    p.add_argument('--max-share', default=100, type=int,
+                   help='a gram that more than this percentage of the listed works hold is '
+                        'common (disclaimers, site boilerplate) and not shared, 1 to 100, '
+                        'default 100: none is')
+    p.add_argument('--keep-case', action='store_true',
+                   help='compare the tokens as written instead of under str.lower()')
+    p.add_argument('--top', default=1000, type=int,
+                   help='keep the first N phrases and grams of their rankings, default '
+                        '1000; 0: all')
+    p.add_argument('-n', '--num-works', default=-1, type=int,
+                   help='number of works to read (for subsampling)')
+    p.add_argument('-s', '--skip-works', default=0, type=int,
+                   help='number of works to skip (for subsampling)')
+    p.add_argument('--listing', default=None, choices=('sorted', 'os'),
+                   help="order of the directory listing in front of the seeded shuffle, as for "
+                        "`search`; also FANDOM_SEARCH_LISTING")
+    p.add_argument('--device', default=0, type=int, help='HIP device ordinal')
+
+    def func(args):
+        return _command('fanon', FANON_CHECKS, args)
+    func.__name__ = '_fanon'
+    p.set_defaults(func=func)
 
 
 def _validate(args):

@@ -1047,3 +1047,74 @@ class ScriptIndex(object):
             self.close()
         except Exception:
             pass
+
+
+def _fanon_canon(canon, canon_off):
+    """The scripts' ids and offsets as the library takes them: none is one empty list."""
+    if canon_off is None or len(canon_off) < 2:
+        return np.zeros(1, np.uint32), np.zeros(1, np.uint64), 0
+    off = abi.as_u64(canon_off)
+    ids = abi.as_u32(canon)
+    if len(ids) == 0:
+        ids = np.zeros(1, np.uint32)
+    return ids, off, len(off) - 1
+
+
+def fanon(tok, work_off, n_ids, canon=None, canon_off=None, length=8, min_works=2,
+          max_share=100, device=0):
+    """`fanon` over host buffers (fs_fanon), which needs no script index: the token ids of the
+    works `work_off` delimits, the scripts' ids (abi.FS_FANON_NO_ID for a word that is no fan
+    token) under `canon_off`.  (works, shared grams in order of first, passages in corpus
+    order, phrases in order of first, {'positions', 'distinct'}) as arrays of
+    abi.FANON_*_DTYPE; the three growing buffers are enlarged until the call fits."""
+    tok, off = abi.as_u32(tok), abi.as_u64(work_off)
+    if len(off) < 1:
+        raise ValueError("work_off needs at least its leading 0")
+    n_works = len(off) - 1
+    ids, coff, n_scripts = _fanon_canon(canon, canon_off)
+    works = np.zeros(max(1, n_works), dtype=abi.FANON_WORK_DTYPE)
+    n_pos, n_dist = C.c_uint64(0), C.c_uint64(0)
+    L = _lib.load()
+    from .command import grow
+    grams, passages, phrases = grow(
+        lambda g, cap_g, got_g, p, cap_p, got_p, f, cap_f, got_f: L.fs_fanon(
+            int(device), abi.ptr(tok if len(tok) else np.zeros(1, np.uint32), C.c_uint32),
+            abi.ptr(off, C.c_uint64), n_works, int(n_ids), abi.ptr(ids, C.c_uint32),
+            abi.ptr(coff, C.c_uint64), n_scripts, int(length), int(min_works), int(max_share),
+            works.ctypes.data_as(C.c_void_p), g, cap_g, p, cap_p, f, cap_f, got_g, got_p, got_f,
+            C.byref(n_pos), C.byref(n_dist)),
+        [abi.FANON_GRAM_DTYPE, abi.FANON_PASSAGE_DTYPE, abi.FANON_PHRASE_DTYPE],
+        [1024, 1024, 1024], "fs_fanon")
+    return works[:n_works], grams, passages, phrases, {'positions': int(n_pos.value),
+                                                       'distinct': int(n_dist.value)}
+
+
+def fanon_device(tok_ptr, n_tok, work_off_ptr, n_works, n_ids, canon_ptr=0, n_canon=0,
+                 canon_off_ptr=0, n_scripts=0, length=8, min_works=2, max_share=100, device=0,
+                 out_ptrs=None, caps=None, totals=None):
+    """`fanon` over device-resident ids and offsets (fs_fanon_dev).  Without `out_ptrs`: (works,
+    grams, passages, phrases) as host arrays, from buffers of torch's that grow until the call
+    fits.  With `out_ptrs` = device addresses (works, grams, passages, phrases; the last three
+    of `caps` records): (grams, passages, phrases) as counts; FsError(FS_E_CAPACITY) with
+    .required = the three counts when a buffer is too small.  `totals`, a dict, receives
+    'positions' and 'distinct'."""
+    L = _lib.load()
+    n_pos, n_dist = C.c_uint64(0), C.c_uint64(0)
+
+    def call(fixed, grown, caps, counts):
+        rc = L.fs_fanon_dev(int(device), C.c_void_p(tok_ptr), int(n_tok),
+                            C.c_void_p(work_off_ptr), int(n_works), int(n_ids),
+                            C.c_void_p(canon_ptr or None), int(n_canon),
+                            C.c_void_p(canon_off_ptr or None), int(n_scripts), int(length),
+                            int(min_works), int(max_share), C.c_void_p(fixed[0]),
+                            C.c_void_p(grown[0]), int(caps[0]), C.c_void_p(grown[1]),
+                            int(caps[1]), C.c_void_p(grown[2]), int(caps[2]),
+                            C.byref(counts[0]), C.byref(counts[1]), C.byref(counts[2]),
+                            C.byref(n_pos), C.byref(n_dist))
+        if totals is not None:
+            totals['positions'], totals['distinct'] = int(n_pos.value), int(n_dist.value)
+        return rc
+    caps = [int(c) for c in caps] if caps is not None else [0 if out_ptrs is not None else 1024] * 3
+    return _rows_call("fs_fanon_dev", call, [(n_works, abi.FANON_WORK_DTYPE)],
+                      [abi.FANON_GRAM_DTYPE, abi.FANON_PASSAGE_DTYPE, abi.FANON_PHRASE_DTYPE],
+                      caps, out_ptrs, "gram, passage or phrase buffer too small")

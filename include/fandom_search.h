@@ -2506,6 +2506,106 @@ int fs_csvw_format(fs_csvw* w, const fs_row* rows, uint64_t n_rows,
                    const uint8_t* name_bytes, const uint64_t* name_off, uint64_t n_works,
                    const uint32_t* fan_sid, const uint8_t** out, uint64_t* out_len);
 
+/* `ao3.py fanon`: the phrases fan works share with each other and the script lacks.  The one
+ * command that reads the corpus itself and no match records.  The fan tokens are dense ids
+ * below n_ids, tok[work_off[w] .. work_off[w + 1]) those of work w; the scripts are ids of the
+ * same numbering, canon[canon_off[s] .. canon_off[s + 1]) those of script s, FS_FANON_NO_ID for a
+ * word no fan token equals.  With K = k:
+ *  - Position p of a work of L tokens has a gram when p + K <= L: its K ids from p on.  A gram
+ *    never spans two works.  occurrences(g) = positions holding g, works(g) = different works
+ *    with one, first(g) = the smallest (work, p).
+ *  - g is canon when its K ids stand consecutively inside one script; common when works(g) * 100
+ *    > max_share * n_works (64-bit; n_works counts empty works too); shared when works(g) >=
+ *    min_works and it is neither.  Canon and common do not exclude each other.
+ *  - A passage is a maximal run of positions p..q of one work that all hold shared grams: tokens
+ *    p .. q + K - 1, n_tokens = q - p + K; least and most = the smallest and largest works(g)
+ *    of its grams.  Two passages are one phrase when their id sequences are equal, compared id
+ *    by id; a phrase's first is the smallest (work, p) of its passages.
+ *  - shared_tokens (canon_tokens) of a work = its tokens inside the gram of at least one shared
+ *    (canon) position: a union, overlapping grams count a token once.
+ * Every output is an integer; grams are told apart by comparing ids, never by hash alone. */
+typedef struct fs_fanon_work {
+  uint32_t n_tokens, n_positions;      /* positions: those with a gram                       */
+  uint32_t shared_positions, canon_positions, common_positions;
+  uint32_t n_passages;
+  uint32_t shared_tokens, canon_tokens;
+  uint32_t longest_start;              /* its longest passage, the first among equals: token */
+  uint32_t longest_tokens;             /* index in the work and n_tokens; 0, 0 without one   */
+} fs_fanon_work;                       /* 40 bytes                                           */
+
+typedef struct fs_fanon_gram {
+  uint32_t work, start;                /* first(g): work and token index in it               */
+  uint32_t works, occurrences;
+} fs_fanon_gram;                       /* 16 bytes                                           */
+
+typedef struct fs_fanon_passage {
+  uint32_t work, start, n_tokens;      /* start: token index in the work                     */
+  uint32_t phrase;                     /* index into the phrases                             */
+  uint32_t least, most;
+} fs_fanon_passage;                    /* 24 bytes                                           */
+
+typedef struct fs_fanon_phrase {
+  uint32_t work, start;                /* first: work and token index in it                  */
+  uint32_t n_tokens, n_passages, n_works;
+  uint32_t least, most;
+  uint32_t reserved;                   /* 0                                                  */
+} fs_fanon_phrase;                     /* 32 bytes                                           */
+
+#define FS_FANON_NO_ID 0xFFFFFFFFu     /* a script word that is no fan token                 */
+#define FS_FANON_MIN_LENGTH 2u
+#define FS_FANON_MAX_LENGTH 32u
+#define FS_FANON_TILE 256u             /* positions a workgroup of the gram pass hashes      */
+/* Counted per token of the corpus: 4 bytes (its gram's slot), 1 byte (its flags) and 2 bits
+ * (the two cover masks); per slot of the gram table, S1 = the power of two at or above twice
+ * the positions plus the scripts' grams, FS_FANON_SLOT_BYTES bytes (key, first, occurrences,
+ * works, canon); per slot of the (gram, work) set, the power of two at or above twice the
+ * positions, 8 bytes: between 63 and 121 bytes per token.  Once the passages are known: 20 bytes
+ * per passage, and per slot of the phrase tables (the power of two at or above twice the
+ * passages) FS_FANON_PHRASE_SLOT_BYTES bytes.  Their sum may be up to FS_FANON_MAX_BYTES, 8 GiB
+ * where the siblings take 1 GiB because here the corpus itself is the input; the environment's
+ * FS_FANON_MAX_BYTES replaces it. */
+#define FS_FANON_SLOT_BYTES 21u
+#define FS_FANON_PHRASE_SLOT_BYTES 32u
+#define FS_FANON_MAX_BYTES (8ull << 30)
+
+/* Host buffers in; n_works work records, up to cap_grams shared grams in order of first, up to
+ * cap_passages passages in corpus order and up to cap_phrases phrases in order of first out, on
+ * HIP device `device`.  n_positions and n_distinct (the positions with a gram and the distinct
+ * grams of the fan works) may be null.  Both entry points: FS_E_INVALID for null arguments, k
+ * outside FS_FANON_MIN_LENGTH..FS_FANON_MAX_LENGTH, min_works == 0, max_share outside 1..100,
+ * a tok[i] >= n_ids, a canon id that is neither below n_ids nor FS_FANON_NO_ID, or offsets that
+ * do not ascend from 0; FS_E_UNSUPPORTED for 2^32 tokens or more (script words included) or
+ * tables above FS_FANON_MAX_BYTES (the message names the bytes needed and says to lower -n);
+ * FS_E_CAPACITY with the three counts filled in when a cap is too small (the three buffers
+ * untouched then, works complete).  A corpus without a position: n_tokens in the work records,
+ * everything else 0, no kernel runs.
+ * The environment's FS_FANON_HASH_BITS=k (a diagnostic, read once per call) keeps k bits of both
+ * hashes (0: every key probes from slot 0); the output is the same. */
+int fs_fanon(int device, const uint32_t* tok, const uint64_t* work_off, uint32_t n_works,
+             uint32_t n_ids, const uint32_t* canon, const uint64_t* canon_off,
+             uint32_t n_scripts, uint32_t k, uint32_t min_works, uint32_t max_share,
+             fs_fanon_work* works, fs_fanon_gram* grams, uint64_t cap_grams,
+             fs_fanon_passage* passages, uint64_t cap_passages, fs_fanon_phrase* phrases,
+             uint64_t cap_phrases, uint64_t* n_grams, uint64_t* n_passages, uint64_t* n_phrases,
+             uint64_t* n_positions, uint64_t* n_distinct);
+/* The same over device-resident ids and offsets (n_tok = d_work_off[n_works] and n_canon =
+ * d_canon_off[n_scripts] say how many ids the two buffers hold) into device buffers; returns
+ * when they are written. */
+int fs_fanon_dev(int device, const uint32_t* d_tok, uint64_t n_tok, const uint64_t* d_work_off,
+                 uint32_t n_works, uint32_t n_ids, const uint32_t* d_canon, uint64_t n_canon,
+                 const uint64_t* d_canon_off, uint32_t n_scripts, uint32_t k, uint32_t min_works,
+                 uint32_t max_share, fs_fanon_work* d_works, fs_fanon_gram* d_grams,
+                 uint64_t cap_grams, fs_fanon_passage* d_passages, uint64_t cap_passages,
+                 fs_fanon_phrase* d_phrases, uint64_t cap_phrases, uint64_t* n_grams,
+                 uint64_t* n_passages, uint64_t* n_phrases, uint64_t* n_positions,
+                 uint64_t* n_distinct);
+/* HIP-event milliseconds of the last fs_fanon / fs_fanon_dev call on this thread: insert (the
+ * scripts' grams, then every position hashed and entered), flag (flags, cover masks, run heads
+ * and their scans), phrases (least, most, the phrase table), place (the phrase order and the
+ * gram, passage and phrase records), works (the work records), copy out, and the total of the
+ * six; 0 for a pass that did not run.  tools/fanon_bench.py. */
+int fs_fanon_times(double* ms);
+
 /* Diagnostics (FS_DIAG=2 in the environment at fs_index_create): per wave range of the
  * last k_scan_rows launch on stream `lane`, eight uint64 {entry, filter staged, scan done,
  * rounds done, finished (ticks of the 100 MHz constant clock), rounds, flushes, records}.
